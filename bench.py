@@ -80,6 +80,7 @@ VALU_PEAK_TFLOPS = 78.6        # 157.3 TF packed-FMA spec / 2: separate mul/add,
 FLOP_PER_BLOCK_ITER = {0: 75e3, 1: 130e3}   # q3 / q4 (DIAGONALS)
 ALGO_BYTES_PER_BLOCK_ITER = 256
 RESIDENT_BUDGET = 64 << 30     # HBM the resident input planes of all steps may take
+DUMP_BUDGET = 48 << 20         # bytes the --dump-outputs files of all ranks may take together
 
 
 KERNEL_SOURCES = ("qs_kernels.hip", "qs_smooth_kernel.inc", "qs_smooth_dp_kernel.inc", "qs_devfn.h", "qs_device.h", "qs_launch.h",
@@ -142,6 +143,9 @@ def parse_args():
     ap.add_argument("--edge-first", action="store_true",
                     help="N > 1: also time the single image on the latency-hiding band schedule (bands.run_band_edge_first): edge rows + "
                          "exchange on a side stream, interior rows on the main stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of blocks where the whole would exceed the budget, see dump_outputs)")
     ap.add_argument("--print-kernel-hash", action="store_true", help="print kernel_sources_sha1() (what profiles/pmc_traffic.json is tied to) and exit")
     a = ap.parse_args()
     if a.print_kernel_hash:
@@ -501,6 +505,28 @@ def _max_over_ranks(torch, dist, world, elapsed, dev, backend):
     return elapsed
 
 
+def dump_outputs(args, torch, rank, world, arrays):
+    """--dump-outputs DIR: the coefficients the timed path computed in its last step, for comparing two builds output for
+    output (the inputs are the same on every run with the same arguments).  `arrays`: name -> int16 tensor
+    [hblk, wblk, 64].  Each is written as DIR/<name>.npy in float32 (exact for int16); one larger than its share of
+    DUMP_BUDGET is cut to a fixed, seeded sample of whole blocks, [k, 64], whose flat block indices go to
+    DIR/<name>_blocks.npy (float64).  N > 1: every rank writes its own band, the names prefixed with rank<r>_."""
+    out = Path(args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    share = DUMP_BUDGET // (world * len(arrays))
+    for name, t in arrays.items():
+        flat = t.reshape(-1, 64)
+        k = share // (2 * 64 * 4)           # (the sample's float32 rows and its float64 indices)
+        if flat.shape[0] * 64 * 4 <= share:
+            np.save(out / f"{prefix}{name}.npy", t.cpu().numpy().astype(np.float32))
+            continue
+        idx = np.sort(np.random.default_rng(20240601).choice(flat.shape[0], size=k, replace=False))
+        sample = flat[torch.from_numpy(idx).to(t.device)].cpu().numpy().astype(np.float32)
+        np.save(out / f"{prefix}{name}.npy", sample)
+        np.save(out / f"{prefix}{name}_blocks.npy", idx.astype(np.float64))
+
+
 def _batch_size(args, nsteps, bytes_per_plane):
     want = args.batch if args.batch > 0 else 12
     return max(1, min(want, RESIDENT_BUDGET // max(1, nsteps * bytes_per_plane)))
@@ -738,6 +764,8 @@ def run_luma(c):
     last = work[-1][-1]                                   # the last plane of the last timed step
     # every plane of the last timed step must be the same result (they had the same input)
     planes_identical = all(bool(torch.equal(work[-1][0], p)) for p in work[-1][1:])
+    if args.dump_outputs:
+        dump_outputs(args, torch, rank, world, {f"coefs_plane{b:02d}": p for b, p in enumerate(work[-1])})
 
     # ---- extra legs (not part of `value`) ------------------------------------------------------------------
     single_plane_ms = value_batch1 = smooth_res = deep_res = edge_res = None
@@ -1000,6 +1028,10 @@ def run_colour(c):
     elapsed = _max_over_ranks(torch, dist, world, time.perf_counter() - t0, dev, args.backend)
     for e in band.eng:
         assert not e.bad_coef(), "range check tripped on synthetic input"
+    if args.dump_outputs:
+        # the last image of the last timed step (the upsampled chroma of the others is not kept)
+        dump_outputs(args, torch, rank, world, {"Y": band.eng[0].coef, **{name: band.up[ci - 1] if band.up[ci - 1] is not None else band.eng[ci].coef
+                                                                           for ci, name in ((1, "Cb"), (2, "Cr"))}})
     res = dict(elapsed=elapsed, batch=batch, total_blocks=total_blocks_img * batch,
                blocks_per_gpu=sum(int(t.shape[0] * t.shape[1]) for t in mine),
                kernel=f"qs_smooth_plane_kernel<{'true' if flags & 1 else 'false'}> (luma plane)",

@@ -46,9 +46,20 @@ def build_oracle() -> Path:
     return HERE / "libqs_oracle.so"
 
 
+REF_SRC = Path("/root/reference")   # oracle/Makefile: REF
+
+
+def reference_sources_available() -> bool:
+    """the reference's sources can be read here (a directory this user may not enter counts as absent)"""
+    try:
+        return (REF_SRC / "quantsmooth.h").is_file() and os.access(REF_SRC / "quantsmooth.h", os.R_OK)
+    except OSError:
+        return False
+
+
 def build_ref() -> bool:
     """compile oracle/_ref/*.so when /root/reference is mounted (build box only)."""
-    if not Path("/root/reference/quantsmooth.h").exists():
+    if not reference_sources_available():
         return False
     subprocess.run(["make", "-s", "-C", str(HERE), "ref"], check=True)
     return True
@@ -285,6 +296,103 @@ class Reference(_Lib):
         self._block(c.ctypes.data_as(C.POINTER(C.c_int16)), q.ctypes.data_as(C.POINTER(C.c_uint16)),
                     plane.ctypes.data + off, p2, stride, flags, luma)
         return c
+
+
+RECORDED = HERE.parent / "tests" / "golden" / "reference_calls.json.gz"
+
+
+def _feed(h, v):
+    """canonical, type-tagged serialisation of call arguments and results into a hash"""
+    if isinstance(v, np.ndarray):
+        a = np.ascontiguousarray(v)
+        h.update(f"nd{a.dtype.str}{a.shape}".encode()); h.update(a.tobytes())
+    elif isinstance(v, dict):
+        h.update(b"{")
+        for k in sorted(v):
+            _feed(h, k); _feed(h, v[k])
+        h.update(b"}")
+    elif isinstance(v, (list, tuple)):
+        h.update(b"[%d" % len(v))
+        for x in v:
+            _feed(h, x)
+        h.update(b"]")
+    elif callable(v):
+        h.update(b"callable")
+    elif isinstance(v, np.generic):
+        _feed(h, v.item())
+    else:
+        h.update(f"{type(v).__name__}:{v!r};".encode())
+
+
+def _digest(v) -> str:
+    import hashlib
+    h = hashlib.sha256()
+    _feed(h, v)
+    return h.hexdigest()[:32]
+
+
+class RecordedReference:
+    """The compiled reference's answers where oracle/_ref cannot be built (its sources are not part of this repository).
+
+    Every call runs the oracle port and asserts that the result -- with the (cur, max, return) sequence the progress
+    callback saw -- has the digest the compiled reference's result had for the same arguments, recorded in
+    tests/golden/reference_calls.json.gz; it then returns the port's result, equal to the reference's by that digest.
+    A call that was never recorded fails.  With `live` (a Reference) the calls go to it and their digests are recorded
+    instead; save() merges them into the file (QS_RECORD_REFERENCE=1, see tests/conftest.py)."""
+
+    METHODS = ("do_quantsmooth", "idct_islow", "idct_float", "fdct_float", "tables", "block")
+
+    def __init__(self, live: Reference | None = None, path: Path = RECORDED):
+        self.live, self.path, self.new = live, Path(path), {}
+        self.impl = live or Oracle()
+        self.variant = live.variant if live else "none"
+        self.known = self._load()
+
+    def _load(self):
+        import gzip
+        import json
+        if not self.path.exists():
+            return {}
+        with gzip.open(self.path, "rt") as f:
+            return json.load(f)
+
+    def save(self):
+        import gzip
+        import json
+        merged = {**self._load(), **self.new}
+        with gzip.GzipFile(self.path, "wb", mtime=0) as f:
+            f.write(json.dumps(merged, sort_keys=True, separators=(",", ":")).encode())
+
+    def quantval192(self, q):
+        return Reference.quantval192(q)
+
+    def __getattr__(self, name):
+        if name not in self.METHODS:
+            raise AttributeError(name)
+        method = getattr(self.impl, name)
+
+        def call(*args, **kw):
+            args_kw = [name, list(args), kw]
+            trace = []
+            user = kw.get("progress")
+            if user is not None:
+                def progress(u, cur, mx):
+                    r = user(u, cur, mx)
+                    trace.append((cur, mx, int(r or 0)))
+                    return r
+                kw = dict(kw, progress=progress)
+            res = method(*args, **kw)
+            # what the callback returned is an input of the call as much as its arguments (a non-zero return cancels)
+            key = _digest(args_kw + [[r for _, _, r in trace]])
+            got = _digest([res, trace])
+            if self.live is not None:
+                self.new[key] = got
+            else:
+                want = self.known.get(key)
+                assert want is not None, f"reference.{name}: these arguments were never recorded ({self.path.name})"
+                assert got == want, f"reference.{name}: the oracle port differs from the recorded reference result"
+            return res
+        return call
 
 
 def verify_bands(oracle, coef_in, quant, flags, niter, got, rows=16, luma=True):

@@ -51,12 +51,20 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """the compiled unmodified reference (oracle/_ref); only where it was built"""
+    """the compiled unmodified reference (oracle/_ref) where it was built; elsewhere its recorded answers: the oracle
+    port, certified call by call against digests of the compiled reference's results (oracle.RecordedReference).
+    QS_RECORD_REFERENCE=1 (with oracle/_ref built) rewrites those digests from the compiled reference."""
     from oracle import oracle as om
     if not om.have_ref("none"):
-        if not om.build_ref():
-            pytest.skip("oracle/_ref not built and /root/reference not mounted")
-    return om.Reference("none")
+        om.build_ref()
+    if not om.have_ref("none"):
+        yield om.RecordedReference()
+    elif os.environ.get("QS_RECORD_REFERENCE") == "1":
+        rec = om.RecordedReference(live=om.Reference("none"))
+        yield rec
+        rec.save()
+    else:
+        yield om.Reference("none")
 
 
 @pytest.fixture(scope="session")

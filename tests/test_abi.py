@@ -181,8 +181,9 @@ def test_turbo_branch_of_the_shim_compiles_and_matches_reference_layout(turbo_nu
             f"-I{JPEGINC}", f"-DQS_STUB_TURBO_NUMBER={turbo_number}"]
     r = subprocess.run(base + [str(CSRC / "jpegqs_shim.c")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    if Path("/root/reference/quantsmooth.h").exists():
-        r = subprocess.run(base + ["-I/root/reference", f"-I{CSRC}", "-DNO_SIMD", "-w",
+    from oracle import oracle as om
+    if om.reference_sources_available():
+        r = subprocess.run(base + [f"-I{om.REF_SRC}", f"-I{CSRC}", "-DNO_SIMD", "-w",
                                    str(ROOT / "tests" / "stubs" / "turbo_layout_check.c")], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
 

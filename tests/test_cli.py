@@ -131,16 +131,13 @@ def test_cli_8192_gray_matches_reference_cli_bytes(gpu, tmp_path, gray8192_jpeg,
     byte for byte what the reference's own CLI (scalar build, OpenMP) writes for the same file -- i.e. all
     1,048,576 blocks equal (reference quantsmooth.c:548-596, quantsmooth.h:1517-1549)"""
     _need_cli()
-    ref_cli = ROOT / "oracle" / "_ref" / "jpegqs_ref_none"
-    if not ref_cli.exists():
-        pytest.skip("oracle/_ref/jpegqs_ref_none did not travel with the tree")
     ours, ref = tmp_path / "ours.jpg", tmp_path / "ref.jpg"
     r = subprocess.run([str(CLI), "-q", str(quality), "-i", "8", str(gray8192_jpeg), str(ours)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r2 = subprocess.run([str(ref_cli), "-q", str(quality), "-i", "0", str(gray8192_jpeg), str(ref)], capture_output=True, text=True)
-    assert r2.returncode == 0, r2.stderr
-    a, b = ours.read_bytes(), ref.read_bytes()
-    assert len(a) > 1 << 20 and a == b, f"outputs differ ({len(a)} vs {len(b)} bytes)"
+    r2_rc, r2_err, b = _RefCli().run(["-q", str(quality), "-i", "0", gray8192_jpeg, ref], out=ref)
+    assert r2_rc == 0, r2_err
+    a = ours.read_bytes()
+    assert len(a) > 1 << 20 and _sha(ours) == b, f"outputs differ ({len(a)} bytes, sha256 {_sha(ours)} vs {b})"
 
 
 # ---- decode-mode API (jpegqs_start_decompress / jpegqs_finish_decompress) -------
@@ -208,6 +205,53 @@ def _built(name):
     return p
 
 
+REF_CLI_RECORD = GOLD / "jpegqs_ref_none.json"
+
+
+class _RefCli:
+    """The reference's own CLI (oracle/_ref/jpegqs_ref_none, scalar build) where it was built; elsewhere what it did,
+    recorded in tests/golden/cli/jpegqs_ref_none.json: exit status, stderr and a digest of the file it wrote, per argument
+    list (input files by a digest of their content).  QS_RECORD_REFERENCE=1 with the binary built rewrites the record."""
+
+    def __init__(self):
+        import json
+        self.exe = REFDIR / "jpegqs_ref_none"
+        self.known = json.loads(REF_CLI_RECORD.read_text()) if REF_CLI_RECORD.exists() else {}
+
+    @staticmethod
+    def _key(args, out):
+        import hashlib
+        import json
+        key = ["out" if a == str(out) else "file:" + hashlib.sha256(Path(a).read_bytes()).hexdigest()[:32]
+               if "/" in a and Path(a).is_file() else a for a in args]
+        return json.dumps(key)
+
+    def run(self, args, out=None):
+        """-> (exit status, stderr, sha256 of `out` or None when it was not written)"""
+        import hashlib
+        import json
+        import os
+        args = [str(a) for a in args]
+        key = self._key(args, out)
+        if not self.exe.exists():
+            if key not in self.known:
+                pytest.fail(f"jpegqs_ref_none was not built and {key} is not in {REF_CLI_RECORD.name}")
+            rec = self.known[key]
+            return rec["rc"], rec["stderr"], rec["out"]
+        r = subprocess.run([str(self.exe), *args], capture_output=True, text=True)
+        got = (r.returncode, r.stderr, hashlib.sha256(Path(out).read_bytes()).hexdigest() if out and Path(out).exists() else None)
+        if os.environ.get("QS_RECORD_REFERENCE") == "1":
+            known = json.loads(REF_CLI_RECORD.read_text()) if REF_CLI_RECORD.exists() else {}
+            known[key] = dict(rc=got[0], stderr=got[1], out=got[2])
+            REF_CLI_RECORD.write_text(json.dumps(known, indent=1, sort_keys=True) + "\n")
+        return got
+
+
+def _sha(path):
+    import hashlib
+    return hashlib.sha256(Path(path).read_bytes()).hexdigest()
+
+
 def _no_noise(text):
     """stderr minus what is not the CLI's: the CPU back end's announcement (no-GPU boxes), a ROCm data-file notice"""
     return [l for l in text.splitlines() if "using the CPU back end" not in l and "amdgpu.ids" not in l]
@@ -218,20 +262,20 @@ def test_cli_verbose_banner_equals_the_reference_cli(tmp_path):
     trace level; without file arguments it stops there with status 1 and NO usage text.  Line for line what the
     reference's own CLI prints (both link the same libjpeg)."""
     _need_cli()
-    ref_cli = _built("jpegqs_ref_none")
+    ref_cli = _RefCli()
     for args in (["-v", "1"], ["--verbose", "3"], ["-v2"]):
         a = subprocess.run([str(CLI), *args], capture_output=True, text=True)
-        b = subprocess.run([str(ref_cli), *args], capture_output=True, text=True)
-        assert a.returncode == b.returncode == 1
-        assert a.stderr == b.stderr and "Compiled with libjpeg" in a.stderr and "Usage" not in a.stderr
+        b_rc, b_err, _ = ref_cli.run(args)
+        assert a.returncode == b_rc == 1
+        assert a.stderr == b_err and "Compiled with libjpeg" in a.stderr and "Usage" not in a.stderr
     # with files: banner + libjpeg's own trace output at level n - 1, identical too
     for level in ("1", "2"):
         oa, ob = tmp_path / "a.jpg", tmp_path / "b.jpg"
         a = subprocess.run([str(CLI), "-v", level, "-q", "3", "-n", "0", "-i", "0", str(GOLD / "gray64.jpg"), str(oa)], capture_output=True, text=True)
-        b = subprocess.run([str(ref_cli), "-v", level, "-q", "3", "-n", "0", "-i", "0", str(GOLD / "gray64.jpg"), str(ob)], capture_output=True, text=True)
-        assert a.returncode == b.returncode == 0
-        assert _no_noise(a.stderr) == _no_noise(b.stderr)
-        assert oa.read_bytes() == ob.read_bytes()
+        b_rc, b_err, b_out = ref_cli.run(["-v", level, "-q", "3", "-n", "0", "-i", "0", GOLD / "gray64.jpg", ob], out=ob)
+        assert a.returncode == b_rc == 0
+        assert _no_noise(a.stderr) == _no_noise(b_err)
+        assert _sha(oa) == b_out
     # -v 0 is silent, and the usage text still comes for a wrong argument count
     r = subprocess.run([str(CLI), "-v", "0"], capture_output=True, text=True)
     assert r.returncode == 1 and "Usage:" in r.stderr and "Compiled with" not in r.stderr
@@ -250,11 +294,11 @@ def _exit2_case(exe, ref_cli, tmp_path, env=None):
         for quality in ("3", "6"):
             oa, ob = tmp_path / "a.jpg", tmp_path / "b.jpg"
             a = subprocess.run([str(exe), "-q", quality, "-i", "0", str(t), str(oa)], capture_output=True, text=True, env=env)
-            b = subprocess.run([str(ref_cli), "-q", quality, "-i", "0", str(t), str(ob)], capture_output=True, text=True)
-            assert a.returncode == b.returncode == 2, (a.returncode, b.returncode, a.stderr)
+            b_rc, b_err, b_out = ref_cli.run(["-q", quality, "-i", "0", t, ob], out=ob)
+            assert a.returncode == b_rc == 2, (a.returncode, b_rc, a.stderr)
             assert "Premature end of JPEG file" in a.stderr
-            assert _no_noise(a.stderr) == _no_noise(b.stderr)
-            assert oa.read_bytes() == ob.read_bytes(), (src, quality)
+            assert _no_noise(a.stderr) == _no_noise(b_err)
+            assert _sha(oa) == b_out, (src, quality)
 
 
 def test_cli_exit_code_2_on_libjpeg_warnings(tmp_path):
@@ -262,15 +306,15 @@ def test_cli_exit_code_2_on_libjpeg_warnings(tmp_path):
     with exit status 2 -- same status, same stderr and same output bytes as the reference's CLI.  Runs on whatever back
     end this box has (the GPU box: the GPU; the build container: the CPU back end)."""
     _need_cli()
-    _exit2_case(CLI, _built("jpegqs_ref_none"), tmp_path)
+    _exit2_case(CLI, _RefCli(), tmp_path)
 
 
 @pytest.mark.gpu
 def test_gpu_cli_exit_code_2_on_libjpeg_warnings(gpu, tmp_path):
     import os
     _need_cli()
-    _exit2_case(CLI, _built("jpegqs_ref_none"), tmp_path, env=dict(os.environ, JPEGQS_BACKEND="hip"))
-    _exit2_case(_built("jpegqs_dropin"), _built("jpegqs_ref_none"), tmp_path, env=dict(os.environ, JPEGQS_BACKEND="hip"))
+    _exit2_case(CLI, _RefCli(), tmp_path, env=dict(os.environ, JPEGQS_BACKEND="hip"))
+    _exit2_case(_built("jpegqs_dropin"), _RefCli(), tmp_path, env=dict(os.environ, JPEGQS_BACKEND="hip"))
 
 
 CLI_GOLDEN_CASES = ([(src, ["-q", str(q), "-n", "3"], f"{src}.q{q}.ref.jpg")

@@ -37,7 +37,8 @@ def cpu():
 def _dropin(name):
     p = REFDIR / name
     if not p.exists():
-        if Path("/root/reference/quantsmooth.c").exists():
+        from oracle import oracle as om
+        if om.reference_sources_available():
             subprocess.run(["make", "-s", "-C", str(ROOT / "oracle"), "dropin"], check=True)
         if not p.exists():
             pytest.skip(f"{p} not built and /root/reference not mounted")

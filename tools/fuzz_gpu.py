@@ -74,12 +74,20 @@ def kwargs(j):
 
 
 if mode == "gen":
-    from oracle.oracle import Oracle, Reference, have_ref   # the replay side (`run`) never touches the oracle
+    from oracle.oracle import Oracle, RecordedReference, Reference, have_ref   # the replay side (`run`) never touches the oracle
     # FUZZ_TRUTH=ref: the expected hashes come from the COMPILED, UNMODIFIED reference (oracle/_ref/libqsref_none.so) instead
     # of the plain-C port -- slower, and how the committed corpus was re-derived in round 6 (identical file: the port is
-    # pinned to the reference on CPU, this shows it on the corpus itself)
+    # pinned to the reference on CPU, this shows it on the corpus itself).  Without oracle/_ref: its recorded results
+    # (the port, checked job by job against them); QS_RECORD_REFERENCE=1 records them from oracle/_ref.
     import os
-    oracle = Reference("none") if os.environ.get("FUZZ_TRUTH") == "ref" and have_ref("none") else Oracle()
+    oracle = Oracle()
+    if os.environ.get("FUZZ_TRUTH") == "ref":
+        if not have_ref("none"):
+            oracle = RecordedReference()
+        elif os.environ.get("QS_RECORD_REFERENCE") == "1":
+            oracle = RecordedReference(live=Reference("none"))
+        else:
+            oracle = Reference("none")
     print("gen: truth =", type(oracle).__name__)
     ntrials = int(sys.argv[3]); seed0 = int(sys.argv[4]) if len(sys.argv) > 4 else 1
     t0 = time.time()
@@ -90,6 +98,8 @@ if mode == "gen":
             f.write(json.dumps(dict(seed0=seed0, trial=trial, flags=flags, niter=niter, batch=is_batch,
                                     desc=[d for _, d in made], expect=exp)) + "\n")
             f.flush()
+    if isinstance(oracle, RecordedReference) and oracle.live is not None:
+        oracle.save()
     print(f"gen: {ntrials} trials in {time.time() - t0:.0f} s -> {path}")
     sys.exit(0)
 
