@@ -17,6 +17,10 @@
  *     in HBM (bench.py, the multi-GPU band driver, pipelines that decode on the
  *     GPU).  One call = one kernel launch, asynchronous on `stream`.
  *
+ *  3. DEVICE JOB  qs_hip_do_quantsmooth_device(): the whole job of layer 1 on
+ *     DEVICE arrays, enqueued on one stream without any host synchronisation
+ *     (graph-capturable); the range-check stop is decided on the device.
+ *
  * All functions return 0 on success and a negative QS_HIP_E* code on failure;
  * qs_hip_last_error() gives the message.  There is no CPU fallback: without a
  * usable HIP device every compute entry point fails with QS_HIP_ENODEV.
@@ -170,6 +174,44 @@ int qs_hip_progress_calls(const qs_hip_job *geometry, int niter, int progprec, i
  * call waits for a prewarm still in flight.  Not in the reference API. */
 int qs_hip_prewarm(const qs_hip_job *geometry, int flags, int niter);
 
+/* ---- device-resident job (whole do_quantsmooth on DEVICE arrays, one stream) ----
+ * The job layer above on coefficient arrays that already live in device memory (a GPU JPEG decoder, a PyTorch
+ * pipeline): the same semantics bit for bit -- every flag combination, the refresh-only passes, the place of the
+ * +-1023 clamp, JOINT_YUV / UPSAMPLE_UV, LOW_QUALITY and the reference's stop rules (quantsmooth.h:2404-2878).
+ * Three calls:
+ *   info     geometry + quant tables + flags + niter -> what the job needs (host only, no device touched);
+ *   prepare  writes the per-component constant blocks into the caller's device workspace; may synchronise `stream`,
+ *            so it is called outside any graph capture, once per geometry + table set + flags + niter;
+ *   run      ENQUEUES the job on `stream` and returns: no allocation, no synchronisation, no event or stream creation
+ *            or query, no other stream (a capture of it is a linear graph), no copy from host memory, no buffer pool,
+ *            no progress callback.  Graph-capturable.
+ * The workspace (device memory, info.workspace_bytes, caller-owned) holds the pixel planes, the constants, the
+ * range-check word and a snapshot of the input; one job at a time may use it.  Its layout is a function of the job
+ * and flags alone, so a run must see the geometry, tables, flags and niter its prepare saw.  The workspace is 256-byte
+ * aligned, the coefficient arrays 16-byte aligned (what hipMalloc and torch's allocator hand out).
+ * The range-check stop (reference :2596-2610) is decided on the device: a precheck kernel snapshots the input and
+ * runs the reference's test before any pass; a fix-up kernel after the last pass rebuilds the reference's result
+ * from the snapshot when a component tripped.  *d_stop (device int32) receives the reference's return value once
+ * the stream reaches the end of the job. */
+typedef struct {
+	size_t workspace_bytes;      /* device workspace the run needs (planes, constants, snapshot, range-check word) */
+	int32_t up_wblk, up_hblk;    /* UPSAMPLE_UV: geometry of the two replacement chroma arrays, else 0 */
+	int32_t out_hsamp0, out_vsamp0;   /* component 0 sampling factors of the result (1 x 1 when chroma is replaced) */
+	int32_t static_stop;         /* 1 when the quant tables alone decide stop (a value >= 0x800, reference :2504) */
+} qs_hip_device_info;
+/* No device needed.  QS_HIP_EINVAL for a bad job. */
+int qs_hip_device_job_info(const qs_hip_job *job, int flags, int niter, qs_hip_device_info *out);
+int qs_hip_device_job_prepare(const qs_hip_job *job, int flags, int niter, void *d_workspace, size_t bytes, void *stream);
+/* job->coef[ci] are DEVICE arrays of hblk * wblk * 64 JCOEF, rewritten in place.  When info.up_wblk > 0,
+ * job->coef_up[0..1] must be caller-allocated DEVICE arrays of up_hblk * up_wblk * 64 JCOEF: they receive the
+ * replacement chroma.  On return job->up_wblk / up_hblk / out_hsamp0 / out_vsamp0 are info's values and the quant
+ * tables are set to 1 (as qs_hip_do_quantsmooth does); all of that, and coef_up, describes the result only when
+ * *d_stop reads 0 -- when it reads 1 the reference drops the replacement chroma (:2835) and component 0 keeps its
+ * sampling factors.  Returns 0 when the job was enqueued; QS_HIP_EINVAL for a short workspace, null pointers or
+ * missing coef_up arrays; QS_HIP_ENODEV without a device. */
+int qs_hip_do_quantsmooth_device(qs_hip_job *job, int flags, int niter, void *d_workspace, size_t bytes,
+		int32_t *d_stop, void *stream);
+
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up
  * to 2 GiB) and HIP streams in process-wide caches, each entry tied to the device it was created
@@ -187,9 +229,10 @@ int qs_hip_device_count(void);
 const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
- * additions only: qs_hip_set_shard_schedule, the RCCL band entry points).  A caller built against
+ * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
+ * qs_hip_device_info and its three calls).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
-#define QS_HIP_ABI_VERSION 6
+#define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);
 
 /* bytes of the per-component constant block; pixel-plane pitch and size */

@@ -7,8 +7,11 @@ and provides seeded synthetic inputs.  There is no CPU compute path here: if
 the library is missing, loading fails loudly.
 """
 from . import synth  # noqa: F401
+from . import torch_qs  # noqa: F401  (imports torch on first use only)
 from .hipqs import (  # noqa: F401
     FLAGS, HipQS, QsHipError, flags_for_quality, lib_path, load_library,
 )
 
-__all__ = ["synth", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]
+from .torch_qs import quantsmooth_  # noqa: F401
+
+__all__ = ["synth", "torch_qs", "quantsmooth_", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]

@@ -79,6 +79,12 @@ class PlaneRefs:
         return self.arr[i]
 
 
+class DeviceInfo(C.Structure):
+    """qs_hip_device_info: what a device-resident job needs (qs_hip_device_job_info)"""
+    _fields_ = [("workspace_bytes", C.c_size_t), ("up_wblk", C.c_int32), ("up_hblk", C.c_int32),
+                ("out_hsamp0", C.c_int32), ("out_vsamp0", C.c_int32), ("static_stop", C.c_int32)]
+
+
 MAX_PLANES = 56
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -97,6 +103,10 @@ ABI = {
     "qs_hip_band_halo_rows": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_size_t)] * 5),
     "qs_hip_prewarm": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int]),
     "qs_hip_progress_calls": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "qs_hip_device_job_info": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.POINTER(DeviceInfo)]),
+    "qs_hip_device_job_prepare": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_do_quantsmooth_device": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_void_p]),
     "qs_hip_free": (None, [C.c_void_p]),
     "qs_hip_release_cache": (None, []),
     "qs_hip_device_count": (C.c_int, []),
@@ -319,6 +329,54 @@ class HipQS:
         results = (C.c_int * max(1, len(made)))()
         self._check(self.lib.qs_hip_do_quantsmooth_batch(ptrs, len(made), flags, niter, results))
         return [self._job_result(m[0], m[1], j["quants"], int(results[i])) for i, (m, j) in enumerate(zip(made, jobs))]
+
+    # -- device-resident job (device pointers as ints, stream as int or None) ---
+    @staticmethod
+    def device_job(coef_ptrs, shapes, quants, *, hsamp=None, vsamp=None, colorspace=None, image_size=None,
+                   coef_up=None) -> Job:
+        """a qs_hip_job over DEVICE arrays: coef_ptrs[ci] = device address of component ci's (hblk, wblk, 64) int16
+        blocks, shapes[ci] = (hblk, wblk); quants[ci] = 64 quantisers (natural order) or None; coef_up = the two device
+        arrays for UPSAMPLE_UV's replacement chroma (device_job_info tells whether and how large)"""
+        n = len(coef_ptrs)
+        if not 1 <= n <= MAXC or len(shapes) != n or len(quants) != n:
+            raise ValueError("device_job: 1..4 components, one shape and one quant table (or None) each")
+        job = Job()
+        job.ncomp = n
+        job.colorspace = colorspace if colorspace is not None else (3 if n == 3 else 1)
+        hsamp = hsamp or [1] * n
+        vsamp = vsamp or [1] * n
+        for ci in range(n):
+            job.hblk[ci], job.wblk[ci] = int(shapes[ci][0]), int(shapes[ci][1])
+            job.hsamp[ci], job.vsamp[ci] = int(hsamp[ci]), int(vsamp[ci])
+            job.coef[ci] = int(coef_ptrs[ci]) if coef_ptrs[ci] else None
+            if quants[ci] is not None:
+                job.has_quant[ci] = 1
+                for i in range(64):
+                    job.quant[ci][i] = int(quants[ci][i])
+        if image_size is None:
+            mh, mv = max(hsamp), max(vsamp)
+            image_size = (job.wblk[0] * 8 * mh // hsamp[0], job.hblk[0] * 8 * mv // vsamp[0])
+        job.image_width, job.image_height = int(image_size[0]), int(image_size[1])
+        if coef_up is not None:
+            job.coef_up[0], job.coef_up[1] = coef_up[0], coef_up[1]
+        return job
+
+    def device_job_info(self, job: Job, flags: int, niter: int) -> dict:
+        """qs_hip_device_job_info (no device needed) -> dict(workspace_bytes, up_wblk, up_hblk, out_hsamp0, out_vsamp0,
+        static_stop)"""
+        info = DeviceInfo()
+        self._check(self.lib.qs_hip_device_job_info(C.byref(job), flags, niter, C.byref(info)))
+        return {f: int(getattr(info, f)) for f, _ in DeviceInfo._fields_}
+
+    def device_job_prepare(self, job: Job, flags: int, niter: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_device_job_prepare: the constant blocks into the workspace (synchronises `stream`; not inside a capture)"""
+        self._check(self.lib.qs_hip_device_job_prepare(C.byref(job), flags, niter, d_workspace, nbytes, stream))
+
+    def do_quantsmooth_device(self, job: Job, flags: int, niter: int, d_workspace: int, nbytes: int, d_stop: int,
+                              stream=None) -> None:
+        """qs_hip_do_quantsmooth_device: enqueue the whole job on `stream`; the reference's return value lands in the
+        device int32 at d_stop.  Sets job.quant to 1 and job.up_* / out_*samp0 like the job layer."""
+        self._check(self.lib.qs_hip_do_quantsmooth_device(C.byref(job), flags, niter, d_workspace, nbytes, d_stop, stream))
 
     # -- plane layer (device pointers as ints, stream as int or None) ----------
     def idct_plane(self, d_consts, d_coef, d_plane, wblk, hblk, first, rep_top, rep_bot, d_status, stream=None):

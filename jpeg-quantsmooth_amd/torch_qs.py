@@ -1,0 +1,118 @@
+"""do_quantsmooth on PyTorch device tensors: the device-resident job route of include/jpegqs_hip.h
+(qs_hip_do_quantsmooth_device) for coefficients that already live on the GPU.
+
+    res = torch_qs.quantsmooth_(coefs, quants, flags, niter, hsamp=[2, 1, 1], vsamp=[2, 1, 1], colorspace=3,
+                                image_size=(1920, 1080))
+    stop = int(res["stop"])          # the reference's return value (reading it synchronises)
+
+Each coefficient array is a contiguous int16 CUDA tensor of shape (hblk, wblk, 64), rewritten in place.  The job is
+enqueued on torch.cuda.current_stream() with no host synchronisation and no allocation outside torch's allocator, so
+it can be captured into a torch.cuda.graph: run it once outside the capture (that prepares the workspace), then
+capture a call that passes the same `workspace=`.
+
+torch is imported on first use only: importing the package does not need it."""
+from __future__ import annotations
+
+import numpy as np
+
+from .hipqs import HipQS
+
+_HIP = None
+
+
+def _hip() -> HipQS:
+    global _HIP
+    if _HIP is None:
+        _HIP = HipQS()
+    return _HIP
+
+
+class Workspace:
+    """device workspace of one job geometry: a torch uint8 tensor plus what it was prepared for"""
+
+    def __init__(self, buf, key=None):
+        self.buf, self.key = buf, key
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.buf.numel())
+
+
+def _key(job, flags, niter):
+    """what the workspace layout and its constants depend on: everything but the array addresses"""
+    from .hipqs import Job
+    g = Job.from_buffer_copy(job)
+    for ci in range(4):
+        g.coef[ci] = None
+    g.coef_up[0] = g.coef_up[1] = None
+    return (bytes(g), int(flags), int(niter))
+
+
+def _check_tensors(coefs, torch):
+    if not isinstance(coefs, (list, tuple)) or not 1 <= len(coefs) <= 4:
+        raise ValueError("quantsmooth_: coefs must be a list of 1..4 tensors")
+    dev = None
+    for ci, t in enumerate(coefs):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"quantsmooth_: component {ci} is not a torch.Tensor")
+        if t.dtype != torch.int16:
+            raise TypeError(f"quantsmooth_: component {ci} has dtype {t.dtype}, expected torch.int16")
+        if t.dim() != 3 or t.shape[2] != 64 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"quantsmooth_: component {ci} has shape {tuple(t.shape)}, expected (hblk, wblk, 64)")
+        if not t.is_contiguous():
+            raise ValueError(f"quantsmooth_: component {ci} is not contiguous")
+        if not t.is_cuda:
+            raise ValueError(f"quantsmooth_: component {ci} is on {t.device}, expected a CUDA (HIP) device tensor")
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError(f"quantsmooth_: component {ci} is on {t.device}, component 0 on {dev}")
+    return dev
+
+
+def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=None, colorspace=None,
+                 image_size=None, workspace: Workspace | None = None) -> dict:
+    """The reference's do_quantsmooth on `coefs` in place (see the module text).
+
+    quants[ci]: 64 quantisers (natural order) or None (component without a table).  Returns a dict:
+      stop       int32 device tensor of one element: the reference's return value (0 done, 1 stopped)
+      coef_up    UPSAMPLE_UV: the two replacement chroma tensors (luma geometry), else None
+      quants     the output quant tables (all ones where a table was given, as the reference leaves them)
+      hsamp0, vsamp0   component 0's output sampling factors
+      workspace  the Workspace used; pass it again (also inside a graph capture) for jobs of the same geometry
+    coef_up, hsamp0 and vsamp0 describe the result when `stop` reads 0; when it reads 1 the reference drops the
+    replacement chroma and component 0 keeps its sampling factors (coef_up's contents are then meaningless)."""
+    import torch
+    dev = _check_tensors(coefs, torch)
+    n = len(coefs)
+    if len(quants) != n:
+        raise ValueError("quantsmooth_: one quant table (or None) per component")
+    qs = [None if q is None else np.asarray(q, dtype=np.int64).reshape(-1) for q in quants]
+    for ci, q in enumerate(qs):
+        if q is not None and (q.size != 64 or q.min() < 0 or q.max() > 0xFFFF):
+            raise ValueError(f"quantsmooth_: quant table {ci} must be 64 values in 0..65535")
+    hip = _hip()
+    job = hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hsamp,
+                         vsamp=vsamp, colorspace=colorspace, image_size=image_size)
+    info = hip.device_job_info(job, flags, niter)
+    key = _key(job, flags, niter)
+    stream = torch.cuda.current_stream(dev)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if workspace is None or workspace.key != key:
+        if capturing:
+            raise RuntimeError("quantsmooth_: inside a graph capture the workspace must come from an earlier call of the "
+                               "same job (workspace=res['workspace']): preparing one synchronises")
+        if workspace is None or workspace.nbytes < info["workspace_bytes"] or workspace.buf.device != dev:
+            workspace = Workspace(torch.empty(max(1, info["workspace_bytes"]), dtype=torch.uint8, device=dev))
+        hip.device_job_prepare(job, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
+        workspace.key = key
+    coef_up = None
+    if info["up_wblk"] > 0:
+        coef_up = [torch.empty((info["up_hblk"], info["up_wblk"], 64), dtype=torch.int16, device=dev) for _ in range(2)]
+        job.coef_up[0], job.coef_up[1] = coef_up[0].data_ptr(), coef_up[1].data_ptr()
+    stop = torch.empty(1, dtype=torch.int32, device=dev)
+    hip.do_quantsmooth_device(job, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stop.data_ptr(),
+                              stream.cuda_stream)
+    qout = [None if qs[ci] is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci in range(n)]
+    return dict(stop=stop, coef_up=coef_up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0),
+                workspace=workspace)
