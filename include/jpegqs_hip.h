@@ -20,6 +20,7 @@
  *  3. DEVICE JOB  qs_hip_do_quantsmooth_device(): the whole job of layer 1 on
  *     DEVICE arrays, enqueued on one stream without any host synchronisation
  *     (graph-capturable); the range-check stop is decided on the device.
+ *     qs_hip_do_quantsmooth_device_batch(): many such jobs sharing launches.
  *
  * All functions return 0 on success and a negative QS_HIP_E* code on failure;
  * qs_hip_last_error() gives the message.  There is no CPU fallback: without a
@@ -211,6 +212,27 @@ int qs_hip_device_job_prepare(const qs_hip_job *job, int flags, int niter, void 
  * missing coef_up arrays; QS_HIP_ENODEV without a device. */
 int qs_hip_do_quantsmooth_device(qs_hip_job *job, int flags, int niter, void *d_workspace, size_t bytes,
 		int32_t *d_stop, void *stream);
+
+/* ---- device-resident batch (many device-resident jobs, one stream) ----
+ * The three calls above for njobs jobs at once, with one flags / niter setting for the whole batch (as
+ * qs_hip_do_quantsmooth_batch).  The planes of the jobs share launches -- independent-component jobs (--quality 3/4) as
+ * plane sets over all of them, coupled YCbCr jobs (JOINT_YUV / UPSAMPLE_UV) stage by stage -- and the range-check stop
+ * is decided per job on the device, each job independent of the others.  Every other job (LOW_QUALITY, tables with
+ * entries <= 1, a table-decided stop, niter 0) runs the single-job sequence on the same stream.  Results are those of
+ * qs_hip_do_quantsmooth_device job by job, bit for bit.
+ *   info     per_job[i] = what qs_hip_device_job_info reports for jobs[i]; *workspace_bytes = the batch's workspace;
+ *   prepare  the constants and descriptor tables into the workspace; may synchronise `stream`, never inside a capture;
+ *   run      enqueues every job on `stream`, with the single-job run call's promises (graph-capturable, a linear graph).
+ * The run call checks each job as qs_hip_do_quantsmooth_device does (the message names the job) and reports on each
+ * job what it does (quant tables set to 1, up_* and out_*samp0).  d_stop: device int32[njobs]; d_stop[i] receives the
+ * reference's return value for jobs[i].  QS_HIP_EINVAL also for njobs < 1, a null job and two jobs whose arrays
+ * overlap.  The workspace serves one batch of this geometry, tables, flags and niter at a time. */
+int qs_hip_device_batch_info(qs_hip_job *const *jobs, int njobs, int flags, int niter,
+		qs_hip_device_info *per_job, size_t *workspace_bytes);
+int qs_hip_device_batch_prepare(qs_hip_job *const *jobs, int njobs, int flags, int niter,
+		void *d_workspace, size_t bytes, void *stream);
+int qs_hip_do_quantsmooth_device_batch(qs_hip_job *const *jobs, int njobs, int flags, int niter,
+		void *d_workspace, size_t bytes, int32_t *d_stop, void *stream);
 
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up

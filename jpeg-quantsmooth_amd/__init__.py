@@ -12,6 +12,6 @@ from .hipqs import (  # noqa: F401
     FLAGS, HipQS, QsHipError, flags_for_quality, lib_path, load_library,
 )
 
-from .torch_qs import quantsmooth_  # noqa: F401
+from .torch_qs import quantsmooth_, quantsmooth_batch_  # noqa: F401
 
-__all__ = ["synth", "torch_qs", "quantsmooth_", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]
+__all__ = ["synth", "torch_qs", "quantsmooth_", "quantsmooth_batch_", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]

@@ -113,3 +113,116 @@ void qs_launch_dev_fixup(const QsDevJobArgs& a, const uint32_t* first_bad, int32
   for (int j = 0; j < a.n; ++j) nvec = a.c[j].nvec > nvec ? a.c[j].nvec : nvec;
   hipLaunchKernelGGL(qs_dev_fixup_kernel, dim3(qs_dev_grid(nvec, 1024)), dim3(256), 0, s, a, first_bad, d_stop);
 }
+
+// ---- the batch form: the same two kernels over the components of many jobs, one chunk (QS_DEVB_CHUNK components)
+// per launch.  The grid is flat over every vector of the chunk: record c owns workgroups [blk0[c], blk0[c + 1]), so a
+// small component does not wait behind a large one.  Each job has its own range-check word (n - k, atomicMax, 0 = none)
+// and its own d_stop entry; a job whose word is 0 costs the fix-up one load per workgroup.  The words are zeroed by a
+// kernel of their own (qs_dev_clear_words_kernel) before the precheck.
+
+// the record that owns this workgroup: the last c with rec[c].blk0 <= blockIdx.x (wave-uniform)
+__device__ __forceinline__ int qs_devb_find(const QsDevBatchArgs& a) {
+  const uint32_t b = blockIdx.x;
+  int lo = 0, hi = a.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.rec[mid].blk0 <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the snapshot of a record, or null when it has none or it would not lie inside the workspace
+__device__ __forceinline__ uint4* qs_devb_snap(const QsDevBatchArgs& a, const QsDevBRec& R, uint64_t nvec) {
+  const uint64_t off = R.snap_off;
+  if (off == QS_DEVB_NO_SNAP || (off & 15) || off > a.ws_bytes || nvec > (a.ws_bytes - off) / 16) return nullptr;
+  return reinterpret_cast<uint4*>(a.ws + off);
+}
+
+__device__ __forceinline__ void qs_devb_lane_quant(const QsDevBRec& R, int32_t (&q)[8]) {
+  const int e = (int)(threadIdx.x & 7);                      // (a workgroup starts on a block boundary)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) q[k] = R.q[e * 8 + k];
+}
+
+__global__ void __launch_bounds__(256)
+qs_dev_precheck_batch_kernel(const QsDevBatchArgs a) {
+  const int c = qs_devb_find(a);
+  const QsDevBRec& R = a.rec[c];
+  if (blockIdx.x < R.blk0 || R.job < 0 || R.job >= a.njobs) return;
+  const uint64_t nvec = a.nvec[c];
+  const uint64_t v0 = (uint64_t)(blockIdx.x - R.blk0) * QS_DEVB_PRE_VPB;
+  if (v0 >= nvec) return;
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(a.coef[c]);
+  uint4* __restrict__ dst = qs_devb_snap(a, R, nvec);
+  const bool check = R.check != 0;
+  int32_t q[8];
+  qs_devb_lane_quant(R, q);
+  int32_t acc = 0;
+#pragma unroll 4
+  for (int r = 0; r < QS_DEVB_PRE_VPB / 256; ++r) {
+    const uint64_t i = v0 + (uint64_t)r * 256 + threadIdx.x;
+    if (i < nvec) {
+      const uint4 v = src[i];
+      if (dst) dst[i] = v;
+      if (check) acc |= qs_dev_range_bits(v, q);
+    }
+  }
+  if (check && __any((acc >> 12) != 0) && (threadIdx.x & 63) == 0)
+    atomicMax(a.words + R.job, (uint32_t)(R.ncomp - R.comp));
+}
+
+__global__ void __launch_bounds__(256)
+qs_dev_fixup_batch_kernel(const QsDevBatchArgs a) {
+  const int c = qs_devb_find(a);
+  const QsDevBRec& R = a.rec[c];
+  if (blockIdx.x < R.blk0 || R.job < 0 || R.job >= a.njobs) return;
+  const uint32_t w = a.words[R.job];                         // n - k, or 0
+  if (R.stop_writer && blockIdx.x == R.blk0 && threadIdx.x == 0) a.d_stop[R.job] = w != 0 ? 1 : 0;
+  if (!w) return;
+  const uint32_t k = (uint32_t)R.ncomp - w;
+  if (k >= QS_DEV_MAXC) return;
+  const int act = R.act[k];
+  const uint64_t nvec = a.nvec[c];
+  const uint64_t v0 = (uint64_t)(blockIdx.x - R.blk0) * QS_DEVB_FIX_VPB;
+  if (act == QS_DEV_KEEP || v0 >= nvec) return;
+  const uint4* __restrict__ src = qs_devb_snap(a, R, nvec);
+  if (!src) return;
+  uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.coef[c]);
+  int32_t q[8];
+  qs_devb_lane_quant(R, q);
+  for (int r = 0; r < QS_DEVB_FIX_VPB / 256; ++r) {
+    const uint64_t i = v0 + (uint64_t)r * 256 + threadIdx.x;
+    if (i < nvec) {
+      const uint4 v = src[i];
+      dst[i] = act == QS_DEV_RESTORE ? v : qs_dev_dequant(v, q, act == QS_DEV_DEQUANT_CLAMP);
+    }
+  }
+}
+
+// zeroes the batch's range-check words.  A kernel, not a hipMemsetAsync: a captured 20-byte zero memset over five words
+// left nonzero values in the first four on the second replay of a graph on MI355X / ROCm 7 (the fifth read 0).
+__global__ void __launch_bounds__(256)
+qs_dev_clear_words_kernel(uint32_t* __restrict__ words, int n) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) words[i] = 0;
+}
+
+void qs_launch_dev_clear_words(uint32_t* words, int n, hipStream_t s) {
+  hipLaunchKernelGGL(qs_dev_clear_words_kernel, dim3(qs_dev_grid((size_t)n, 64)), dim3(256), 0, s, words, n);
+}
+
+// the grid of a chunk: the workgroups its records own (the same prefix the prepare call wrote into rec[].blk0)
+static unsigned qs_devb_grid(const QsDevBatchArgs& a, uint64_t vpb) {
+  uint64_t g = 0;
+  for (int c = 0; c < a.n; ++c) g += (a.nvec[c] + vpb - 1) / vpb;
+  return (unsigned)g;
+}
+
+void qs_launch_dev_precheck_batch(const QsDevBatchArgs& a, hipStream_t s) {
+  if (const unsigned g = qs_devb_grid(a, QS_DEVB_PRE_VPB))
+    hipLaunchKernelGGL(qs_dev_precheck_batch_kernel, dim3(g), dim3(256), 0, s, a);
+}
+
+void qs_launch_dev_fixup_batch(const QsDevBatchArgs& a, hipStream_t s) {
+  if (const unsigned g = qs_devb_grid(a, QS_DEVB_FIX_VPB))
+    hipLaunchKernelGGL(qs_dev_fixup_batch_kernel, dim3(g), dim3(256), 0, s, a);
+}

@@ -107,6 +107,12 @@ ABI = {
     "qs_hip_device_job_prepare": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_do_quantsmooth_device": (C.c_int, [C.POINTER(Job), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_void_p]),
+    "qs_hip_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_int, C.POINTER(DeviceInfo),
+                                            C.POINTER(C.c_size_t)]),
+    "qs_hip_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+    "qs_hip_do_quantsmooth_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                      C.c_size_t, C.c_void_p, C.c_void_p]),
     "qs_hip_free": (None, [C.c_void_p]),
     "qs_hip_release_cache": (None, []),
     "qs_hip_device_count": (C.c_int, []),
@@ -377,6 +383,32 @@ class HipQS:
         """qs_hip_do_quantsmooth_device: enqueue the whole job on `stream`; the reference's return value lands in the
         device int32 at d_stop.  Sets job.quant to 1 and job.up_* / out_*samp0 like the job layer."""
         self._check(self.lib.qs_hip_do_quantsmooth_device(C.byref(job), flags, niter, d_workspace, nbytes, d_stop, stream))
+
+    # -- device-resident batch (a list of device_job() Jobs) -------------------------
+    @staticmethod
+    def _job_ptrs(jobs):
+        return (C.POINTER(Job) * max(1, len(jobs)))(*[C.pointer(j) if j is not None else None for j in jobs])
+
+    def device_batch_info(self, jobs, flags: int, niter: int):
+        """qs_hip_device_batch_info (no device needed) -> (list of per-job dicts as device_job_info returns them,
+        the batch's workspace bytes)"""
+        per = (DeviceInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_device_batch_info(self._job_ptrs(jobs), len(jobs), flags, niter, per, C.byref(total)))
+        return [{f: int(getattr(per[i], f)) for f, _ in DeviceInfo._fields_} for i in range(len(jobs))], int(total.value)
+
+    def device_batch_prepare(self, jobs, flags: int, niter: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_device_batch_prepare: constants and descriptor tables into the workspace (synchronises `stream`; not
+        inside a capture)"""
+        self._check(self.lib.qs_hip_device_batch_prepare(self._job_ptrs(jobs), len(jobs), flags, niter, d_workspace,
+                                                         nbytes, stream))
+
+    def do_quantsmooth_device_batch(self, jobs, flags: int, niter: int, d_workspace: int, nbytes: int, d_stop: int,
+                                    stream=None) -> None:
+        """qs_hip_do_quantsmooth_device_batch: enqueue every job on `stream`; job i's return value lands in the device
+        int32 at d_stop + 4 * i.  Sets each job's quant to 1 and up_* / out_*samp0 like the single-job call."""
+        self._check(self.lib.qs_hip_do_quantsmooth_device_batch(self._job_ptrs(jobs), len(jobs), flags, niter,
+                                                                d_workspace, nbytes, d_stop, stream))
 
     # -- plane layer (device pointers as ints, stream as int or None) ----------
     def idct_plane(self, d_consts, d_coef, d_plane, wblk, hblk, first, rep_top, rep_bot, d_status, stream=None):

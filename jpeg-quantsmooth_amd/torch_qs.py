@@ -10,6 +10,11 @@ enqueued on torch.cuda.current_stream() with no host synchronisation and no allo
 it can be captured into a torch.cuda.graph: run it once outside the capture (that prepares the workspace), then
 capture a call that passes the same `workspace=`.
 
+    res = torch_qs.quantsmooth_batch_([dict(coefs=..., quants=..., hsamp=..., ...), ...], flags, niter)
+    stops = res["stop"]              # one int32 per image; res["images"][i] has image i's coef_up, quants, ...
+
+runs many images in one call, their planes sharing kernel launches (qs_hip_do_quantsmooth_device_batch).
+
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
@@ -48,26 +53,36 @@ def _key(job, flags, niter):
     return (bytes(g), int(flags), int(niter))
 
 
-def _check_tensors(coefs, torch):
+def _check_tensors(coefs, torch, who="quantsmooth_"):
     if not isinstance(coefs, (list, tuple)) or not 1 <= len(coefs) <= 4:
-        raise ValueError("quantsmooth_: coefs must be a list of 1..4 tensors")
+        raise ValueError(f"{who}: coefs must be a list of 1..4 tensors")
     dev = None
     for ci, t in enumerate(coefs):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"quantsmooth_: component {ci} is not a torch.Tensor")
+            raise TypeError(f"{who}: component {ci} is not a torch.Tensor")
         if t.dtype != torch.int16:
-            raise TypeError(f"quantsmooth_: component {ci} has dtype {t.dtype}, expected torch.int16")
+            raise TypeError(f"{who}: component {ci} has dtype {t.dtype}, expected torch.int16")
         if t.dim() != 3 or t.shape[2] != 64 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"quantsmooth_: component {ci} has shape {tuple(t.shape)}, expected (hblk, wblk, 64)")
+            raise ValueError(f"{who}: component {ci} has shape {tuple(t.shape)}, expected (hblk, wblk, 64)")
         if not t.is_contiguous():
-            raise ValueError(f"quantsmooth_: component {ci} is not contiguous")
+            raise ValueError(f"{who}: component {ci} is not contiguous")
         if not t.is_cuda:
-            raise ValueError(f"quantsmooth_: component {ci} is on {t.device}, expected a CUDA (HIP) device tensor")
+            raise ValueError(f"{who}: component {ci} is on {t.device}, expected a CUDA (HIP) device tensor")
         if dev is None:
             dev = t.device
         elif t.device != dev:
-            raise ValueError(f"quantsmooth_: component {ci} is on {t.device}, component 0 on {dev}")
+            raise ValueError(f"{who}: component {ci} is on {t.device}, component 0 on {dev}")
     return dev
+
+
+def _check_quants(quants, n, who="quantsmooth_"):
+    if len(quants) != n:
+        raise ValueError(f"{who}: one quant table (or None) per component")
+    qs = [None if q is None else np.asarray(q, dtype=np.int64).reshape(-1) for q in quants]
+    for ci, q in enumerate(qs):
+        if q is not None and (q.size != 64 or q.min() < 0 or q.max() > 0xFFFF):
+            raise ValueError(f"{who}: quant table {ci} must be 64 values in 0..65535")
+    return qs
 
 
 def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=None, colorspace=None,
@@ -85,12 +100,7 @@ def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=Non
     import torch
     dev = _check_tensors(coefs, torch)
     n = len(coefs)
-    if len(quants) != n:
-        raise ValueError("quantsmooth_: one quant table (or None) per component")
-    qs = [None if q is None else np.asarray(q, dtype=np.int64).reshape(-1) for q in quants]
-    for ci, q in enumerate(qs):
-        if q is not None and (q.size != 64 or q.min() < 0 or q.max() > 0xFFFF):
-            raise ValueError(f"quantsmooth_: quant table {ci} must be 64 values in 0..65535")
+    qs = _check_quants(quants, n)
     hip = _hip()
     job = hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hsamp,
                          vsamp=vsamp, colorspace=colorspace, image_size=image_size)
@@ -116,3 +126,68 @@ def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=Non
     qout = [None if qs[ci] is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci in range(n)]
     return dict(stop=stop, coef_up=coef_up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0),
                 workspace=workspace)
+
+
+def quantsmooth_batch_(images, flags: int, niter: int, *, workspace: Workspace | None = None) -> dict:
+    """quantsmooth_ on many images in one call (qs_hip_do_quantsmooth_device_batch): their planes share kernel launches,
+    so a batch of small or medium images fills the GPU where one image does not.  Results are quantsmooth_'s, image by
+    image, bit for bit.
+
+    images[i]: a dict with quantsmooth_'s per-image arguments -- coefs, quants and optionally hsamp, vsamp, colorspace,
+    image_size.  One flags / niter setting for the whole batch.  All tensors on one device, none of them twice.
+    Returns a dict:
+      stop       int32 device tensor of len(images) elements: stop[i] is image i's return value (0 done, 1 stopped)
+      images     per image: dict(coef_up, quants, hsamp0, vsamp0), as quantsmooth_ returns them
+      workspace  the Workspace used; pass it again (also inside a graph capture) for a batch of the same geometry"""
+    import torch
+    who = "quantsmooth_batch_"
+    if not isinstance(images, (list, tuple)) or not images:
+        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    dev, seen, jobs, tables = None, set(), [], []
+    hip = _hip()
+    for i, im in enumerate(images):
+        if not isinstance(im, dict) or "coefs" not in im or "quants" not in im:
+            raise ValueError(f"{who}: image {i} must be a dict with coefs and quants")
+        coefs = im["coefs"]
+        if isinstance(coefs, (list, tuple)) and coefs:      # (the tables first: they need no device)
+            qs = _check_quants(im["quants"], len(coefs), who=f"{who}: image {i}")
+        d = _check_tensors(coefs, torch, who=f"{who}: image {i}")
+        if dev is None:
+            dev = d
+        elif d != dev:
+            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
+        for t in coefs:
+            if t.data_ptr() in seen:
+                raise ValueError(f"{who}: image {i} passes a tensor (or its storage) that appears earlier in the batch")
+            seen.add(t.data_ptr())
+        tables.append(qs)
+        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs,
+                                   hsamp=im.get("hsamp"), vsamp=im.get("vsamp"), colorspace=im.get("colorspace"),
+                                   image_size=im.get("image_size")))
+    per, total = hip.device_batch_info(jobs, flags, niter)
+    key = tuple(_key(job, flags, niter) for job in jobs)
+    stream = torch.cuda.current_stream(dev)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if workspace is None or workspace.key != key:
+        if capturing:
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call of the same "
+                               "batch (workspace=res['workspace']): preparing one synchronises")
+        if workspace is None or workspace.nbytes < total or workspace.buf.device != dev:
+            workspace = Workspace(torch.empty(max(1, total), dtype=torch.uint8, device=dev))
+        hip.device_batch_prepare(jobs, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
+        workspace.key = key
+    ups = []
+    for job, info in zip(jobs, per):
+        up = None
+        if info["up_wblk"] > 0:
+            up = [torch.empty((info["up_hblk"], info["up_wblk"], 64), dtype=torch.int16, device=dev) for _ in range(2)]
+            job.coef_up[0], job.coef_up[1] = up[0].data_ptr(), up[1].data_ptr()
+        ups.append(up)
+    stop = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    hip.do_quantsmooth_device_batch(jobs, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stop.data_ptr(),
+                                    stream.cuda_stream)
+    out = []
+    for job, qs, up in zip(jobs, tables, ups):
+        qout = [None if q is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci, q in enumerate(qs)]
+        out.append(dict(coef_up=up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0)))
+    return dict(stop=stop, images=out, workspace=workspace)

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Images per second of the device-resident route for a batch of full-HD 4:2:0 images, one stream (run on the MI355X).
+
+For each quality it times, on the same device tensors:
+  (a) loop     one torch_qs.quantsmooth_ call per image;
+  (b) batch    one torch_qs.quantsmooth_batch_ call for all images;
+  (c) graph    (b) captured into a torch.cuda.graph and replayed.
+Each mode is warmed up, then timed with device events over windows of at least --window seconds, --repeats times, so
+the spread shows.  The inputs are copied in before each call (the calls rewrite them in place); the copy is timed in
+every mode alike.  (a) and (b) must leave identical bytes (coefficients, replacement chroma, stops): checked first.
+Prints one JSON line.
+
+    python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--qualities", default="3,6")
+    ap.add_argument("--niter", type=int, default=3)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    pkg = jpegqs_pkg.load()
+    torch_qs = pkg.torch_qs
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    nsrc = min(4, a.images)                                  # distinct inputs, repeated over the batch
+    src = [pkg.synth.synth_ycc(a.width, a.height, 2, 2, quality=50, seed=11 + k) for k in range(nsrc)]
+    pristine = [[torch.from_numpy(c).to(dev) for c in src[k % nsrc]["coefs"]] for k in range(a.images)]
+    work = [[t.clone() for t in p] for p in pristine]
+    kw = dict(hsamp=src[0]["hsamp"], vsamp=src[0]["vsamp"], colorspace=3, image_size=(a.width, a.height))
+    quants = [src[k % nsrc]["quants"] for k in range(a.images)]
+    blocks = sum(int(t.shape[0] * t.shape[1]) for t in pristine[0]) * a.images
+    stream = torch.cuda.current_stream(dev)
+
+    def reset():
+        for w, p in zip(work, pristine):
+            for t, s in zip(w, p):
+                t.copy_(s)
+
+    def timed(step, what):
+        """images/s over windows of >= a.window s, a.repeats times (device events, after a warm-up)"""
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        per_call = max(time.perf_counter() - t0, 1e-6)
+        calls = max(1, int(np.ceil(a.window / per_call)))
+        rates = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(calls):
+                step()
+            e1.record(stream)
+            e1.synchronize()
+            rates.append(calls * a.images / (e0.elapsed_time(e1) / 1e3))
+        return dict(mode=what, calls_per_window=calls, images_per_s=[round(r, 1) for r in rates],
+                    median_images_per_s=round(float(np.median(rates)), 1),
+                    median_blocks_per_s=round(float(np.median(rates)) * blocks / a.images, 0))
+
+    out = dict(tool="bench_device_batch", images=a.images, width=a.width, height=a.height, niter=a.niter,
+               blocks_per_image=blocks // a.images, device=torch.cuda.get_device_name(dev), results=[])
+    for quality in [int(q) for q in a.qualities.split(",")]:
+        flags = pkg.flags_for_quality(quality)
+        ws = {}
+
+        def loop():
+            reset()
+            res = []
+            for k, w in enumerate(work):
+                r = torch_qs.quantsmooth_(w, quants[k], flags, a.niter, workspace=ws.get(k), **kw)
+                ws[k] = r["workspace"]
+                res.append(r)
+            return res
+
+        images = [dict(coefs=w, quants=quants[k], **kw) for k, w in enumerate(work)]
+        bws = {}
+
+        def batch():
+            reset()
+            r = torch_qs.quantsmooth_batch_(images, flags, a.niter, workspace=bws.get("ws"))
+            bws["ws"] = r["workspace"]
+            return r
+
+        # identical bytes from (a) and (b)
+        ra = loop()
+        got_a = [[t.cpu() for t in w] for w in work] + [[t.cpu() for t in r["coef_up"]] for r in ra if r["coef_up"]]
+        stop_a = [int(r["stop"].item()) for r in ra]
+        rb = batch()
+        got_b = [[t.cpu() for t in w] for w in work] + [[t.cpu() for t in r["coef_up"]] for r in rb["images"] if r["coef_up"]]
+        stop_b = rb["stop"].cpu().tolist()
+        same = stop_a == stop_b and len(got_a) == len(got_b) and all(
+            torch.equal(x, y) for p, q in zip(got_a, got_b) for x, y in zip(p, q))
+        if not same:
+            raise SystemExit(f"bench_device_batch: quality {quality}: the loop and the batch differ")
+
+        row = dict(quality=quality, flags=flags, identical_a_b=same, modes=[timed(loop, "a_loop"), timed(batch, "b_batch")])
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            reset()
+            torch_qs.quantsmooth_batch_(images, flags, a.niter, workspace=bws["ws"])
+        row["modes"].append(timed(g.replay, "c_graph"))
+        med = {m["mode"]: m["median_images_per_s"] for m in row["modes"]}
+        row["b_over_a"] = round(med["b_batch"] / med["a_loop"], 2)
+        row["c_over_a"] = round(med["c_graph"] / med["a_loop"], 2)
+        out["results"].append(row)
+        del g
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
