@@ -181,19 +181,21 @@ int qs_hip_prewarm(const qs_hip_job *geometry, int flags, int niter);
  * +-1023 clamp, JOINT_YUV / UPSAMPLE_UV, LOW_QUALITY and the reference's stop rules (quantsmooth.h:2404-2878).
  * Three calls:
  *   info     geometry + quant tables + flags + niter -> what the job needs (host only, no device touched);
- *   prepare  writes the per-component constant blocks into the caller's device workspace; may synchronise `stream`,
- *            so it is called outside any graph capture, once per geometry + table set + flags + niter;
+ *   prepare  writes the per-component constant blocks and the range-check tables into the caller's device workspace;
+ *            may synchronise `stream`, so it is called outside any graph capture, once per geometry + table set +
+ *            flags + niter;
  *   run      ENQUEUES the job on `stream` and returns: no allocation, no synchronisation, no event or stream creation
  *            or query, no other stream (a capture of it is a linear graph), no copy from host memory, no buffer pool,
  *            no progress callback.  Graph-capturable.
  * The workspace (device memory, info.workspace_bytes, caller-owned) holds the pixel planes, the constants, the
- * range-check word and a snapshot of the input; one job at a time may use it.  Its layout is a function of the job
+ * range-check word and tables and a snapshot of the input; one job at a time may use it.  Its layout is a function of the job
  * and flags alone, so a run must see the geometry, tables, flags and niter its prepare saw.  The workspace is 256-byte
  * aligned, the coefficient arrays 16-byte aligned (what hipMalloc and torch's allocator hand out).
- * The range-check stop (reference :2596-2610) is decided on the device: a precheck kernel snapshots the input and
- * runs the reference's test before any pass; a fix-up kernel after the last pass rebuilds the reference's result
- * from the snapshot when a component tripped.  *d_stop (device int32) receives the reference's return value once
- * the stream reaches the end of the job. */
+ * The range-check stop (reference :2596-2610) is decided on the device: a kernel zeroes the range-check word, a
+ * precheck kernel snapshots the input and runs the reference's test before any pass; a fix-up kernel after the last
+ * pass rebuilds the reference's result from the snapshot when a component tripped, and writes *d_stop (device int32),
+ * the reference's return value, once the stream reaches the end of the job.  These three calls run the batch route
+ * below with one job. */
 typedef struct {
 	size_t workspace_bytes;      /* device workspace the run needs (planes, constants, snapshot, range-check word) */
 	int32_t up_wblk, up_hblk;    /* UPSAMPLE_UV: geometry of the two replacement chroma arrays, else 0 */
@@ -217,9 +219,9 @@ int qs_hip_do_quantsmooth_device(qs_hip_job *job, int flags, int niter, void *d_
  * The three calls above for njobs jobs at once, with one flags / niter setting for the whole batch (as
  * qs_hip_do_quantsmooth_batch).  The planes of the jobs share launches -- independent-component jobs (--quality 3/4) as
  * plane sets over all of them, coupled YCbCr jobs (JOINT_YUV / UPSAMPLE_UV) stage by stage -- and the range-check stop
- * is decided per job on the device, each job independent of the others.  Every other job (LOW_QUALITY, tables with
- * entries <= 1, a table-decided stop, niter 0) runs the single-job sequence on the same stream.  Results are those of
- * qs_hip_do_quantsmooth_device job by job, bit for bit.
+ * is decided per job on the device by one precheck / fix-up pair for the whole batch, each job independent of the
+ * others.  Every other job (LOW_QUALITY, tables with entries <= 1, a table-decided stop, niter 0) runs its own
+ * component sequence on the same stream.  Results are those of qs_hip_do_quantsmooth_device job by job, bit for bit.
  *   info     per_job[i] = what qs_hip_device_job_info reports for jobs[i]; *workspace_bytes = the batch's workspace;
  *   prepare  the constants and descriptor tables into the workspace; may synchronise `stream`, never inside a capture;
  *   run      enqueues every job on `stream`, with the single-job run call's promises (graph-capturable, a linear graph).

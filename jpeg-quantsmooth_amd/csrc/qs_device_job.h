@@ -1,4 +1,4 @@
-// qs_device_job.h -- what the device-resident job route (qs_device_job.cpp) shares with its two kernels
+// qs_device_job.h -- what the device-resident job route (qs_device_job.cpp) shares with its kernels
 // (qs_kernels_device.hip).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,32 +14,12 @@ enum {
   QS_DEV_DEQUANT_CLAMP = 3    // the same, then the +-1023 clamp: the component whose range check tripped (:2598, 2668-2689)
 };
 
-struct QsDevComp {
-  int16_t* coef;              // the caller's coefficient array (device)
-  int16_t* snap;              // its snapshot in the workspace, null when no fix-up can need it
-  uint64_t nvec;              // 16-byte vectors: blocks * 8
-  int32_t check;              // its first pass A would run the range check (a component processed with passes)
-  int32_t act[QS_DEV_MAXC];   // QS_DEV_* when the first tripped component is k = 0..3
-  int32_t q[64];              // quantval as stored in the file, natural order
-};
-
-// passed by value (kernarg segment)
-struct QsDevJobArgs {
-  QsDevComp c[QS_DEV_MAXC];
-  int32_t n;                  // components
-  int32_t static_stop;        // the quant tables alone decide stop (a value >= 0x800, reference :2504)
-};
-
-// first_bad: the range-check word, zeroed before the precheck; n - k when component k is the first that tripped
-void qs_launch_dev_precheck(const QsDevJobArgs& a, uint32_t* first_bad, hipStream_t s);
-void qs_launch_dev_fixup(const QsDevJobArgs& a, const uint32_t* first_bad, int32_t* d_stop, hipStream_t s);
-
-// ---- the batch form (qs_device_batch.cpp): one precheck / fix-up launch per chunk of components of many jobs ----
-// What prepare derived from the quant tables lives in the workspace (QsDevBRec, one per component of a chunk); what
-// addresses caller memory travels in the kernel arguments of the run call (QsDevBatchArgs).  The kernels bound every
-// access by the latter: a record that does not match the run's geometry can give wrong numbers, never a stray address.
+// One precheck / fix-up launch per chunk of components of one or many jobs.  What prepare derived from the quant
+// tables lives in the workspace (QsDevBRec, one per component of a chunk); what addresses caller memory travels in the
+// kernel arguments of the run call (QsDevBatchArgs).  The kernels bound every access by the latter: a record that does
+// not match the run's geometry can give wrong numbers, never a stray address.
 #define QS_DEVB_CHUNK 64            // components per launch (about 1.1 KiB of kernel arguments)
-#define QS_DEVB_PRE_VPB 2048        // 16-byte vectors per workgroup: precheck (8 per lane) ...
+#define QS_DEVB_PRE_VPB 1024        // 16-byte vectors per workgroup: precheck (4 per lane) ...
 #define QS_DEVB_FIX_VPB 8192        // ... and fix-up (32 per lane; nearly every workgroup exits at once)
 
 struct QsDevBRec {
@@ -51,7 +31,8 @@ struct QsDevBRec {
   int32_t check;                    // precheck: run the range test on it
   int32_t stop_writer;              // fix-up: the record that writes d_stop[job]
   uint32_t blk0;                    // its first workgroup in its chunk's launch (prefix over the chunk)
-  int32_t pad[2];
+  int32_t static_stop;              // its job's quant tables alone decide stop (a value >= 0x800, reference :2504)
+  int32_t pad;
 };
 #define QS_DEVB_NO_SNAP (~(uint64_t)0)
 

@@ -1,20 +1,23 @@
-// qs_kernels_device.hip -- the two kernels of the device-resident job route (csrc/qs_device_job.cpp):
+// qs_kernels_device.hip -- the kernels of the device-resident job route (csrc/qs_device_job.cpp), over the components
+// of one or many jobs, one chunk (QS_DEVB_CHUNK components) per launch:
 //
-//   qs_dev_precheck_kernel  before any pass: copies the coefficients of the components that may have to be rebuilt
-//                           into a snapshot in the workspace, and evaluates the reference's range check
-//                           (quantsmooth.h:2596-2602: val |= coef * quantval + 0x800; stop when val >> 12) on the
-//                           components whose first pass A would run it.  The first component that fails, j, lands in
-//                           one device word as n - j (atomicMax, one atomic per wave that saw a failure); 0 = none,
-//                           so the word is reset with a ZERO memset (a captured hipMemsetAsync of 0xff bytes was seen
-//                           to write 0 on the second and later replays of a graph on MI355X / ROCm 7).
-//   qs_dev_fixup_kernel     after the last pass: reads that word once; nothing tripped (the normal case) -> every wave
-//                           exits at once.  Otherwise it rebuilds what the reference leaves behind when it stops at
-//                           component k (quantsmooth.h:2610, 2543-2566, 2668-2689) from the snapshot, per component
-//                           by a table the host computed for every possible k.  Writes the job's `stop` word.
+//   qs_dev_clear_words_kernel     zeroes the jobs' range-check words before the precheck.
+//   qs_dev_precheck_batch_kernel  before any pass: copies the coefficients of the components that may have to be
+//                                 rebuilt into a snapshot in the workspace, and evaluates the reference's range check
+//                                 (quantsmooth.h:2596-2602: val |= coef * quantval + 0x800; stop when val >> 12) on the
+//                                 components whose first pass A would run it.  The first component of a job that
+//                                 fails, j, lands in the job's word as n - j (atomicMax, one atomic per wave that saw a
+//                                 failure); 0 = none.
+//   qs_dev_fixup_batch_kernel     after the last pass: reads the job's word; nothing tripped (the normal case) -> the
+//                                 workgroup exits at once.  Otherwise it rebuilds what the reference leaves behind when
+//                                 it stops at component k (quantsmooth.h:2610, 2543-2566, 2668-2689) from the snapshot,
+//                                 per component by a row the host computed for every possible k.  Writes every job's
+//                                 `stop`.
 //
-// Both stream 16 bytes per lane (8 coefficients, one eighth of a block), grid-stride.  The passes themselves run
-// unconditionally between the two; the existing kernels are not touched (they tolerate tripped inputs: the eager
-// host route runs them on such data before it re-runs the job).
+// The grid is flat over every 16-byte vector of the chunk: record c owns workgroups [blk0[c], blk0[c + 1]), so a small
+// component does not wait behind a large one.  The passes themselves run unconditionally between precheck and fix-up;
+// the existing kernels are not touched (they tolerate tripped inputs: the eager host route runs them on such data
+// before it re-runs the job).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "qs_device_job.h"
@@ -43,82 +46,6 @@ __device__ __forceinline__ uint4 qs_dev_dequant(const uint4 v, const int32_t (&q
   }
   return make_uint4(d[0], d[1], d[2], d[3]);
 }
-
-// the 8 quantisers this lane's vectors are multiplied with: the grid stride is a multiple of 8 vectors, so a lane always
-// handles the same eighth of a block
-__device__ __forceinline__ void qs_dev_lane_quant(const QsDevComp& C, int32_t (&q)[8]) {
-  const int e = (int)(threadIdx.x & 7);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) q[k] = C.q[e * 8 + k];
-}
-
-__global__ void __launch_bounds__(256)
-qs_dev_precheck_kernel(const QsDevJobArgs a, uint32_t* __restrict__ first_bad) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (int j = 0; j < a.n; ++j) {
-    const QsDevComp& C = a.c[j];
-    if (!C.snap && !C.check) continue;                       // (wave-uniform)
-    int32_t q[8];
-    qs_dev_lane_quant(C, q);
-    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(C.coef);
-    uint4* __restrict__ dst = reinterpret_cast<uint4*>(C.snap);
-    int32_t acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < C.nvec; i += stride) {
-      const uint4 v = src[i];
-      if (dst) dst[i] = v;
-      if (C.check) acc |= qs_dev_range_bits(v, q);
-    }
-    if (C.check && __any((acc >> 12) != 0) && (threadIdx.x & 63) == 0)
-      atomicMax(first_bad, (uint32_t)(a.n - j));
-  }
-}
-
-__global__ void __launch_bounds__(256)
-qs_dev_fixup_kernel(const QsDevJobArgs a, const uint32_t* __restrict__ first_bad, int32_t* __restrict__ d_stop) {
-  const uint32_t w = *first_bad;                             // one scalar load per wave: n - k, or 0
-  const bool tripped = w != 0;
-  const uint32_t k = tripped ? (uint32_t)a.n - w : 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *d_stop = (tripped || a.static_stop) ? 1 : 0;
-  if (!tripped) return;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (int j = 0; j < a.n; ++j) {
-    const QsDevComp& C = a.c[j];
-    const int act = C.act[k];
-    if (act == QS_DEV_KEEP) continue;                        // (wave-uniform)
-    int32_t q[8];
-    qs_dev_lane_quant(C, q);
-    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(C.snap);
-    uint4* __restrict__ dst = reinterpret_cast<uint4*>(C.coef);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < C.nvec; i += stride) {
-      const uint4 v = src[i];
-      dst[i] = act == QS_DEV_RESTORE ? v : qs_dev_dequant(v, q, act == QS_DEV_DEQUANT_CLAMP);
-    }
-  }
-}
-
-static int qs_dev_grid(size_t nvec, int cap) {
-  const size_t g = (nvec + 255) / 256;
-  return (int)(g < 1 ? 1 : g > (size_t)cap ? (size_t)cap : g);
-}
-
-void qs_launch_dev_precheck(const QsDevJobArgs& a, uint32_t* first_bad, hipStream_t s) {
-  size_t nvec = 0;
-  for (int j = 0; j < a.n; ++j) if (a.c[j].snap || a.c[j].check) nvec = a.c[j].nvec > nvec ? a.c[j].nvec : nvec;
-  if (!nvec) return;
-  hipLaunchKernelGGL(qs_dev_precheck_kernel, dim3(qs_dev_grid(nvec, 8192)), dim3(256), 0, s, a, first_bad);
-}
-
-void qs_launch_dev_fixup(const QsDevJobArgs& a, const uint32_t* first_bad, int32_t* d_stop, hipStream_t s) {
-  size_t nvec = 0;
-  for (int j = 0; j < a.n; ++j) nvec = a.c[j].nvec > nvec ? a.c[j].nvec : nvec;
-  hipLaunchKernelGGL(qs_dev_fixup_kernel, dim3(qs_dev_grid(nvec, 1024)), dim3(256), 0, s, a, first_bad, d_stop);
-}
-
-// ---- the batch form: the same two kernels over the components of many jobs, one chunk (QS_DEVB_CHUNK components)
-// per launch.  The grid is flat over every vector of the chunk: record c owns workgroups [blk0[c], blk0[c + 1]), so a
-// small component does not wait behind a large one.  Each job has its own range-check word (n - k, atomicMax, 0 = none)
-// and its own d_stop entry; a job whose word is 0 costs the fix-up one load per workgroup.  The words are zeroed by a
-// kernel of their own (qs_dev_clear_words_kernel) before the precheck.
 
 // the record that owns this workgroup: the last c with rec[c].blk0 <= blockIdx.x (wave-uniform)
 __device__ __forceinline__ int qs_devb_find(const QsDevBatchArgs& a) {
@@ -177,7 +104,7 @@ qs_dev_fixup_batch_kernel(const QsDevBatchArgs a) {
   const QsDevBRec& R = a.rec[c];
   if (blockIdx.x < R.blk0 || R.job < 0 || R.job >= a.njobs) return;
   const uint32_t w = a.words[R.job];                         // n - k, or 0
-  if (R.stop_writer && blockIdx.x == R.blk0 && threadIdx.x == 0) a.d_stop[R.job] = w != 0 ? 1 : 0;
+  if (R.stop_writer && blockIdx.x == R.blk0 && threadIdx.x == 0) a.d_stop[R.job] = (w != 0 || R.static_stop) ? 1 : 0;
   if (!w) return;
   const uint32_t k = (uint32_t)R.ncomp - w;
   if (k >= QS_DEV_MAXC) return;
@@ -199,15 +126,16 @@ qs_dev_fixup_batch_kernel(const QsDevBatchArgs a) {
   }
 }
 
-// zeroes the batch's range-check words.  A kernel, not a hipMemsetAsync: a captured 20-byte zero memset over five words
-// left nonzero values in the first four on the second replay of a graph on MI355X / ROCm 7 (the fifth read 0).
+// zeroes the range-check words.  A kernel, not a memset call: a captured 20-byte zero memset over five words left
+// nonzero values in the first four on the second replay of a graph on MI355X / ROCm 7 (the fifth read 0).
 __global__ void __launch_bounds__(256)
 qs_dev_clear_words_kernel(uint32_t* __restrict__ words, int n) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) words[i] = 0;
 }
 
 void qs_launch_dev_clear_words(uint32_t* words, int n, hipStream_t s) {
-  hipLaunchKernelGGL(qs_dev_clear_words_kernel, dim3(qs_dev_grid((size_t)n, 64)), dim3(256), 0, s, words, n);
+  const int g = (n + 255) / 256;
+  hipLaunchKernelGGL(qs_dev_clear_words_kernel, dim3(g < 1 ? 1 : g > 64 ? 64 : g), dim3(256), 0, s, words, n);
 }
 
 // the grid of a chunk: the workgroups its records own (the same prefix the prepare call wrote into rec[].blk0)

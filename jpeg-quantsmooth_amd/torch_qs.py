@@ -85,6 +85,44 @@ def _check_quants(quants, n, who="quantsmooth_"):
     return qs
 
 
+def _enqueue(jobs, tables, dev, flags, niter, workspace, who, single):
+    """what quantsmooth_ (single: the single-job calls) and quantsmooth_batch_ share: the workspace, prepared outside
+    any capture when the jobs changed; the replacement chroma tensors; the run on the current stream; what it reports"""
+    import torch
+    hip = _hip()
+    if single:
+        arg, prepare, run = jobs[0], hip.device_job_prepare, hip.do_quantsmooth_device
+        per = [hip.device_job_info(arg, flags, niter)]
+        total = per[0]["workspace_bytes"]
+    else:
+        arg, prepare, run = jobs, hip.device_batch_prepare, hip.do_quantsmooth_device_batch
+        per, total = hip.device_batch_info(jobs, flags, niter)
+    key = (single,) + tuple(_key(job, flags, niter) for job in jobs)     # (a job alone is laid out unlike a batch of one)
+    stream = torch.cuda.current_stream(dev)
+    if workspace is None or workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call of the same "
+                               f"{'job' if single else 'batch'} (workspace=res['workspace']): preparing one synchronises")
+        if workspace is None or workspace.nbytes < total or workspace.buf.device != dev:
+            workspace = Workspace(torch.empty(max(1, total), dtype=torch.uint8, device=dev))
+        prepare(arg, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
+        workspace.key = key
+    ups = []
+    for job, inf in zip(jobs, per):
+        up = None
+        if inf["up_wblk"] > 0:
+            up = [torch.empty((inf["up_hblk"], inf["up_wblk"], 64), dtype=torch.int16, device=dev) for _ in range(2)]
+            job.coef_up[0], job.coef_up[1] = up[0].data_ptr(), up[1].data_ptr()
+        ups.append(up)
+    stop = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    run(arg, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stop.data_ptr(), stream.cuda_stream)
+    out = []
+    for job, qs, up in zip(jobs, tables, ups):
+        qout = [None if q is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci, q in enumerate(qs)]
+        out.append(dict(coef_up=up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0)))
+    return stop, out, workspace
+
+
 def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=None, colorspace=None,
                  image_size=None, workspace: Workspace | None = None) -> dict:
     """The reference's do_quantsmooth on `coefs` in place (see the module text).
@@ -99,33 +137,11 @@ def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=Non
     replacement chroma and component 0 keeps its sampling factors (coef_up's contents are then meaningless)."""
     import torch
     dev = _check_tensors(coefs, torch)
-    n = len(coefs)
-    qs = _check_quants(quants, n)
-    hip = _hip()
-    job = hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hsamp,
-                         vsamp=vsamp, colorspace=colorspace, image_size=image_size)
-    info = hip.device_job_info(job, flags, niter)
-    key = _key(job, flags, niter)
-    stream = torch.cuda.current_stream(dev)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if workspace is None or workspace.key != key:
-        if capturing:
-            raise RuntimeError("quantsmooth_: inside a graph capture the workspace must come from an earlier call of the "
-                               "same job (workspace=res['workspace']): preparing one synchronises")
-        if workspace is None or workspace.nbytes < info["workspace_bytes"] or workspace.buf.device != dev:
-            workspace = Workspace(torch.empty(max(1, info["workspace_bytes"]), dtype=torch.uint8, device=dev))
-        hip.device_job_prepare(job, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
-        workspace.key = key
-    coef_up = None
-    if info["up_wblk"] > 0:
-        coef_up = [torch.empty((info["up_hblk"], info["up_wblk"], 64), dtype=torch.int16, device=dev) for _ in range(2)]
-        job.coef_up[0], job.coef_up[1] = coef_up[0].data_ptr(), coef_up[1].data_ptr()
-    stop = torch.empty(1, dtype=torch.int32, device=dev)
-    hip.do_quantsmooth_device(job, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stop.data_ptr(),
-                              stream.cuda_stream)
-    qout = [None if qs[ci] is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci in range(n)]
-    return dict(stop=stop, coef_up=coef_up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0),
-                workspace=workspace)
+    qs = _check_quants(quants, len(coefs))
+    job = _hip().device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hsamp,
+                            vsamp=vsamp, colorspace=colorspace, image_size=image_size)
+    stop, (out,), workspace = _enqueue([job], [qs], dev, flags, niter, workspace, "quantsmooth_", True)
+    return dict(stop=stop, **out, workspace=workspace)
 
 
 def quantsmooth_batch_(images, flags: int, niter: int, *, workspace: Workspace | None = None) -> dict:
@@ -164,30 +180,5 @@ def quantsmooth_batch_(images, flags: int, niter: int, *, workspace: Workspace |
         jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs,
                                    hsamp=im.get("hsamp"), vsamp=im.get("vsamp"), colorspace=im.get("colorspace"),
                                    image_size=im.get("image_size")))
-    per, total = hip.device_batch_info(jobs, flags, niter)
-    key = tuple(_key(job, flags, niter) for job in jobs)
-    stream = torch.cuda.current_stream(dev)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if workspace is None or workspace.key != key:
-        if capturing:
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call of the same "
-                               "batch (workspace=res['workspace']): preparing one synchronises")
-        if workspace is None or workspace.nbytes < total or workspace.buf.device != dev:
-            workspace = Workspace(torch.empty(max(1, total), dtype=torch.uint8, device=dev))
-        hip.device_batch_prepare(jobs, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
-        workspace.key = key
-    ups = []
-    for job, info in zip(jobs, per):
-        up = None
-        if info["up_wblk"] > 0:
-            up = [torch.empty((info["up_hblk"], info["up_wblk"], 64), dtype=torch.int16, device=dev) for _ in range(2)]
-            job.coef_up[0], job.coef_up[1] = up[0].data_ptr(), up[1].data_ptr()
-        ups.append(up)
-    stop = torch.empty(len(jobs), dtype=torch.int32, device=dev)
-    hip.do_quantsmooth_device_batch(jobs, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stop.data_ptr(),
-                                    stream.cuda_stream)
-    out = []
-    for job, qs, up in zip(jobs, tables, ups):
-        qout = [None if q is None else np.array(job.quant[ci][:], dtype=np.uint16) for ci, q in enumerate(qs)]
-        out.append(dict(coef_up=up, quants=qout, hsamp0=int(job.out_hsamp0), vsamp0=int(job.out_vsamp0)))
+    stop, out, workspace = _enqueue(jobs, tables, dev, flags, niter, workspace, who, False)
     return dict(stop=stop, images=out, workspace=workspace)

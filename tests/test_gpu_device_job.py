@@ -194,12 +194,16 @@ def capture_inputs(synth):
 
 
 @pytest.mark.parametrize("quality", [3, 6])
-def test_single_stream_graph_capture_replays_exactly(tq, reference, synth, pkg, quality):
+def test_single_stream_graph_capture_replays_exactly(tq, hip, reference, synth, pkg, quality):
     """one job captured on one stream (a linear graph: the route uses no other stream, no host synchronisation, no
-    allocation outside torch's graph pool); two replays with different inputs copied into the static tensors"""
+    allocation outside torch's graph pool); four replays with different inputs copied into the static tensors: two
+    clean ones, one whose range check trips, a clean one again.  Then a niter-0 job replayed: its stop comes from
+    the fix-up kernel inside the graph"""
     torch, torch_qs = tq
     flags, niter = pkg.flags_for_quality(quality), 2
     inputs = capture_inputs(synth)
+    bad = dict(inputs[0], coefs=[c.copy() for c in inputs[0]["coefs"]])
+    bad["coefs"][0][1, 2, 0] = 0x7ff                         # 0x7ff * q >= 0x800 for any q >= 2
     kw = {k: inputs[0][k] for k in ("hsamp", "vsamp", "colorspace", "image_size")}
     static = [torch.from_numpy(c).cuda() for c in inputs[0]["coefs"]]
     warm = torch_qs.quantsmooth_(static, inputs[0]["quants"], flags, niter, **kw)     # prepares the workspace
@@ -207,10 +211,29 @@ def test_single_stream_graph_capture_replays_exactly(tq, reference, synth, pkg, 
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         res = torch_qs.quantsmooth_(static, inputs[0]["quants"], flags, niter, workspace=warm["workspace"], **kw)
-    for x in inputs:
+    for r, x in enumerate(inputs + [bad, inputs[1]]):
         for t, c in zip(static, x["coefs"]):
             t.copy_(torch.from_numpy(c))
         g.replay()
         torch.cuda.synchronize()
         got = _result(torch, static, res, kw)
-        assert_same_result(got, reference_run(reference, x, flags, niter), f"graph replay q{quality}")
+        assert got["ret"] == (1 if r == 2 else 0), r
+        want = hip.do_quantsmooth(x["coefs"], x["quants"], flags, niter, **kw)
+        assert_same_result(got, want, f"graph replay {r} q{quality}")
+        if r < 2:
+            assert_same_result(got, reference_run(reference, x, flags, niter), f"graph replay {r} q{quality}")
+
+    warm = torch_qs.quantsmooth_(static, inputs[0]["quants"], flags, 0, **kw)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        res = torch_qs.quantsmooth_(static, inputs[0]["quants"], flags, 0, workspace=warm["workspace"], **kw)
+    x = inputs[1]
+    for t, c in zip(static, x["coefs"]):
+        t.copy_(torch.from_numpy(c))
+    res["stop"].fill_(7)
+    g.replay()
+    torch.cuda.synchronize()
+    got = _result(torch, static, res, kw)
+    assert got["ret"] == 0
+    assert_same_result(got, hip.do_quantsmooth(x["coefs"], x["quants"], flags, 0, **kw), f"graph replay niter 0 q{quality}")
