@@ -61,3 +61,50 @@ def inject_extreme_blocks(j, seed=7):
             for k in (1, 8, 9, 2, 16):
                 c[by, bx, k] = -sgn * (int(rng.integers(300, 1500)) // int(q[k])) * (1 if rng.integers(0, 2) else -1)
     return dict(j, coefs=coefs)
+
+
+def fuzz_generators():
+    """tools/fuzz_gpu.py's seeded job generators (trial_jobs, stop_trial_jobs, jobs_of, digest, kwargs, ...), without
+    running its command line: the part of the file above `if mode == "gen":`"""
+    import sys
+    root = GOLDEN.parent.parent
+    src = (root / "tools" / "fuzz_gpu.py").read_text().split('if mode == "gen":')[0]
+    ns = {"__file__": str(root / "tools" / "fuzz_gpu.py")}
+    argv = sys.argv
+    sys.argv = ["fuzz_gpu.py", "import-only", "-"]
+    try:
+        exec(compile(src, "fuzz_gpu_generators", "exec"), ns)
+    finally:
+        sys.argv = argv
+    return ns
+
+
+def stop_corpus():
+    """tests/golden/fuzz_stops.jsonl: one dict per trial"""
+    import json
+    with open(GOLDEN / "fuzz_stops.jsonl") as f:
+        return [json.loads(line) for line in f]
+
+
+# products beyond int16 in a 4:2:0 job: (component, block row, block column, coefficient index, coefficient, quantiser).
+# Component 0 trips (the reference stops there: int16(c * q), then the +-1023 clamp); component 1 comes after the stop
+# and is only dequantised (int16(c * q), no clamp); component 2 holds one product inside the range.
+WRAP_PLANTS = [(0, 0, 0, 0, 20000, 2), (0, 3, 5, 9, -20000, 2), (0, 4, 4, 63, 11000, 3), (0, 5, 7, 1, -16385, 2),
+               (1, 0, 0, 0, 30000, 3), (1, 2, 1, 17, -30000, 3), (1, 2, 2, 8, 16384, 2), (2, 1, 1, 5, -2048, 1)]
+
+
+def wrap_job(synth):
+    """a 4:2:0 job whose range check trips in luma with products beyond +-32767 (WRAP_PLANTS)"""
+    y = synth.synth_ycc(120, 96, 2, 2, quality=50, seed=77)
+    coefs = [c.copy() for c in y["coefs"]]
+    quants = [q.copy() for q in y["quants"]]
+    for ci, by, bx, e, c, q in WRAP_PLANTS:
+        coefs[ci][by, bx, e] = c
+        quants[ci][e] = q
+    return dict(coefs=coefs, quants=quants, hsamp=y["hsamp"], vsamp=y["vsamp"], colorspace=3, image_size=(120, 96))
+
+
+def wrap_expected(ci, c, q):
+    """what the reference leaves for one WRAP_PLANTS entry after stopping at component 0"""
+    v = int(np.int16(np.int32(c) * np.int32(q)))             # JCOEF arithmetic: the product wraps to int16
+    return max(-1023, min(1023, v)) if ci == 0 else v
