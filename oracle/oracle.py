@@ -163,7 +163,53 @@ class _Lib:
                     hsamp0=job.out_hsamp0, vsamp0=job.out_vsamp0)
 
 
-class Oracle(_Lib):
+class _Batches:
+    """batched forms of the block-level calls (one call per test case: RecordedReference keeps one digest per call)
+    and the row-level chroma upsampler; shared by Oracle and Reference"""
+
+    def idct_blocks(self, coefs):
+        """int16 [n, 64] -> uint8 [n, 64]: idct_islow of every block (an 8x8 tile, stride 8)"""
+        c = np.ascontiguousarray(coefs, dtype=np.int16).reshape(-1, 64)
+        return np.stack([self.idct_islow(b) for b in c]) if len(c) else np.zeros((0, 64), np.uint8)
+
+    def fdct_blocks(self, x):
+        """float32 [n, 64] -> float32 [n, 64]: fdct_float of every block"""
+        a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 64)
+        return np.stack([self.fdct_float(b) for b in a]) if len(a) else np.zeros((0, 64), np.float32)
+
+    def blocks(self, coefs, eff_quant, plane, positions, flags, luma=1, plane2=None):
+        """block() of each (bx, by) in `positions` on its own copy of coefs[by, bx] (int16 [hblk, wblk, 64]), all
+        reading the same plane(s) (uint8 [h + 2, w + 2], apron of one pixel) -> int16 [len(positions), 64]"""
+        c = np.ascontiguousarray(coefs, dtype=np.int16)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        if plane2 is not None:
+            plane2 = np.ascontiguousarray(plane2, dtype=np.uint8)
+        out = [self.block(c[by, bx], eff_quant, plane, bx, by, flags, luma, plane2) for bx, by in positions]
+        return np.stack(out) if out else np.zeros((0, 64), np.int16)
+
+    def upsample_strips(self, chroma, lowres, luma, w1, ww, hh, st, ws, hs, strips):
+        """the chroma upsampler, upsample_row() per strip of low-res rows, on copies of the inputs.
+        chroma / lowres: uint8 [H + 2, S] low-res planes with their one-pixel apron (same stride S); luma: uint8
+        [HH + 2, S1] full-res luma with its apron; the rows the strips read must lie in the arrays.  strips: list of
+        (y0, y1, view): upsample_row(w1, y0 + view, y1 + view, ...) with every pointer moved back by `view` low-res
+        rows, i.e. strip [y0, y1) computed as if it started at row y0 + view (view = 8: a strip of the first 8 rows
+        without the first strip's right-edge replicate).  -> uint8 [hh_rows, st] output buffer, zero where unwritten"""
+        chroma = np.ascontiguousarray(chroma, dtype=np.uint8)
+        lowres = np.ascontiguousarray(lowres, dtype=np.uint8)
+        luma = np.ascontiguousarray(luma, dtype=np.uint8)
+        assert chroma.shape == lowres.shape
+        stride, stride1 = chroma.shape[1], luma.shape[1]
+        mem = np.zeros((hh, st), dtype=np.uint8)
+        for y0, y1, view in strips:
+            assert 0 <= y0 <= y1 and (y1 - y0) <= 8 and (y1 + 1) * hs <= mem.shape[0]
+            self._upsample_row(w1, y0 + view, y1 + view, chroma.ctypes.data - view * stride,
+                               lowres.ctypes.data - view * stride, stride,
+                               luma.ctypes.data - view * hs * stride1, stride1,
+                               mem.ctypes.data - view * hs * st, st, ww, ws, hs)
+        return mem
+
+
+class Oracle(_Batches, _Lib):
     """our restatement (libqs_oracle.so)"""
 
     def __init__(self, path: Path | None = None):
@@ -181,6 +227,8 @@ class Oracle(_Lib):
         self._interval = self.fn("interval", None, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3)
         self._recip = self.fn("interval_recip", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)])
         self._prep = self.fn("quant_prep", None, [u16p, u16p, C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        self._upsample_row = self.fn("upsample_row", None, [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p,
+                                     C.c_int, C.c_void_p] + [C.c_int] * 4)
 
     def idct_islow(self, coef):
         c = np.ascontiguousarray(coef, dtype=np.int16)
@@ -232,7 +280,7 @@ class Oracle(_Lib):
         return c
 
 
-class Reference(_Lib):
+class Reference(_Batches, _Lib):
     """the compiled, unmodified reference behind ref_harness.c"""
 
     def __init__(self, variant: str = "none"):
@@ -244,6 +292,8 @@ class Reference(_Lib):
         self._fdctf = self.fn("fdct_float", None, [f32p, f32p])
         self._tables = self.fn("tables", C.c_int, [C.c_int, f32p])
         self._block = self.fn("block", None, [i16p, u16p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int])
+        self._upsample_row = self.fn("upsample_row", None, [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p,
+                                     C.c_int, C.c_void_p] + [C.c_int] * 4)
         v = self.fn("variant", C.c_char_p, [])
         self.compiled_variant = v().decode()
 
@@ -340,7 +390,8 @@ class RecordedReference:
     A call that was never recorded fails.  With `live` (a Reference) the calls go to it and their digests are recorded
     instead; save() merges them into the file (QS_RECORD_REFERENCE=1, see tests/conftest.py)."""
 
-    METHODS = ("do_quantsmooth", "idct_islow", "idct_float", "fdct_float", "tables", "block")
+    METHODS = ("do_quantsmooth", "idct_islow", "idct_float", "fdct_float", "tables", "block",
+               "idct_blocks", "fdct_blocks", "blocks", "upsample_strips")
 
     def __init__(self, live: Reference | None = None, path: Path = RECORDED):
         self.live, self.path, self.new = live, Path(path), {}

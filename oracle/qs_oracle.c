@@ -64,9 +64,14 @@ void qso_quant_prep(const uint16_t q[64], uint16_t eff[64], int *all_le1, int *a
 /* A5/A.6: the multiple of `div` nearest to `coef` (ties away from zero) and
  * the integer interval that quantises to it.  Exact-division form
  * (reference quantsmooth.h:338-341, 1552-1557).                             */
+int qso_interval_recip(int coef, int div, int *orig);
 void qso_interval(int coef, int div, int *orig, int *lo, int *hi) {
 	int half_dn = (div - 1) >> 1, half_up = div >> 1;
 	int o = (coef + (coef < 0 ? -half_up : half_up)) / div * div;
+	/* above 0x7ff the reciprocal form the reference runs is no longer the exact
+	 * division (e.g. 32767 under 65535 gives 65535, not 0): the driver stops
+	 * on such tables (:2501-2503), the block function still takes them */
+	if (div > 0x7ff) qso_interval_recip(coef, div, &o);
 	*orig = o;
 	*hi = o + (o < 0 ? half_up : half_dn);
 	*lo = o - (o > 0 ? half_up : half_dn);
@@ -502,9 +507,44 @@ static void make_luma_lowres(const plane_t *Y, plane_t *L, int ws, int hs) {
 	for (y = h1; y <= L->h; y++) memcpy(plane_px(L, -1, y), plane_px(L, -1, h1 - 1), L->pitch);
 }
 
-/* A12: chroma upsampling guided by full-resolution luma.
- * reference quantsmooth.h:1851-1864, 2133-2158, 2363-2393 (per 8-row strip)
- * and :2724-2730 (strip loop + bottom replicate).
+/* A12: chroma upsampling guided by full-resolution luma, one strip of low-res
+ * rows [y0, y1) with the reference's row-level arguments (reference
+ * quantsmooth.h:1851-1864, 2133-2158, 2363-2393).  image / image2 = low-res
+ * chroma / luma (same stride, pointing at the apron pixel (-1, -1)), image1 =
+ * full-res luma (stride1, apron pixel (-1, -1)), mem = full-res output rows
+ * (pitch st), ww = full-res width in pixels.                                  */
+void qso_upsample_row(int w1, int y0, int y1, const uint8_t *image, const uint8_t *image2, int stride,
+		const uint8_t *image1, int stride1, uint8_t *mem, int st, int ww, int ws, int hs) {
+	int x, y, xx, yy, xend = (w1 + 7) & ~7;
+	image += (size_t)(y0 + 1) * stride + 1;
+	image2 += (size_t)(y0 + 1) * stride + 1;
+	image1 += (size_t)(y0 * hs + 1) * stride1 + 1;
+	mem += (size_t)y0 * hs * st;
+	y1 -= y0;
+	for (y = 0; y < y1; y++)
+		for (x = 0; x < xend; x++) {
+			int32_t sA, sB;
+			const uint8_t *c = image + (size_t)y * stride + x, *l = image2 + (size_t)y * stride + x;
+			float scale = regress_scale(l, stride, c, stride, &sA, &sB);
+			float offset = (float)*c - (float)*l * scale + 0.5f;
+			for (yy = 0; yy < hs; yy++) for (xx = 0; xx < ws; xx++) {
+				int v = f2i_x86((float)image1[(size_t)(y * hs + yy) * stride1 + x * ws + xx] * scale + offset);
+				mem[(size_t)(y * hs + yy) * st + x * ws + xx] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+			}
+		}
+	/* Right-edge replicate.  The reference's loop `for (yy = y0*hs; yy < y1*hs; ...)`
+	 * runs with y1 already made relative to y0 and `mem` already advanced
+	 * (reference quantsmooth.h:1860-1861, 2390-2393): for the strips of the
+	 * driver (y0 a multiple of 8) it covers the first strip only; later strips
+	 * keep the computed values.  Reproduced as is.                             */
+	for (yy = y0 * hs; yy < y1 * hs; yy++) {
+		uint8_t *row = mem + (size_t)yy * st;
+		int a = row[w1 * ws - 1];
+		for (x = w1 * ws; x < ww; x++) row[x] = (uint8_t)a;
+	}
+}
+
+/* the strip loop + bottom replicate of reference :2724-2730.
  * C = low-res chroma plane, L = low-res luma, Y = full-res luma,
  * out = full-res chroma pixels (pitch st, ww x hh valid).                     */
 static void upsample_chroma(const plane_t *C, const plane_t *L, const plane_t *Y,
@@ -513,28 +553,9 @@ static void upsample_chroma(const plane_t *C, const plane_t *L, const plane_t *Y
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic)
 #endif
-	for (y = 0; y < h1; y++) {
-		int x, xx, yy, xend = (w1 + 7) & ~7;
-		for (x = 0; x < xend; x++) {
-			int32_t sA, sB;
-			float scale = regress_scale(plane_px(L, x, y), L->pitch, plane_px(C, x, y), C->pitch, &sA, &sB);
-			float offset = (float)*plane_px(C, x, y) - (float)*plane_px(L, x, y) * scale + 0.5f;
-			for (yy = 0; yy < hs; yy++) for (xx = 0; xx < ws; xx++) {
-				int v = f2i_x86((float)*plane_px(Y, x * ws + xx, y * hs + yy) * scale + offset);
-				out[(size_t)(y * hs + yy) * st + x * ws + xx] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
-			}
-		}
-		/* Right-edge replicate.  The reference applies it only to the rows of
-		 * the FIRST 8-row strip: its loop `for (yy = y0*hs; yy < y1*hs; ...)`
-		 * runs with y1 already made relative to y0 and `mem` already advanced
-		 * (reference quantsmooth.h:1860-1861, 2390-2393), so it is empty for
-		 * y0 >= 8.  Later strips keep the computed values.  Reproduced as is. */
-		if (y < 8)
-			for (yy = 0; yy < hs; yy++) {
-				uint8_t *row = out + (size_t)(y * hs + yy) * st;
-				for (x = w1 * ws; x < ww; x++) row[x] = row[w1 * ws - 1];
-			}
-	}
+	for (y = 0; y < h1; y += 8)
+		qso_upsample_row(w1, y, y + 8 < h1 ? y + 8 : h1, plane_px(C, -1, -1), plane_px(L, -1, -1), C->pitch,
+				plane_px(Y, -1, -1), Y->pitch, out, st, ww, ws, hs);
 	for (y = h1 * hs; y < hh; y++)
 		memcpy(out + (size_t)y * st, out + (size_t)(h1 * hs - 1) * st, st);
 }

@@ -63,6 +63,8 @@ void qso_block(int16_t *coef, const uint16_t eff_quant[64],
 		const uint8_t *image, const uint8_t *image2, int stride,
 		int flags, int luma);
 void qso_fdct_clamp(float *buf, int16_t *coef, const uint16_t eff_quant[64]);
+void qso_upsample_row(int w1, int y0, int y1, const uint8_t *image, const uint8_t *image2, int stride,
+		const uint8_t *image1, int stride1, uint8_t *mem, int st, int ww, int ws, int hs);
 /* band passes in the product's plane layout (CPU stand-in for the kernels in
  * the multi-process band tests) */
 void qso_band_idct(int16_t *coef, int wblk, int hblk, const uint16_t rawq[64], int first,
