@@ -236,6 +236,41 @@ int qs_hip_device_batch_prepare(qs_hip_job *const *jobs, int njobs, int flags, i
 int qs_hip_do_quantsmooth_device_batch(qs_hip_job *const *jobs, int njobs, int flags, int niter,
 		void *d_workspace, size_t bytes, int32_t *d_stop, void *stream);
 
+/* ---- device decode to pixels (the coefficient arrays of device-resident jobs -> interleaved uint8 samples) ----
+ * What libjpeg 9 hands out of jpeg_read_scanlines() for the same coefficient arrays, quant tables and sampling factors
+ * (JDCT_ISLOW, the default do_fancy_upsampling -- libjpeg 9 upsamples 2x chroma by DCT scaling -- and the default
+ * output colour space), bit for bit, over the whole int16 coefficient x uint16 quantiser domain.  Jobs are qs_hip_job
+ * records over DEVICE arrays, typically those a qs_hip_do_quantsmooth_device[_batch] run has just reported on: their
+ * quant tables (all ones after smoothing), coef, and for UPSAMPLE_UV coef_up / up_wblk / up_hblk.  Layouts:
+ *   grayscale (1 component, colorspace 1, any sampling)                        -> height x width x 1
+ *   YCbCr -> RGB (colorspace 3), chroma 1x1, luma 1x1, 2x1, 1x2, 2x2 or 4x1    -> height x width x 3
+ *   RGB without a colour transform (colorspace 2), the same sampling           -> height x width x 3
+ * anything else: QS_HIP_ENOTSUP.  image_width x image_height is required and is the output crop; each component
+ * needs the blocks libjpeg's geometry gives it (width_in_blocks x height_in_blocks, QS_HIP_EINVAL otherwise).
+ * A job with up_wblk > 0 has two geometries: the replacement chroma at luma resolution with 1x1 sampling (the reference's
+ * result when its stop is 0) and the original chroma and sampling (stop 1, reference quantsmooth.h:2835).  With d_stop
+ * (device int32[njobs], what the smoothing run wrote) the kernel picks one per job from d_stop[i]; with d_stop NULL
+ * the replacement chroma is used.  Same three-call pattern as the device-resident job:
+ *   info     per_job[i] = output shape and layout of jobs[i]; *workspace_bytes; no device touched;
+ *   prepare  writes the per-job descriptors (geometry, tables) into the workspace; may synchronise `stream`, never
+ *            inside a capture; once per geometry + table set (the layout does not depend on array addresses);
+ *   run      ENQUEUES the decode on `stream`: one kernel launch per QS_HIP_DECODE_CHUNK jobs (the arrays and outputs
+ *            travel in its arguments), no allocation, no synchronisation, no copy (graph-capturable).  It must see the
+ *            geometry and tables prepare saw.
+ * d_out[i]: device buffer of (height - 1) * out_pitch[i] + width * channels bytes, rows out_pitch[i] bytes apart;
+ * only the samples of the image are written.  Arrays 16-byte aligned. */
+#define QS_HIP_DECODE_CHUNK 44
+typedef struct {
+	int32_t width, height, channels;   /* output of job i: height rows of width * channels samples */
+	int32_t layout;                    /* 0 grayscale, 1 YCbCr -> RGB, 2 RGB */
+} qs_hip_decode_info;
+int qs_hip_decode_device_batch_info(qs_hip_job *const *jobs, int njobs, qs_hip_decode_info *per_job,
+		size_t *workspace_bytes);
+int qs_hip_decode_device_batch_prepare(qs_hip_job *const *jobs, int njobs, void *d_workspace, size_t bytes,
+		void *stream);
+int qs_hip_decode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint8_t *const *d_out,
+		const size_t *out_pitch, void *d_workspace, size_t bytes, void *stream);
+
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up
  * to 2 GiB) and HIP streams in process-wide caches, each entry tied to the device it was created
@@ -254,7 +289,7 @@ const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
- * qs_hip_device_info and its three calls).  A caller built against
+ * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

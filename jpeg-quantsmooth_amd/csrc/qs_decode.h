@@ -1,0 +1,253 @@
+// qs_decode.h -- the device decode to pixels (qs_hip_decode_device_batch, csrc/qs_kernels_decode.hip): libjpeg 9's
+// JDCT_ISLOW inverse DCTs (jidctint.c: jpeg_idct_islow, jpeg_idct_16x16, jpeg_idct_16x8, jpeg_idct_8x16), its range
+// limit and its YCbCr -> RGB tables (jdcolor.c), as functions the kernel and a host build can both compile, and the
+// per-job descriptor the host driver writes into the caller's workspace.
+//
+// Numerical contract: libjpeg 9's INT32 is `long` (64 bits) and its workspace between the two
+// passes is `int`.  Both passes are linear in their inputs up to their one final right shift, so
+//   pass 1: ws = (int32)((sum + 2^10) >> 11)  needs bits 11..42 of the sum: 64-bit arithmetic (an int32 product
+//           coef * q times a 14-bit constant exceeds 32 bits);
+//   pass 2: sample = limit[((sum + bias) >> 18) & 1023] needs bits 18..27 of the sum only, i.e. the sum modulo 2^28:
+//           wrapping 32-bit arithmetic gives exactly those bits, whatever the size of the true sum.
+// Pass 1 runs in wrapping 32 bits where the block's dequantised values are bounded so that its final sums fit int32
+// (QS_DEC_FAST_BOUND), in 64 bits otherwise.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define QS_DEC_HD __host__ __device__ inline
+#define QD_UNROLL _Pragma("unroll")
+#else
+#define QS_DEC_HD static inline
+#define QD_UNROLL
+#endif
+
+enum {                           // the supported layouts (qs_hip_decode_device_batch_info)
+  QS_DEC_GRAY = 0,               // one component, any sampling: 8x8 islow
+  QS_DEC_YCC = 1,                // YCbCr -> RGB, chroma 1x1, luma (h, v) in {(1,1), (2,1), (1,2), (2,2), (4,1)}
+  QS_DEC_RGB = 2                 // RGB without a colour transform, same sampling set, no conversion
+};
+
+// One job as the kernel sees it (workspace, written by the prepare call): geometry and tables, no addresses.  Two
+// geometries when the job carries UPSAMPLE_UV's replacement chroma: variant 0 = the replacement chroma at luma
+// resolution (taken when d_stop[job] reads 0), variant 1 = the original chroma and sampling (reference :2835).
+struct QsDecGeom {
+  int32_t wblk[3], hblk[3];      // each component's block array (wblk = row stride in blocks)
+  int32_t hs, vs;                // component 0's sampling factors (chroma is 1x1); 1x1 for gray
+};
+
+struct QsDecJob {
+  QsDecGeom g[2];
+  int32_t width, height;         // output crop
+  int32_t layout, nout;          // QS_DEC_*, output samples per pixel (1 or 3)
+  int32_t two;                   // 1: the variant follows d_stop[job] (else variant 0)
+  int32_t tiles_x;               // output tiles of QS_DEC_TW x QS_DEC_TH pixels per tile row
+  int32_t tile0, tiles;          // first workgroup of this job in its chunk's launch, and how many it has
+  uint16_t q[3][64];             // the components' tables (natural order)
+};
+
+// What addresses caller memory travels in the kernel arguments of the run call, one chunk of jobs per launch, so the
+// kernel bounds every access by them (a workspace that does not match the run gives wrong pixels, never a stray
+// address: the output extent comes from here too).
+#define QS_DEC_CHUNK 44            // jobs per launch (about 3.8 KiB of kernel arguments)
+struct QsDecPtrs {
+  const int16_t* coef[5];        // 0..2 variant 0's arrays; 3..4 variant 1's chroma (luma is coef[0] in both)
+  uint8_t* out;
+  int64_t pitch;
+  int32_t width, height;         // the output extent the caller gave
+  int32_t nblk[5];               // blocks in each array
+  int32_t pad;
+};
+struct QsDecArgs {
+  const QsDecJob* jobs;          // the chunk's descriptors (workspace)
+  const int32_t* d_stop;         // the caller's int32[njobs] or null, indexed by job0 + i
+  int32_t job0, n;
+  QsDecPtrs p[QS_DEC_CHUNK];
+};
+
+#define QS_DEC_TW 64             // output tile: 64 x 16 pixels = every MCU shape of the supported layouts
+#define QS_DEC_TH 16
+
+// 14-bit fixed-point constants of jidctint.c (CONST_BITS 13): FIX(x) = (INT32)(x * 8192 + 0.5)
+#define QD_FIX(x) ((int32_t)((x) * 8192 + 0.5))
+
+// One 8-point column / row of jpeg_idct_islow.  in[k] = input k (already dequantised for pass 1); dc_bias is added
+// to in[0] << 13.  out[i] = the sum before the final shift.  T: int64_t (pass 1) or uint32_t (wrapping; pass 2 and
+// the bounded pass 1).
+template <class T>
+QS_DEC_HD void qd_idct8(const T* in, T dc_bias, T* out) {
+  T z2 = in[0], z3 = in[4];
+  z2 = (T)(z2 << 13) + dc_bias;
+  z3 = (T)(z3 << 13);
+  T tmp0 = z2 + z3, tmp1 = z2 - z3;
+  z2 = in[2]; z3 = in[6];
+  T z1 = (z2 + z3) * (T)QD_FIX(0.541196100);
+  T tmp2 = z1 + z2 * (T)QD_FIX(0.765366865);
+  T tmp3 = z1 - z3 * (T)QD_FIX(1.847759065);
+  const T tmp10 = tmp0 + tmp2, tmp13 = tmp0 - tmp2, tmp11 = tmp1 + tmp3, tmp12 = tmp1 - tmp3;
+  tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
+  z2 = tmp0 + tmp2;
+  z3 = tmp1 + tmp3;
+  z1 = (z2 + z3) * (T)QD_FIX(1.175875602);
+  z2 = z2 * (T)(-QD_FIX(1.961570560));
+  z3 = z3 * (T)(-QD_FIX(0.390180644));
+  z2 += z1;
+  z3 += z1;
+  z1 = (tmp0 + tmp3) * (T)(-QD_FIX(0.899976223));
+  tmp0 = tmp0 * (T)QD_FIX(0.298631336);
+  tmp3 = tmp3 * (T)QD_FIX(1.501321110);
+  tmp0 += z1 + z2;
+  tmp3 += z1 + z3;
+  z1 = (tmp1 + tmp2) * (T)(-QD_FIX(2.562915447));
+  tmp1 = tmp1 * (T)QD_FIX(2.053119869);
+  tmp2 = tmp2 * (T)QD_FIX(3.072711026);
+  tmp1 += z1 + z3;
+  tmp2 += z1 + z2;
+  out[0] = tmp10 + tmp3; out[7] = tmp10 - tmp3;
+  out[1] = tmp11 + tmp2; out[6] = tmp11 - tmp2;
+  out[2] = tmp12 + tmp1; out[5] = tmp12 - tmp1;
+  out[3] = tmp13 + tmp0; out[4] = tmp13 - tmp0;
+}
+
+// One 16-point column / row of jpeg_idct_16x16 (8 inputs, 16 outputs), same conventions.
+template <class T>
+QS_DEC_HD void qd_idct16(const T* in, T dc_bias, T* out) {
+  T tmp0 = (T)(in[0] << 13) + dc_bias;
+  T z1 = in[4];
+  T tmp1 = z1 * (T)QD_FIX(1.306562965);
+  T tmp2 = z1 * (T)QD_FIX(0.541196100);
+  T tmp10 = tmp0 + tmp1, tmp11 = tmp0 - tmp1, tmp12 = tmp0 + tmp2, tmp13 = tmp0 - tmp2;
+  z1 = in[2];
+  T z2 = in[6];
+  T z3 = z1 - z2;
+  T z4 = z3 * (T)QD_FIX(0.275899379);
+  z3 = z3 * (T)QD_FIX(1.387039845);
+  tmp0 = z3 + z2 * (T)QD_FIX(2.562915447);
+  tmp1 = z4 + z1 * (T)QD_FIX(0.899976223);
+  tmp2 = z3 - z1 * (T)QD_FIX(0.601344887);
+  T tmp3 = z4 - z2 * (T)QD_FIX(0.509795579);
+  const T tmp20 = tmp10 + tmp0, tmp27 = tmp10 - tmp0, tmp21 = tmp12 + tmp1, tmp26 = tmp12 - tmp1;
+  const T tmp22 = tmp13 + tmp2, tmp25 = tmp13 - tmp2, tmp23 = tmp11 + tmp3, tmp24 = tmp11 - tmp3;
+  z1 = in[1]; z2 = in[3]; z3 = in[5]; z4 = in[7];
+  tmp11 = z1 + z3;
+  tmp1 = (z1 + z2) * (T)QD_FIX(1.353318001);
+  tmp2 = tmp11 * (T)QD_FIX(1.247225013);
+  tmp3 = (z1 + z4) * (T)QD_FIX(1.093201867);
+  tmp10 = (z1 - z4) * (T)QD_FIX(0.897167586);
+  tmp11 = tmp11 * (T)QD_FIX(0.666655658);
+  tmp12 = (z1 - z2) * (T)QD_FIX(0.410524528);
+  tmp0 = tmp1 + tmp2 + tmp3 - z1 * (T)QD_FIX(2.286341144);
+  tmp13 = tmp10 + tmp11 + tmp12 - z1 * (T)QD_FIX(1.835730603);
+  z1 = (z2 + z3) * (T)QD_FIX(0.138617169);
+  tmp1 += z1 + z2 * (T)QD_FIX(0.071888074);
+  tmp2 += z1 - z3 * (T)QD_FIX(1.125726048);
+  z1 = (z3 - z2) * (T)QD_FIX(1.407403738);
+  tmp11 += z1 - z3 * (T)QD_FIX(0.766367282);
+  tmp12 += z1 + z2 * (T)QD_FIX(1.971951411);
+  z2 += z4;
+  z1 = z2 * (T)(-QD_FIX(0.666655658));
+  tmp1 += z1;
+  tmp3 += z1 + z4 * (T)QD_FIX(1.065388962);
+  z2 = z2 * (T)(-QD_FIX(1.247225013));
+  tmp10 += z2 + z4 * (T)QD_FIX(3.141271809);
+  tmp12 += z2;
+  z2 = (z3 + z4) * (T)(-QD_FIX(1.353318001));
+  tmp2 += z2;
+  tmp3 += z2;
+  z2 = (z4 - z3) * (T)QD_FIX(0.410524528);
+  tmp10 += z2;
+  tmp11 += z2;
+  out[0] = tmp20 + tmp0;  out[15] = tmp20 - tmp0;
+  out[1] = tmp21 + tmp1;  out[14] = tmp21 - tmp1;
+  out[2] = tmp22 + tmp2;  out[13] = tmp22 - tmp2;
+  out[3] = tmp23 + tmp3;  out[12] = tmp23 - tmp3;
+  out[4] = tmp24 + tmp10; out[11] = tmp24 - tmp10;
+  out[5] = tmp25 + tmp11; out[10] = tmp25 - tmp11;
+  out[6] = tmp26 + tmp12; out[9] = tmp26 - tmp12;
+  out[7] = tmp27 + tmp13; out[8] = tmp27 - tmp13;
+}
+
+// libjpeg 9's IDCT range limit (jdct.h: RANGE_CENTER 512, RANGE_SUBSET 384, RANGE_MASK 1023; jdmaster.c:
+// prepare_range_limit_table): index x = (v + 512) & 1023 of the descaled value v; limit[x] = clamp(x - 384, 0, 255).
+// The +512 is folded into pass 2's bias, so x arrives here already masked.
+QS_DEC_HD uint8_t qd_limit(uint32_t x) {
+  const int v = (int)(x & 1023) - 384;
+  return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+
+// pass-2 bias, added to in[0] << 13: (RANGE_CENTER << (PASS1_BITS + 3)) + (1 << (PASS1_BITS + 2)), then << 13
+#define QD_PASS2_BIAS ((uint32_t)((512u << 5) + (1u << 4)) << 13)
+
+// Pass 1 in wrapping 32-bit arithmetic is exact whenever its final sums fit int32: additions and products modulo 2^32
+// agree with the true ones modulo 2^32, and a sum in [-2^31, 2^31) is its own residue.  Each final sum is
+// sum_k M[i][k] * dq[k] + 2^10 with integer weights |M[i][k]| <= 2^13 * sqrt(2) * 1.0004 < 11590 (the composed FIX()
+// constants of the 8- and 16-point kernels), so |sum| <= 8 * 11590 * max|dq| + 2^10 < 2^31 for max|dq| <= 23000.
+// QS_DEC_FAST_BOUND takes 2^14; blocks above it take the 64-bit pass 1.
+#define QS_DEC_FAST_BOUND 16384
+
+// DEQUANTIZE of jidctint.c: an int product (|coef * q| <= 32768 * 65535 < 2^31, never overflows)
+QS_DEC_HD void qd_dequant(const int16_t* coef, const uint16_t* q, int32_t* dq) {
+  for (int i = 0; i < 64; ++i) dq[i] = (int32_t)coef[i] * (int32_t)q[i];
+}
+
+// One block of dequantised values dq: IDCT to rows x cols samples into dst (row stride `stride`).
+// W16: 16-point row pass (16 columns out), H16: 16-point column pass (16 rows out); XREP: each output column written
+// XREP times (2: libjpeg's h2v1 replication after a 16x8 IDCT, 4:1:1 chroma).
+template <bool W16, bool H16, int XREP = 1>
+QS_DEC_HD void qd_idct_block(const int32_t* dq, uint8_t* dst, int stride) {
+  constexpr int R = H16 ? 16 : 8, Cn = W16 ? 16 : 8;
+  int32_t ws[R * 8];                       // libjpeg's `int workspace[8 * R]`, here [row][col]
+  int32_t mx = 0;
+  QD_UNROLL
+  for (int i = 0; i < 64; ++i) {
+    const int32_t a = dq[i] < 0 ? -dq[i] : dq[i];        // (-32768 * 65535 > INT32_MIN: no overflow in the negation)
+    mx = a > mx ? a : mx;
+  }
+  const bool fast = mx <= QS_DEC_FAST_BOUND;
+  QD_UNROLL
+  for (int c = 0; c < 8; ++c) {                          // pass 1: columns
+    if (fast) {
+      uint32_t in[8], o[16];
+      QD_UNROLL
+  for (int k = 0; k < 8; ++k) in[k] = (uint32_t)dq[k * 8 + c];
+      if (H16) qd_idct16<uint32_t>(in, 1u << 10, o); else qd_idct8<uint32_t>(in, 1u << 10, o);
+      QD_UNROLL
+  for (int r = 0; r < R; ++r) ws[r * 8 + c] = (int32_t)o[r] >> 11;
+    } else {
+      int64_t in[8], o[16];
+      QD_UNROLL
+  for (int k = 0; k < 8; ++k) in[k] = dq[k * 8 + c];
+      if (H16) qd_idct16<int64_t>(in, (int64_t)1 << 10, o); else qd_idct8<int64_t>(in, (int64_t)1 << 10, o);
+      QD_UNROLL
+  for (int r = 0; r < R; ++r) ws[r * 8 + c] = (int32_t)(o[r] >> 11);   // (int) of libjpeg's INT32: wraps
+    }
+  }
+  QD_UNROLL
+  for (int r = 0; r < R; ++r) {                          // pass 2: rows, modulo 2^32
+    uint32_t in[8], o[16];
+    QD_UNROLL
+  for (int k = 0; k < 8; ++k) in[k] = (uint32_t)ws[r * 8 + k];
+    if (W16) qd_idct16<uint32_t>(in, QD_PASS2_BIAS, o); else qd_idct8<uint32_t>(in, QD_PASS2_BIAS, o);
+    QD_UNROLL
+  for (int c = 0; c < Cn; ++c) {
+      const uint8_t v = qd_limit(o[c] >> 18);
+      QD_UNROLL
+  for (int k = 0; k < XREP; ++k) dst[r * stride + c * XREP + k] = v;
+    }
+  }
+}
+
+// jdcolor.c (libjpeg 9, JCS_YCbCr): SCALEBITS 16, tables over the 256 chroma values
+#define QD_ONE_HALF (1 << 15)
+QS_DEC_HD int32_t qd_fix16(double x) { return (int32_t)(x * 65536.0 + 0.5); }
+QS_DEC_HD void qd_ycc_rgb(int y, int cb, int cr, uint8_t* out) {
+  const int xb = cb - 128, xr = cr - 128;
+  // (INT32 arithmetic: the products stay far below 2^31)
+  const int crr = (int)((qd_fix16(1.402) * xr + QD_ONE_HALF) >> 16);
+  const int cbb = (int)((qd_fix16(1.772) * xb + QD_ONE_HALF) >> 16);
+  const int g = (int)((-qd_fix16(0.714136286) * xr + (-qd_fix16(0.344136286) * xb + QD_ONE_HALF)) >> 16);
+  auto lim = [](int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); };   // sample_range_limit
+  out[0] = lim(y + crr);
+  out[1] = lim(y + g);
+  out[2] = lim(y + cbb);
+}

@@ -1,0 +1,113 @@
+// qs_kernels_decode.hip -- the kernel of the device decode to pixels (csrc/qs_decode_job.cpp,
+// qs_hip_decode_device_batch): dequantise, inverse DCT, chroma upsampling and colour conversion exactly as libjpeg 9
+// does them with JDCT_ISLOW and its default settings, for every job of a batch in ONE launch.
+//
+// A workgroup (one wave) owns an output tile of QS_DEC_TW x QS_DEC_TH = 64 x 16 pixels of one job, a whole number of
+// MCUs in every supported layout.  Phase 1: one lane per 8x8 block the tile needs -- 16 luma blocks, and per chroma
+// component the blocks whose scaled IDCT (libjpeg 9 upsamples 2x chroma by DCT scaling: jpeg_idct_16x16, _16x8, _8x16;
+// 4:1:1 = 16x8 then 2x horizontal replication) covers the tile -- reads its 128 bytes, runs the IDCT in registers and
+// writes the samples into LDS planes.  Phase 2: the lanes convert colour (jdcolor.c's integer tables, SCALEBITS 16)
+// into an LDS copy of the tile's output rows.  Phase 3: the rows go out as consecutive bytes per lane (coalesced).
+// Rows and columns beyond the image are neither computed into the output nor stored.
+//
+// Geometry and tables live in the caller's workspace (written by the prepare call); the arrays, the outputs and the
+// output extent travel in the kernel arguments (QsDecArgs), one chunk of up to QS_DEC_CHUNK jobs per launch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "qs_decode.h"
+
+#define QS_DEC_LANES 64
+
+__global__ void __launch_bounds__(QS_DEC_LANES)
+qs_decode_kernel(const QsDecArgs a) {
+  __shared__ uint8_t px[3][QS_DEC_TH][QS_DEC_TW];          // component samples of the tile
+  __shared__ uint8_t rows[QS_DEC_TH][QS_DEC_TW * 3];        // the tile's output rows
+  const QsDecJob* J = a.jobs;
+  const int tile = (int)blockIdx.x;
+  int lo = 0, hi = a.n - 1;                                // the job whose tiles hold this workgroup
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (J[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+  }
+  const QsDecJob& job = J[lo];
+  const int t = tile - job.tile0;
+  if (t < 0 || t >= job.tiles) return;
+  const int X0 = (t % job.tiles_x) * QS_DEC_TW, Y0 = (t / job.tiles_x) * QS_DEC_TH;
+  const QsDecPtrs& P = a.p[lo];
+  const int variant = job.two && a.d_stop && a.d_stop[a.job0 + lo] != 0 ? 1 : 0;
+  const QsDecGeom& g = job.g[variant];
+  if ((g.hs != 1 && g.hs != 2 && g.hs != 4) || (g.vs != 1 && g.vs != 2) || g.hs * g.vs > 4) return;   // (never prepared)
+  const int width = min(job.width, P.width), height = min(job.height, P.height);
+  const int lane = (int)threadIdx.x;
+
+  // phase 1: 16 luma blocks, then nc blocks per chroma component
+  const int ncomp = job.layout == QS_DEC_GRAY ? 1 : 3;
+  const int cw = 8 * g.hs, ch = 8 * g.vs;                  // pixels one chroma block covers
+  const int ncx = QS_DEC_TW / cw, nc = ncx * (QS_DEC_TH / ch);
+  if (lane < 16 + (ncomp - 1) * nc) {
+    int ci = 0, bx, by, x0, y0;
+    if (lane < 16) {
+      bx = (X0 >> 3) + (lane & 7); by = (Y0 >> 3) + (lane >> 3);
+      x0 = (lane & 7) * 8; y0 = (lane >> 3) * 8;
+    } else {
+      const int k = (lane - 16) % nc;
+      ci = 1 + (lane - 16) / nc;
+      bx = X0 / cw + k % ncx; by = Y0 / ch + k / ncx;
+      x0 = (k % ncx) * cw; y0 = (k / ncx) * ch;
+    }
+    const int pw = ci ? cw : 8, ph = ci ? ch : 8;
+    const int k = variant && ci ? 2 + ci : ci;
+    const int16_t* base = P.coef[k];
+    if (X0 + x0 < width && Y0 + y0 < height && bx < g.wblk[ci] && by < g.hblk[ci] &&
+        (long long)by * g.wblk[ci] + bx < P.nblk[k]) {
+      const int16_t* src = base + ((size_t)by * g.wblk[ci] + bx) * 64;
+      const uint4* s4 = reinterpret_cast<const uint4*>(src);
+      const uint16_t* q = job.q[ci];
+      int32_t dq[64];
+#pragma unroll
+      for (int v = 0; v < 8; ++v) {                        // the block's 128 bytes, 16 per load
+        const uint4 w = s4[v];
+        const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          dq[v * 8 + 2 * k] = (int32_t)(int16_t)(d[k] & 0xffff) * (int32_t)q[v * 8 + 2 * k];
+          dq[v * 8 + 2 * k + 1] = ((int32_t)d[k] >> 16) * (int32_t)q[v * 8 + 2 * k + 1];
+        }
+      }
+      uint8_t* dst = &px[ci][y0][x0];
+      if (pw == 8 && ph == 8) qd_idct_block<false, false>(dq, dst, QS_DEC_TW);
+      else if (pw == 16 && ph == 16) qd_idct_block<true, true>(dq, dst, QS_DEC_TW);
+      else if (pw == 16 && ph == 8) qd_idct_block<true, false>(dq, dst, QS_DEC_TW);
+      else if (pw == 8 && ph == 16) qd_idct_block<false, true>(dq, dst, QS_DEC_TW);
+      else qd_idct_block<true, false, 2>(dq, dst, QS_DEC_TW);     // 32 x 8: 4:1:1
+    }
+  }
+  __syncthreads();
+
+  // phase 2: colour conversion into the output rows (jdcolor.c: ycc_rgb_convert, rgb_convert, grayscale_convert)
+  const int w = min(QS_DEC_TW, width - X0), h = min(QS_DEC_TH, height - Y0);
+  for (int r = 0; r < h; ++r) {
+    if (lane >= w) break;
+    if (job.layout == QS_DEC_YCC) {
+      qd_ycc_rgb(px[0][r][lane], px[1][r][lane], px[2][r][lane], &rows[r][lane * 3]);
+    } else if (job.layout == QS_DEC_RGB) {
+      rows[r][lane * 3] = px[0][r][lane];
+      rows[r][lane * 3 + 1] = px[1][r][lane];
+      rows[r][lane * 3 + 2] = px[2][r][lane];
+    } else {
+      rows[r][lane] = px[0][r][lane];
+    }
+  }
+  __syncthreads();
+
+  // phase 3: the rows out, consecutive lanes on consecutive bytes
+  const int nb = w * job.nout;
+  for (int r = 0; r < h; ++r) {
+    uint8_t* out = P.out + (size_t)(Y0 + r) * P.pitch + (size_t)X0 * job.nout;
+    for (int b = lane; b < nb; b += QS_DEC_LANES) out[b] = rows[r][b];
+  }
+}
+
+void qs_launch_decode(const QsDecArgs& a, int tiles, hipStream_t s) {
+  if (tiles > 0) hipLaunchKernelGGL(qs_decode_kernel, dim3(tiles), dim3(QS_DEC_LANES), 0, s, a);
+}

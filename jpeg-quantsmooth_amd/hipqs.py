@@ -85,6 +85,11 @@ class DeviceInfo(C.Structure):
                 ("out_hsamp0", C.c_int32), ("out_vsamp0", C.c_int32), ("static_stop", C.c_int32)]
 
 
+class DecodeInfo(C.Structure):
+    """qs_hip_decode_info: the output of one job of the device decode (qs_hip_decode_device_batch_info)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32)]
+
+
 MAX_PLANES = 56
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -113,6 +118,12 @@ ABI = {
                                                C.c_void_p]),
     "qs_hip_do_quantsmooth_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                       C.c_size_t, C.c_void_p, C.c_void_p]),
+    "qs_hip_decode_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(DecodeInfo),
+                                                   C.POINTER(C.c_size_t)]),
+    "qs_hip_decode_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.c_size_t,
+                                                      C.c_void_p]),
+    "qs_hip_decode_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_free": (None, [C.c_void_p]),
     "qs_hip_release_cache": (None, []),
     "qs_hip_device_count": (C.c_int, []),
@@ -409,6 +420,33 @@ class HipQS:
         int32 at d_stop + 4 * i.  Sets each job's quant to 1 and up_* / out_*samp0 like the single-job call."""
         self._check(self.lib.qs_hip_do_quantsmooth_device_batch(self._job_ptrs(jobs), len(jobs), flags, niter,
                                                                 d_workspace, nbytes, d_stop, stream))
+
+    # -- device decode to pixels (a list of device_job() Jobs) ---------------------------
+    def decode_batch_info(self, jobs):
+        """qs_hip_decode_device_batch_info (no device needed) -> (list of dict(width, height, channels, layout),
+        the batch's workspace bytes)"""
+        per = (DecodeInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_decode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        return [{f: int(getattr(per[i], f)) for f, _ in DecodeInfo._fields_} for i in range(len(jobs))], int(total.value)
+
+    @staticmethod
+    def _outs(d_out, pitch):
+        return (C.c_void_p * max(1, len(d_out)))(*d_out), (C.c_size_t * max(1, len(pitch)))(*pitch)
+
+    def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_decode_device_batch_prepare: geometry and tables into the workspace (synchronises `stream`; not inside
+        a capture)"""
+        self._check(self.lib.qs_hip_decode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), d_workspace, nbytes,
+                                                                stream))
+
+    def decode_batch(self, jobs, d_stop, d_out, pitch, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_decode_device_batch: enqueue the decode of every job (one launch per 44 jobs); d_out[i] = device
+        address of job i's output, pitch[i] = bytes between its rows; d_stop: the device int32[njobs] a
+        smoothing run wrote (picks each UPSAMPLE_UV job's geometry on the device) or None"""
+        outs, pitches = self._outs(d_out, pitch)
+        self._check(self.lib.qs_hip_decode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, pitches,
+                                                        d_workspace, nbytes, stream))
 
     # -- plane layer (device pointers as ints, stream as int or None) ----------
     def idct_plane(self, d_consts, d_coef, d_plane, wblk, hblk, first, rep_top, rep_bot, d_status, stream=None):

@@ -15,6 +15,11 @@ capture a call that passes the same `workspace=`.
 
 runs many images in one call, their planes sharing kernel launches (qs_hip_do_quantsmooth_device_batch).
 
+    px = torch_qs.decode(coefs, quants, hsamp=[2, 1, 1], vsamp=[2, 1, 1], colorspace=3, image_size=(1920, 1080),
+                         result=res)   # uint8 (H, W, C): what libjpeg 9 decodes from the smoothed arrays
+
+decodes coefficient tensors to pixels on the device (qs_hip_decode_device_batch), after smoothing or on their own.
+
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
@@ -33,14 +38,15 @@ def _hip() -> HipQS:
 
 
 class Workspace:
-    """device workspace of one job geometry: a torch uint8 tensor plus what it was prepared for"""
+    """device workspace of one job geometry: a torch uint8 tensor plus what it was prepared for (decode and
+    decode_batch also take an empty Workspace() and fill it in place)"""
 
-    def __init__(self, buf, key=None):
+    def __init__(self, buf=None, key=None):
         self.buf, self.key = buf, key
 
     @property
     def nbytes(self) -> int:
-        return int(self.buf.numel())
+        return 0 if self.buf is None else int(self.buf.numel())
 
 
 def _key(job, flags, niter):
@@ -182,3 +188,121 @@ def quantsmooth_batch_(images, flags: int, niter: int, *, workspace: Workspace |
                                    image_size=im.get("image_size")))
     stop, out, workspace = _enqueue(jobs, tables, dev, flags, niter, workspace, who, False)
     return dict(stop=stop, images=out, workspace=workspace)
+
+
+# ---- decode to pixels (qs_hip_decode_device_batch) -------------------------------------------------------------------
+
+def _decode_job(hip, coefs, quants, im, res, who, torch):
+    """the qs_hip_job of one image to decode: its arrays and geometry, and what a smoothing result `res` reported
+    (the output tables, UPSAMPLE_UV's replacement chroma)"""
+    _check_tensors(coefs, torch, who=who)
+    if res is not None:
+        quants = res["quants"]
+    qs = _check_quants(quants, len(coefs), who=who)
+    up = res.get("coef_up") if res is not None else None
+    if up is not None:
+        _check_tensors(list(up), torch, who=f"{who}: coef_up")
+    job = hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=im.get("hsamp"),
+                         vsamp=im.get("vsamp"), colorspace=im.get("colorspace"), image_size=im.get("image_size"),
+                         coef_up=None if up is None else (up[0].data_ptr(), up[1].data_ptr()))
+    if up is not None:
+        job.up_hblk, job.up_wblk = int(up[0].shape[0]), int(up[0].shape[1])
+    return job
+
+
+def _decode_enqueue(jobs, dev, stop, outs, workspace, who):
+    """the decode's workspace (prepared outside any capture when the geometry or tables changed), the outputs, the run"""
+    import torch
+    hip = _hip()
+    per, total = hip.decode_batch_info(jobs)
+    key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs)
+    if workspace is None:
+        workspace = Workspace()
+    if workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
+                               f"geometry (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:      # (filled in place: decode() returns no dict)
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.decode_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+        workspace.key = key
+    if outs is None:
+        outs = [None] * len(jobs)
+    res = []
+    for i, (inf, o) in enumerate(zip(per, outs)):
+        shape = (inf["height"], inf["width"], inf["channels"])
+        if o is None:
+            o = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or tuple(o.shape) != shape:
+            raise ValueError(f"{who}: output {i} must be a uint8 tensor of shape {shape} on {dev}")
+        elif o.stride(2) != 1 or o.stride(1) != inf["channels"]:
+            raise ValueError(f"{who}: output {i} must have contiguous rows (stride {o.stride()})")
+        res.append(o)
+    pitches = [int(o.stride(0)) if o.shape[0] > 1 else o.shape[1] * o.shape[2] for o in res]
+    d_stop = None if stop is None else stop.data_ptr()
+    hip.decode_batch(jobs, d_stop, [o.data_ptr() for o in res], pitches, workspace.buf.data_ptr(), workspace.nbytes,
+                     torch.cuda.current_stream(dev).cuda_stream)
+    return res, workspace
+
+
+def _check_stop(stop, n, dev, who, torch):
+    if not isinstance(stop, torch.Tensor) or stop.dtype != torch.int32 or stop.device != dev or stop.numel() != n \
+            or not stop.is_contiguous():
+        raise ValueError(f"{who}: result['stop'] must be the int32 device tensor of {n} element(s) the smoothing returned")
+
+
+def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, out=None,
+           workspace: Workspace | None = None):
+    """Decode coefficient tensors to pixels on the current stream, exactly as libjpeg 9 does (JDCT_ISLOW, its default
+    upsampling -- 2x chroma by DCT scaling -- and default output colour space).  Returns a uint8 CUDA tensor
+    (image_height, image_width, C): C = 1 for grayscale, 3 (RGB) for YCbCr and RGB images.
+
+    coefs, quants, hsamp, vsamp, colorspace: as quantsmooth_ takes them; image_size = (width, height) is required.
+    result: what quantsmooth_ returned for these coefs -- its output tables and replacement chroma are used, and for
+    UPSAMPLE_UV the choice between the replacement chroma (stop 0) and the original chroma (stop 1) is made on the device
+    from result['stop'], with no host synchronisation.  out: a preallocated uint8 tensor of that shape (rows may be
+    padded).  workspace: a Workspace, prepared in place when the geometry or tables change (outside a capture) and
+    reused as it is inside one: pass the same object to the call that is captured."""
+    r = decode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
+                           image_size=image_size)],
+                     result=None if result is None else dict(stop=result["stop"], images=[result]),
+                     outs=None if out is None else [out], workspace=workspace, _who="decode")
+    return r["images"][0]
+
+
+def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None = None, _who="decode_batch") -> dict:
+    """decode on many images in one call (one kernel launch for up to 44 images).  images[i]: a dict with decode's
+    per-image arguments (coefs, quants, hsamp, vsamp, colorspace, image_size).  result: what quantsmooth_batch_ returned
+    for these images, in the same order.  outs: optional preallocated outputs.  Returns dict(images=[uint8 tensors],
+    workspace=Workspace)."""
+    import torch
+    who = _who
+    if not isinstance(images, (list, tuple)) or not images:
+        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    for i, im in enumerate(images):
+        if isinstance(im, dict) and im.get("image_size") is None:
+            raise ValueError(f"{who}: image {i} has no image_size: the decode needs (width, height)")
+    if result is not None and len(result["images"]) != len(images):
+        raise ValueError(f"{who}: result holds {len(result['images'])} images, the batch {len(images)}")
+    if outs is not None and len(outs) != len(images):
+        raise ValueError(f"{who}: one output (or None) per image")
+    hip = _hip()
+    dev, jobs = None, []
+    for i, im in enumerate(images):
+        if not isinstance(im, dict) or "coefs" not in im:
+            raise ValueError(f"{who}: image {i} must be a dict with coefs")
+        res = None if result is None else result["images"][i]
+        if res is None and im.get("quants") is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+        d = _check_tensors(im["coefs"], torch, who=f"{who}: image {i}")
+        if dev is None:
+            dev = d
+        elif d != dev:
+            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
+        jobs.append(_decode_job(hip, im["coefs"], im.get("quants"), im, res, f"{who}: image {i}", torch))
+    stop = None
+    if result is not None:
+        stop = result["stop"]
+        _check_stop(stop, len(images), dev, who, torch)
+    px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who)
+    return dict(images=px, workspace=workspace)

@@ -10,7 +10,13 @@ the spread shows.  The inputs are copied in before each call (the calls rewrite 
 every mode alike.  (a) and (b) must leave identical bytes (coefficients, replacement chroma, stops): checked first.
 Prints one JSON line.
 
-    python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]"""
+--decode times the device decode to pixels instead (torch_qs.decode_batch, one launch per batch): 8192^2 grayscale,
+8192^2 4:2:0 and --images x 1080p 4:2:0 in one batch, as time per call and GB/s of coefficients read plus samples
+written; and, for 8192^2 4:2:0, the host alternative it replaces: the copy of the coefficients to the host plus
+libjpeg 9's single-thread decode (tests/libjpeg9_decode.c, whose time includes writing the coefficients to an in-memory
+JPEG first).
+
+    python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5] [--decode]"""
 import argparse
 import json
 import sys
@@ -30,7 +36,10 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--decode", action="store_true", help="time the device decode to pixels instead")
     a = ap.parse_args()
+    if a.decode:
+        return bench_decode(a)
 
     import numpy as np
     import torch
@@ -126,6 +135,61 @@ def main():
         row["c_over_a"] = round(med["c_graph"] / med["a_loop"], 2)
         out["results"].append(row)
         del g
+    print(json.dumps(out), flush=True)
+
+
+def bench_decode(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import LibJpeg9, synth_image
+    torch_qs = jpegqs_pkg.load().torch_qs
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev)
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3)]),
+             (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3)] * a.images)]
+    out = dict(tool="bench_device_batch", leg="decode", device=torch.cuda.get_device_name(dev), results=[])
+    for name, ims in cases:
+        images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], quants=im["quants"], hsamp=im["hsamp"],
+                       vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
+        ws = torch_qs.Workspace()
+        outs = torch_qs.decode_batch(images, workspace=ws)["images"]
+        nbytes = sum(sum(c.numel() * 2 for c in im["coefs"]) for im in images) + sum(o.numel() for o in outs)
+        for _ in range(3):
+            torch_qs.decode_batch(images, outs=outs, workspace=ws)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            calls = 20
+            e0.record(stream)
+            for _ in range(calls):
+                torch_qs.decode_batch(images, outs=outs, workspace=ws)
+            e1.record(stream)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / calls)
+        med = float(np.median(ms))
+        row = dict(case=name, images=len(images), mbytes=round(nbytes / 1e6, 1), ms=[round(m, 4) for m in ms],
+                   median_ms=round(med, 4), gb_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
+        if name == "8192x8192_420":
+            with tempfile.TemporaryDirectory() as td:
+                lj9 = LibJpeg9(Path(td))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                host = [c.cpu().numpy() for c in images[0]["coefs"]]
+                t1 = time.perf_counter()
+                px = lj9.decode(host, ims[0]["quants"], ims[0]["hsamp"], ims[0]["vsamp"], 3, ims[0]["image_size"])
+                t2 = time.perf_counter()
+            row["host_alternative"] = dict(copy_ms=round((t1 - t0) * 1e3, 1), libjpeg9_ms=round((t2 - t1) * 1e3, 1),
+                                           identical=bool(np.array_equal(px, outs[0].cpu().numpy())))
+        out["results"].append(row)
     print(json.dumps(out), flush=True)
 
 
