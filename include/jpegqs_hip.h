@@ -271,6 +271,59 @@ int qs_hip_decode_device_batch_prepare(qs_hip_job *const *jobs, int njobs, void 
 int qs_hip_decode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint8_t *const *d_out,
 		const size_t *out_pitch, void *d_workspace, size_t bytes, void *stream);
 
+/* ---- device entropy coder (the coefficient arrays of device-resident jobs -> the bytes of a baseline JPEG scan) ----
+ * What libjpeg 9 writes between the SOS header and EOI when jpeg_write_coefficients gets the same arrays (jchuff.c:
+ * sequential Huffman, no scan script, no restart interval, 8-bit precision), byte for byte: one interleaved scan over all
+ * components (MCUs in raster order; blocks an edge MCU lacks are coded as jctrans.c's dummy blocks), or one
+ * non-interleaved scan for a one-component image; the last byte padded with one-bits, 0x00 after every 0xFF.  Jobs are
+ * qs_hip_job records over DEVICE arrays as the decode takes them: each array contiguous and 16-byte aligned
+ * (QS_HIP_EINVAL otherwise: an offset view of a larger buffer may not be), quant tables not needed; colour spaces 1
+ * (grayscale), 2 (RGB), 3 (YCbCr), 4 (CMYK), 5 (YCCK); more than 10 blocks in an MCU: QS_HIP_ENOTSUP.  A job with
+ * up_wblk > 0 has the decode's two geometries, chosen per job on the device from d_stop[i] (NULL: replacement chroma).
+ * Component ci uses DC and AC table dc_tbl[ci] = ac_tbl[ci]: what jpeg_set_colorspace assigns (table 1 for the chroma of
+ * YCbCr and YCCK, table 0 otherwise).  The same three-call pattern:
+ *   info       per_job[i] and *workspace_bytes; no device touched.  The workspace holds the unstuffed stream at its
+ *              worst-case size (208 bytes per block), so it is larger than the coefficient arrays;
+ *   prepare    geometry and Huffman code tables into the workspace; tables: NULL, or per job NULL or a qs_hip_huff_tables --
+ *              a table whose has_* byte is 0 is the standard table of JPEG Annex K.3 (libjpeg's default); may synchronise
+ *              `stream`, never inside a capture;
+ *   run        ENQUEUES seven kernel launches per QS_HIP_ENCODE_CHUNK jobs on `stream`: no allocation, no
+ *              synchronisation, no copy (graph-capturable, a linear graph).
+ * d_out[i]: device buffer of out_capacity[i] bytes; nothing is written at or beyond the capacity.  d_len[i] (device
+ * uint64): the bytes the segment needs.  d_status[i] (device int32): 0 ok; 1 a coefficient libjpeg refuses with
+ * JERR_BAD_DCT_COEF (an AC value of more than 10 bits, a DC difference of more than 11); 2 out_capacity[i] < d_len[i]
+ * (d_len is exact: retry with that size); 3 a symbol without a code in the tables given.  With 1 or 3 d_len[i] is 0 and
+ * the buffer's content unspecified.
+ *   histogram  the symbol counts of the same scan: d_counts = device uint32[njobs][4][257], tables in the order DC 0,
+ *              DC 1, AC 0, AC 1; entry 256 is libjpeg's reserved pseudo-symbol and reads 1.  d_status[i]: 0 or 1. */
+#define QS_HIP_ENCODE_CHUNK 32
+typedef struct {
+	uint8_t bits[17];      /* bits[l] = codes of length l (1..16), as in a DHT marker */
+	uint8_t huffval[256];  /* the symbols in order of increasing code length */
+} qs_hip_huff_table;
+typedef struct {
+	qs_hip_huff_table dc[2], ac[2];
+	uint8_t has_dc[2], has_ac[2];   /* 0: the standard table instead */
+} qs_hip_huff_tables;
+typedef struct {
+	int32_t dc_tbl[QS_HIP_MAXC], ac_tbl[QS_HIP_MAXC];   /* table of each component */
+	int32_t blocks_in_mcu[2];      /* of the two geometries (equal when the job has one) */
+	uint64_t max_segment_bytes;    /* no segment of this job is longer */
+} qs_hip_encode_info;
+int qs_hip_encode_device_batch_info(qs_hip_job *const *jobs, int njobs, qs_hip_encode_info *per_job,
+		size_t *workspace_bytes);
+int qs_hip_encode_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const qs_hip_huff_tables *const *tables,
+		void *d_workspace, size_t bytes, void *stream);
+int qs_hip_encode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint8_t *const *d_out,
+		const size_t *out_capacity, uint64_t *d_len, int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
+int qs_hip_encode_device_batch_histogram(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint32_t *d_counts,
+		int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
+/* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
+ * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT. */
+int qs_hip_huff_optimal(const uint32_t freq[257], uint8_t bits[17], uint8_t huffval[256]);
+/* Host only.  The standard table of Annex K.3: is_ac 0 / 1, tbl 0 (luminance) / 1 (chrominance). */
+int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[256]);
+
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up
  * to 2 GiB) and HIP streams in process-wide caches, each entry tied to the device it was created
@@ -289,7 +342,7 @@ const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
- * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode).  A caller built against
+ * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

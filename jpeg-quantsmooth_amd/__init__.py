@@ -6,6 +6,7 @@ driver, built in-tree by csrc/Makefile); this package only binds it (ctypes)
 and provides seeded synthetic inputs.  There is no CPU compute path here: if
 the library is missing, loading fails loudly.
 """
+from . import jpeg_file  # noqa: F401  (host only: the markers around an entropy-coded segment)
 from . import synth  # noqa: F401
 from . import torch_qs  # noqa: F401  (imports torch on first use only)
 from .hipqs import (  # noqa: F401
@@ -14,4 +15,4 @@ from .hipqs import (  # noqa: F401
 
 from .torch_qs import quantsmooth_, quantsmooth_batch_  # noqa: F401
 
-__all__ = ["synth", "torch_qs", "quantsmooth_", "quantsmooth_batch_", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]
+__all__ = ["jpeg_file", "synth", "torch_qs", "quantsmooth_", "quantsmooth_batch_", "FLAGS", "HipQS", "QsHipError", "flags_for_quality", "lib_path", "load_library"]

@@ -1,0 +1,77 @@
+// qs_encode.h -- the device entropy coder (qs_hip_encode_device_batch, csrc/qs_kernels_encode.hip): what the kernels
+// and the host driver (csrc/qs_encode_job.cpp) share.  The output is the entropy-coded segment of one baseline
+// sequential Huffman scan as libjpeg 9 (jchuff.c behind jpeg_write_coefficients) writes it: DESIGN.md section 13.
+#pragma once
+#include <stdint.h>
+
+#define QS_ENC_CHUNK 32            // jobs per launch set (their addresses travel in the kernel arguments, 3.1 KiB)
+#define QS_ENC_WG 256              // lanes per workgroup = scan blocks per workgroup of the sizing and emit kernels
+// longest code of one block: DC 16 + 11 bits, 63 AC of 16 + 10 bits
+#define QS_ENC_MAXBITS (27 + 63 * 26)
+// words the emit kernel stages per workgroup: 256 blocks of QS_ENC_MAXBITS behind up to 31 bits of the word they start in
+#define QS_ENC_LDS_WORDS ((31 + QS_ENC_WG * QS_ENC_MAXBITS + 31) / 32)
+#define QS_ENC_SCHUNK 4096         // bytes of the unstuffed stream per stuffing step (16 per lane)
+#define QS_ENC_SWG_MAX 1024        // workgroups a job's stuffing kernels get at most (they stride over the chunks)
+
+// status bits collected per job while it runs (QsEncState.flags); the caller sees 1, 3 or 2 in this order of precedence
+#define QS_ENC_F_BADCOEF 1u
+#define QS_ENC_F_NOCODE 2u
+
+// the scan of one geometry: how scan block b maps to a component and a block of its array
+struct QsEncGeom {
+  int32_t ncomp;
+  int32_t nw[4], nh[4];            // libjpeg's width_in_blocks / height_in_blocks: the blocks that exist
+  int32_t stride[4];               // row stride of the array in blocks
+  int32_t hs[4], vs[4];            // blocks per MCU across / down (1 x 1 in a one-component scan)
+  int32_t first[4];                // index of the component's first block inside an MCU
+  int32_t slot[4];                 // which of QsEncPtrs.coef holds the component
+  int32_t mcus_x, mcus, bpm;       // MCUs per row, MCUs in the scan, blocks per MCU
+  int32_t nblocks;                 // mcus * bpm
+};
+
+// One job as the kernels see it (workspace, written by prepare): geometry, code tables and where its scratch arrays
+// lie in the workspace.  No addresses of caller memory.
+struct QsEncJob {
+  QsEncGeom g[2];                  // variant 0 (d_stop 0: replacement chroma when the job has it), variant 1
+  int32_t two;                     // 1: the variant follows d_stop[job]
+  int32_t tbl[4];                  // Huffman table (0 / 1) of each component
+  int32_t wg0, nwg;                // sizing / emit workgroups of this job in its chunk's launches
+  int32_t swg0, nswg;              // the same for the stuffing kernels
+  int32_t pad;
+  uint64_t off_bits;               // uint16[nwg * 256]: code length of each scan block
+  uint64_t off_wgsum;              // uint32[nwg]: bits of each workgroup's blocks
+  uint64_t off_wgoff;              // uint64[nwg]: their exclusive scan
+  uint64_t off_raw, raw_cap;       // the unstuffed stream (bytes), its capacity
+  uint64_t off_ffcnt;              // uint32[raw_cap / QS_ENC_SCHUNK]: 0xFF bytes per stuffing chunk
+  uint64_t off_ffoff;              // uint64[...]: their exclusive scan
+  uint64_t off_state;              // QsEncState
+  uint32_t dc[2][16];              // (size << 16) | code by category; size 0 = the table has no such symbol
+  uint32_t ac[2][256];             // the same by run/size symbol
+};
+
+struct QsEncState {
+  uint64_t total_bits;             // of the unstuffed stream
+  uint64_t raw_bytes;              // ceil(total_bits / 8)
+  uint32_t flags;                  // QS_ENC_F_*
+  uint32_t dead;                   // 1: flags were set when the scan ran; the later kernels leave the job alone
+  uint32_t nchunks, pad;
+};
+
+struct QsEncPtrs {
+  const int16_t* coef[6];          // 0..3 variant 0's arrays; 4..5 variant 1's chroma (component 0 is coef[0] in both)
+  int32_t nblk[6];                 // blocks in each array: the kernels bound every read by them
+  uint8_t* out;
+  uint64_t cap;                    // bytes the caller's buffer holds
+};
+struct QsEncArgs {
+  const QsEncJob* jobs;            // the chunk's descriptors (workspace)
+  uint8_t* ws;                     // the workspace base the descriptors' offsets refer to
+  const int32_t* d_stop;           // the caller's int32[njobs] or null, indexed by job0 + i
+  uint64_t* d_len;                 // indexed by job0 + i
+  int32_t* d_status;
+  uint32_t* d_counts;              // histogram run: uint32[njobs][4][257], else null
+  int32_t job0, n;
+  int32_t wg0[QS_ENC_CHUNK];       // each job's first workgroup in the block kernels' launch (QsEncJob.wg0) ...
+  int32_t swg0[QS_ENC_CHUNK];      // ... and in the stuffing kernels': a workgroup finds its job without touching memory
+  QsEncPtrs p[QS_ENC_CHUNK];
+};

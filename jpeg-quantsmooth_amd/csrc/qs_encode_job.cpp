@@ -1,0 +1,415 @@
+// qs_encode_job.cpp -- the device entropy coder of the flat C ABI (include/jpegqs_hip.h):
+// qs_hip_encode_device_batch_info / _prepare / qs_hip_encode_device_batch / _histogram, and the host-only
+// qs_hip_huff_optimal / qs_hip_huff_standard.  What libjpeg 9 writes between the SOS header and EOI for
+// jpeg_write_coefficients on the arrays of qs_hip_job records (no scan script, no restart interval, 8 bits), computed
+// on the device (qs_kernels_encode.hip).
+//
+// Workspace: the QsEncJob descriptors of the batch, then per job its scratch arrays (block code lengths, workgroup
+// sums and offsets, the unstuffed stream at its worst-case size, the stuffing counts) -- a function of the jobs'
+// geometry alone; the code tables in the descriptors come from prepare's `tables`.
+#include "qs_common.h"
+#include "qs_encode.h"
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, hipStream_t s);
+
+namespace {
+
+// JPEG Annex K.3 (the tables libjpeg installs with jpeg_set_defaults): [0] luminance, [1] chrominance
+const uint8_t STD_DC_BITS[2][17] = {{0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
+                                    {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t STD_AC_BITS[2][17] = {{0, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
+                                    {0, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+const uint8_t STD_AC_VAL[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+
+void standard_table(int is_ac, int tbl, qs_hip_huff_table* t) {
+  memset(t, 0, sizeof *t);
+  if (is_ac) {
+    memcpy(t->bits, STD_AC_BITS[tbl], 17);
+    memcpy(t->huffval, STD_AC_VAL[tbl], 162);
+  } else {
+    memcpy(t->bits, STD_DC_BITS[tbl], 17);
+    for (int i = 0; i < 12; ++i) t->huffval[i] = (uint8_t)i;
+  }
+}
+
+// jpeg_make_c_derived_tbl of jchuff.c: (size << 16) | code per symbol, 0 where the table has none
+int derive(const qs_hip_huff_table& t, bool is_dc, uint32_t* out, int nout, const char* who, const char* what) {
+  for (int i = 0; i < nout; ++i) out[i] = 0;
+  int p = 0;
+  uint32_t code = 0;
+  for (int l = 1; l <= 16; ++l) {
+    for (int i = 0; i < t.bits[l]; ++i, ++p, ++code) {
+      if (p >= 256 || code >= (1u << l)) return qs_fail(QS_HIP_EINVAL, "%s: %s is not a valid Huffman table", who, what);
+      const int sym = t.huffval[p];
+      if ((is_dc && sym > 15) || out[sym % nout])
+        return qs_fail(QS_HIP_EINVAL, "%s: %s has a bad or repeated symbol 0x%02x", who, what, sym);
+      out[sym] = ((uint32_t)l << 16) | code;
+    }
+    code <<= 1;
+  }
+  return QS_HIP_OK;
+}
+
+int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+// one geometry: the sampling factors hs / vs, array strides and slots of its components
+int geometry(const qs_hip_job* job, const int* hs, const int* vs, const int* stride, const int* rows, const int* slot,
+             QsEncGeom* g, const char* who) {
+  const int n = job->ncomp, W = job->image_width, H = job->image_height;
+  int mh = 1, mv = 1;
+  for (int c = 0; c < n; ++c) {
+    mh = std::max(mh, hs[c]);
+    mv = std::max(mv, vs[c]);
+  }
+  memset(g, 0, sizeof *g);
+  g->ncomp = n;
+  for (int c = 0; c < n; ++c) {
+    g->nw[c] = ceil_div((long long)W * hs[c], 8LL * mh);          // jcmaster.c: width_in_blocks / height_in_blocks
+    g->nh[c] = ceil_div((long long)H * vs[c], 8LL * mv);
+    g->stride[c] = stride[c];
+    g->slot[c] = slot[c];
+    if (stride[c] < g->nw[c] || rows[c] < g->nh[c])
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d has %d x %d blocks, a %d x %d image sampled %dx%d needs %d x %d", who, c,
+                     stride[c], rows[c], W, H, hs[c], vs[c], g->nw[c], g->nh[c]);
+  }
+  if (n == 1) {                                                   // non-interleaved: an MCU is one block
+    g->hs[0] = g->vs[0] = 1;
+    g->bpm = 1;
+    g->mcus_x = g->nw[0];
+    g->mcus = g->nw[0] * g->nh[0];
+  } else {
+    int first = 0;
+    for (int c = 0; c < n; ++c) {
+      g->hs[c] = hs[c];
+      g->vs[c] = vs[c];
+      g->first[c] = first;
+      first += hs[c] * vs[c];
+    }
+    if (first > 10)
+      return qs_fail(QS_HIP_ENOTSUP, "%s: %d blocks in an MCU; libjpeg takes at most 10", who, first);
+    g->bpm = first;
+    g->mcus_x = ceil_div(W, 8LL * mh);
+    const long long mcus = (long long)g->mcus_x * ceil_div(H, 8LL * mv);
+    if (mcus * first > 0x7fff0000LL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 blocks in the scan", who);
+    g->mcus = (int)mcus;
+  }
+  g->nblocks = g->mcus * g->bpm;
+  return QS_HIP_OK;
+}
+
+int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, qs_hip_encode_info* info, const char* who) {
+  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
+  const int n = job->ncomp;
+  if (job->image_width <= 0 || job->image_height <= 0 || job->image_width > 65500 || job->image_height > 65500)
+    return qs_fail(QS_HIP_EINVAL, "%s: the encoder needs image_width x image_height within 65500 (got %d x %d)", who,
+                   job->image_width, job->image_height);
+  memset(D, 0, sizeof *D);
+  if (P) memset(P, 0, sizeof *P);
+  // jpeg_set_colorspace: table 1 for the chroma of YCbCr and YCCK, table 0 for everything else
+  const int cs = job->colorspace;
+  const int need = cs == 1 ? 1 : (cs == 2 || cs == 3) ? 3 : (cs == 4 || cs == 5) ? 4 : 0;
+  if (need != n)
+    return qs_fail(QS_HIP_ENOTSUP, "%s: %d components in colour space %d: the encoder covers grayscale (1), RGB and YCbCr (3), "
+                   "CMYK and YCCK (4)", who, n, cs);
+  for (int c = 0; c < n; ++c) {
+    D->tbl[c] = ((cs == 3 || cs == 5) && (c == 1 || c == 2)) ? 1 : 0;
+    if (job->hsamp[c] < 1 || job->hsamp[c] > 4 || job->vsamp[c] < 1 || job->vsamp[c] > 4)
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d has sampling factors %dx%d", who, c, job->hsamp[c], job->vsamp[c]);
+    if (job->wblk[c] < 1 || job->hblk[c] < 1) return qs_fail(QS_HIP_EINVAL, "%s: component %d has no blocks", who, c);
+  }
+  const bool up = job->up_wblk > 0 && n == 3;
+  int hs[4], vs[4], stride[4], rows[4], slot[4];
+  for (int v = 0; v < (up ? 2 : 1); ++v) {
+    const bool repl = up && v == 0;
+    for (int c = 0; c < n; ++c) {
+      const bool r = repl && c > 0;
+      hs[c] = job->hsamp[c];
+      vs[c] = job->vsamp[c];
+      if (repl) {                                                 // the reference's result: chroma at luma resolution
+        hs[c] = c ? 1 : (job->out_hsamp0 > 0 ? job->out_hsamp0 : 1);
+        vs[c] = c ? 1 : (job->out_vsamp0 > 0 ? job->out_vsamp0 : 1);
+      }
+      stride[c] = r ? job->up_wblk : job->wblk[c];
+      rows[c] = r ? job->up_hblk : job->hblk[c];
+      slot[c] = (up && !repl && c) ? 3 + c : c;
+      const int16_t* arr = r ? job->coef_up[c - 1] : job->coef[c];
+      if (need_arrays && (!arr || (reinterpret_cast<uintptr_t>(arr) & 15)))
+        return qs_fail(QS_HIP_EINVAL, "%s: component %d%s has no data or is not 16-byte aligned", who, c,
+                       r ? " (replacement chroma)" : "");
+      if (P) {
+        P->coef[slot[c]] = arr;
+        P->nblk[slot[c]] = stride[c] * rows[c];
+      }
+    }
+    if (int rc = geometry(job, hs, vs, stride, rows, slot, &D->g[v], who)) return rc;
+  }
+  D->two = up ? 1 : 0;
+  if (info) {
+    memset(info, 0, sizeof *info);
+    for (int c = 0; c < n; ++c) info->dc_tbl[c] = info->ac_tbl[c] = D->tbl[c];
+    info->blocks_in_mcu[0] = D->g[0].bpm;
+    info->blocks_in_mcu[1] = up ? D->g[1].bpm : D->g[0].bpm;
+  }
+  return QS_HIP_OK;
+}
+
+struct Who {
+  char s[96];
+  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
+};
+
+uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QsEncJob), 256); }
+
+// the descriptors of a batch with their workspace layout; returns the workspace size in *total
+int describe_all(qs_hip_job* const* jobs, int njobs, bool need_arrays, std::vector<QsEncJob>& D, std::vector<QsEncPtrs>* P,
+                 qs_hip_encode_info* info, uint64_t* total, const char* who) {
+  if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
+  D.assign((size_t)njobs, QsEncJob());
+  if (P) P->assign((size_t)njobs, QsEncPtrs());
+  uint64_t off = descriptors_bytes(njobs);
+  long long wgs = 0, swgs = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (int r = describe(jobs[i], &D[i], P ? &(*P)[i] : nullptr, need_arrays, info ? &info[i] : nullptr, Who(who, i).s))
+      return r;
+    QsEncJob& J = D[i];
+    if (i % QS_ENC_CHUNK == 0) wgs = swgs = 0;
+    const int nblocks = std::max(J.g[0].nblocks, J.two ? J.g[1].nblocks : 0);
+    J.nwg = ceil_div(nblocks, QS_ENC_WG);
+    J.wg0 = (int)wgs;
+    wgs += J.nwg;
+    const uint64_t slots = (uint64_t)J.nwg * QS_ENC_WG;
+    J.raw_cap = align_up((slots * QS_ENC_MAXBITS + 7) / 8, 16) + 16;
+    const uint64_t chunks = (J.raw_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK;
+    J.nswg = (int)std::min<uint64_t>(chunks, QS_ENC_SWG_MAX);
+    J.swg0 = (int)swgs;
+    swgs += J.nswg;
+    if (wgs > 0x7fffffffLL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
+    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += align_up(bytes, 256); return at; };
+    J.off_state = take(sizeof(QsEncState));
+    J.off_bits = take(slots * 2);
+    J.off_wgsum = take((uint64_t)J.nwg * 4);
+    J.off_wgoff = take((uint64_t)J.nwg * 8);
+    J.off_raw = take(J.raw_cap);
+    J.off_ffcnt = take(chunks * 4);
+    J.off_ffoff = take(chunks * 8);
+    if (info) info[i].max_segment_bytes = 2 * (((uint64_t)nblocks * QS_ENC_MAXBITS + 7) / 8);   // every byte stuffed
+  }
+  *total = off;
+  return QS_HIP_OK;
+}
+
+int check_ws(uint64_t need, const void* d_workspace, size_t bytes, const char* who) {
+  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < need)
+    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %llu", who, bytes,
+                   (unsigned long long)need);
+  return QS_HIP_OK;
+}
+
+int device_ok() {
+  if (qs_hip_device_count() <= 0)
+    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+  return QS_HIP_OK;
+}
+
+template <class F> int guarded(F f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
+  } catch (...) {
+    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
+  }
+}
+
+// what the run and the histogram call share: the chunks' kernel arguments and launches
+int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* const* d_out, const size_t* out_capacity,
+            uint64_t* d_len, int32_t* d_status, uint32_t* d_counts, void* d_workspace, size_t bytes, void* stream,
+            const char* who) {
+  std::vector<QsEncJob> D;
+  std::vector<QsEncPtrs> P;
+  uint64_t total = 0;
+  if (int r = describe_all(jobs, njobs, true, D, &P, nullptr, &total, who)) return r;
+  if (!d_counts) {
+    if (!d_out || !out_capacity || !d_len || !d_status) return qs_fail(QS_HIP_EINVAL, "%s: null output argument", who);
+    for (int i = 0; i < njobs; ++i) {
+      if (!d_out[i]) return qs_fail(QS_HIP_EINVAL, "%s: job %d has no output buffer", who, i);
+      P[(size_t)i].out = d_out[i];
+      P[(size_t)i].cap = out_capacity[i];
+    }
+  }
+  if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+  if (int r = device_ok()) return r;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int j0 = 0; j0 < njobs; j0 += QS_ENC_CHUNK) {
+    QsEncArgs a;
+    memset(&a, 0, sizeof a);
+    a.jobs = static_cast<const QsEncJob*>(d_workspace) + j0;
+    a.ws = static_cast<uint8_t*>(d_workspace);
+    a.d_stop = d_stop;
+    a.d_len = d_len;
+    a.d_status = d_status;
+    a.d_counts = d_counts;
+    a.job0 = j0;
+    a.n = std::min(QS_ENC_CHUNK, njobs - j0);
+    for (int k = 0; k < a.n; ++k) {
+      a.p[k] = P[(size_t)j0 + k];
+      a.wg0[k] = D[(size_t)j0 + k].wg0;
+      a.swg0[k] = D[(size_t)j0 + k].swg0;
+    }
+    const QsEncJob& last = D[(size_t)j0 + a.n - 1];
+    qs_launch_encode(a, last.wg0 + last.nwg, last.swg0 + last.nswg, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return QS_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int qs_hip_encode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_encode_info* per_job,
+                                               size_t* bytes) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_encode_device_batch_info";
+    if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
+    std::vector<QsEncJob> D;
+    uint64_t total = 0;
+    if (int r = describe_all(jobs, njobs, false, D, nullptr, per_job, &total, who)) return r;
+    *bytes = (size_t)total;
+    return QS_HIP_OK;
+  });
+}
+
+extern "C" int qs_hip_encode_device_batch_prepare(qs_hip_job* const* jobs, int njobs,
+                                                  const qs_hip_huff_tables* const* tables, void* d_workspace,
+                                                  size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_encode_device_batch_prepare";
+    std::vector<QsEncJob> D;
+    uint64_t total = 0;
+    if (int r = describe_all(jobs, njobs, false, D, nullptr, nullptr, &total, who)) return r;
+    for (int i = 0; i < njobs; ++i) {
+      const qs_hip_huff_tables* T = tables ? tables[i] : nullptr;
+      for (int t = 0; t < 2; ++t) {
+        qs_hip_huff_table dc, ac;
+        if (T && T->has_dc[t]) dc = T->dc[t]; else standard_table(0, t, &dc);
+        if (T && T->has_ac[t]) ac = T->ac[t]; else standard_table(1, t, &ac);
+        char what[64];
+        snprintf(what, sizeof what, "job %d, DC table %d", i, t);
+        if (int r = derive(dc, true, D[(size_t)i].dc[t], 16, who, what)) return r;
+        snprintf(what, sizeof what, "job %d, AC table %d", i, t);
+        if (int r = derive(ac, false, D[(size_t)i].ac[t], 256, who, what)) return r;
+      }
+    }
+    if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+    if (int r = device_ok()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsEncJob), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
+    return QS_HIP_OK;
+  });
+}
+
+extern "C" int qs_hip_encode_device_batch(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop,
+                                          uint8_t* const* d_out, const size_t* out_capacity, uint64_t* d_len,
+                                          int32_t* d_status, void* d_workspace, size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    return enqueue(jobs, njobs, d_stop, d_out, out_capacity, d_len, d_status, nullptr, d_workspace, bytes, stream,
+                   "qs_hip_encode_device_batch");
+  });
+}
+
+extern "C" int qs_hip_encode_device_batch_histogram(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop,
+                                                    uint32_t* d_counts, int32_t* d_status, void* d_workspace,
+                                                    size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_encode_device_batch_histogram";
+    if (!d_counts) return qs_fail(QS_HIP_EINVAL, "%s: null d_counts", who);
+    return enqueue(jobs, njobs, d_stop, nullptr, nullptr, nullptr, d_status, d_counts, d_workspace, bytes, stream, who);
+  });
+}
+
+extern "C" int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[256]) {
+  if (tbl < 0 || tbl > 1 || !bits || !huffval) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_standard: table 0 or 1");
+  qs_hip_huff_table t;
+  standard_table(is_ac != 0, tbl, &t);
+  memcpy(bits, t.bits, 17);
+  memcpy(huffval, t.huffval, 256);
+  return QS_HIP_OK;
+}
+
+// jpeg_gen_optimal_table of jchuff.c (JPEG Annex K.2): Huffman's procedure with the reserved pseudo-symbol 256 and code
+// lengths cut back to 16 (figure K.3) give the number of codes of each length.  The symbols are listed as libjpeg 9d
+// lists them: by falling count, equal counts by rising value -- so a more frequent symbol never has the longer code,
+// also where the cut-back split a length (the 9c and earlier order, by length then value, differs in the DHT bytes)
+extern "C" int qs_hip_huff_optimal(const uint32_t freq_in[257], uint8_t bits_out[17], uint8_t huffval[256]) {
+  if (!freq_in || !bits_out || !huffval) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_optimal: null argument");
+  return guarded([&]() -> int {
+  const int MAXLEN = 32;
+  long long freq[257];
+  int bits[MAXLEN + 1] = {0}, codesize[257] = {0}, others[257];
+  for (int i = 0; i < 256; ++i) freq[i] = freq_in[i];
+  freq[256] = 1;                                           // no real symbol gets the all-ones code
+  for (int i = 0; i < 257; ++i) others[i] = -1;
+  for (;;) {
+    int c1 = -1, c2 = -1;
+    long long v = 1000000000000LL;
+    for (int i = 0; i <= 256; ++i)                         // the least frequent symbol, the larger value in a tie
+      if (freq[i] && freq[i] <= v) { v = freq[i]; c1 = i; }
+    v = 1000000000000LL;
+    for (int i = 0; i <= 256; ++i)
+      if (freq[i] && freq[i] <= v && i != c1) { v = freq[i]; c2 = i; }
+    if (c2 < 0) break;
+    freq[c1] += freq[c2];
+    freq[c2] = 0;
+    for (++codesize[c1]; others[c1] >= 0;) { c1 = others[c1]; ++codesize[c1]; }
+    others[c1] = c2;
+    for (++codesize[c2]; others[c2] >= 0;) { c2 = others[c2]; ++codesize[c2]; }
+  }
+  for (int i = 0; i <= 256; ++i)
+    if (codesize[i]) {
+      if (codesize[i] > MAXLEN) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_optimal: code length overflow");
+      ++bits[codesize[i]];
+    }
+  int i;
+  for (i = MAXLEN; i > 16; --i)
+    while (bits[i] > 0) {
+      int j = i - 2;
+      while (bits[j] == 0) --j;
+      bits[i] -= 2;
+      ++bits[i - 1];
+      bits[j + 1] += 2;
+      --bits[j];
+    }
+  while (bits[i] == 0) --i;                                // the reserved symbol leaves the longest length
+  --bits[i];
+  bits_out[0] = 0;
+  for (int l = 1; l <= 16; ++l) bits_out[l] = (uint8_t)bits[l];
+  memset(huffval, 0, 256);
+  std::vector<int> syms;
+  for (int s = 0; s < 256; ++s)
+    if (freq_in[s]) syms.push_back(s);
+  std::stable_sort(syms.begin(), syms.end(), [&](int a, int b) { return freq_in[a] > freq_in[b]; });
+  for (size_t p = 0; p < syms.size(); ++p) huffval[p] = (uint8_t)syms[p];
+  return QS_HIP_OK;
+  });
+}

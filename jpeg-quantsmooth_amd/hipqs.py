@@ -90,6 +90,22 @@ class DecodeInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32)]
 
 
+class HuffTable(C.Structure):
+    """qs_hip_huff_table: bits[l] = codes of length l, huffval = the symbols by increasing code length"""
+    _fields_ = [("bits", C.c_uint8 * 17), ("huffval", C.c_uint8 * 256)]
+
+
+class HuffTables(C.Structure):
+    """qs_hip_huff_tables: up to two DC and two AC tables of one job (has_* 0: the standard table)"""
+    _fields_ = [("dc", HuffTable * 2), ("ac", HuffTable * 2), ("has_dc", C.c_uint8 * 2), ("has_ac", C.c_uint8 * 2)]
+
+
+class EncodeInfo(C.Structure):
+    """qs_hip_encode_info: one job of the device entropy coder (qs_hip_encode_device_batch_info)"""
+    _fields_ = [("dc_tbl", C.c_int32 * MAXC), ("ac_tbl", C.c_int32 * MAXC), ("blocks_in_mcu", C.c_int32 * 2),
+                ("max_segment_bytes", C.c_uint64)]
+
+
 MAX_PLANES = 56
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -124,6 +140,17 @@ ABI = {
                                                       C.c_void_p]),
     "qs_hip_decode_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_encode_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(EncodeInfo),
+                                                   C.POINTER(C.c_size_t)]),
+    "qs_hip_encode_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(HuffTables)),
+                                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_encode_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]),
+    "qs_hip_encode_device_batch_histogram": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_huff_optimal": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "qs_hip_huff_standard": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_free": (None, [C.c_void_p]),
     "qs_hip_release_cache": (None, []),
     "qs_hip_device_count": (C.c_int, []),
@@ -447,6 +474,68 @@ class HipQS:
         outs, pitches = self._outs(d_out, pitch)
         self._check(self.lib.qs_hip_decode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, pitches,
                                                         d_workspace, nbytes, stream))
+
+    # -- device entropy coder (a list of device_job() Jobs) -------------------------------
+    def encode_batch_info(self, jobs):
+        """qs_hip_encode_device_batch_info (no device needed) -> (list of dict(dc_tbl, ac_tbl, blocks_in_mcu,
+        max_segment_bytes), the batch's workspace bytes)"""
+        per = (EncodeInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_encode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        return [dict(dc_tbl=list(per[i].dc_tbl[:jobs[i].ncomp]), ac_tbl=list(per[i].ac_tbl[:jobs[i].ncomp]),
+                     blocks_in_mcu=list(per[i].blocks_in_mcu), max_segment_bytes=int(per[i].max_segment_bytes))
+                for i in range(len(jobs))], int(total.value)
+
+    @staticmethod
+    def huff_tables(dc=None, ac=None) -> HuffTables:
+        """a qs_hip_huff_tables: dc / ac = {table index: (bits[17], huffval)}; a table left out is the standard one"""
+        t = HuffTables()
+        for tabs, arr, has in ((dc or {}, t.dc, t.has_dc), (ac or {}, t.ac, t.has_ac)):
+            for k, (bits, vals) in tabs.items():
+                if k not in (0, 1) or len(bits) != 17 or len(vals) > 256:
+                    raise ValueError("huff_tables: table 0 or 1, bits[17], at most 256 symbols")
+                arr[k].bits[:] = [int(b) for b in bits]
+                for i, v in enumerate(vals):
+                    arr[k].huffval[i] = int(v)
+                has[k] = 1
+        return t
+
+    def encode_batch_prepare(self, jobs, tables, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_encode_device_batch_prepare: geometry and code tables into the workspace (synchronises `stream`; not
+        inside a capture); tables: None or one HuffTables / None per job"""
+        ptrs = None
+        if tables is not None:
+            ptrs = (C.POINTER(HuffTables) * max(1, len(jobs)))(*[C.pointer(t) if t is not None else None for t in tables])
+        self._check(self.lib.qs_hip_encode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), ptrs, d_workspace,
+                                                                nbytes, stream))
+
+    def encode_batch(self, jobs, d_stop, d_out, capacity, d_len: int, d_status: int, d_workspace: int, nbytes: int,
+                     stream=None) -> None:
+        """qs_hip_encode_device_batch: enqueue the scan coder of every job; d_out[i] = device address of job i's buffer
+        of capacity[i] bytes, d_len / d_status = device uint64[njobs] / int32[njobs]"""
+        outs, caps = self._outs(d_out, capacity)
+        self._check(self.lib.qs_hip_encode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, caps, d_len,
+                                                        d_status, d_workspace, nbytes, stream))
+
+    def encode_batch_histogram(self, jobs, d_stop, d_counts: int, d_status: int, d_workspace: int, nbytes: int,
+                               stream=None) -> None:
+        """qs_hip_encode_device_batch_histogram: symbol counts uint32[njobs][4][257] (DC 0, DC 1, AC 0, AC 1)"""
+        self._check(self.lib.qs_hip_encode_device_batch_histogram(self._job_ptrs(jobs), len(jobs), d_stop, d_counts,
+                                                                  d_status, d_workspace, nbytes, stream))
+
+    def huff_optimal(self, freq):
+        """qs_hip_huff_optimal (host only): symbol counts (256 or 257) -> (bits[17], huffval) as libjpeg's
+        optimize_coding makes them"""
+        f = (C.c_uint32 * 257)(*([int(v) for v in list(freq)[:256]] + [1]))
+        bits, vals = (C.c_uint8 * 17)(), (C.c_uint8 * 256)()
+        self._check(self.lib.qs_hip_huff_optimal(f, bits, vals))
+        return list(bits), list(vals)[:sum(bits)]
+
+    def huff_standard(self, is_ac: int, tbl: int):
+        """qs_hip_huff_standard (host only): the table of JPEG Annex K.3 -> (bits[17], huffval)"""
+        bits, vals = (C.c_uint8 * 17)(), (C.c_uint8 * 256)()
+        self._check(self.lib.qs_hip_huff_standard(int(is_ac), int(tbl), bits, vals))
+        return list(bits), list(vals)[:sum(bits)]
 
     # -- plane layer (device pointers as ints, stream as int or None) ----------
     def idct_plane(self, d_consts, d_coef, d_plane, wblk, hblk, first, rep_top, rep_bot, d_status, stream=None):

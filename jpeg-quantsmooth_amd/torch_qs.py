@@ -20,6 +20,11 @@ runs many images in one call, their planes sharing kernel launches (qs_hip_do_qu
 
 decodes coefficient tensors to pixels on the device (qs_hip_decode_device_batch), after smoothing or on their own.
 
+    data = torch_qs.encode(coefs, quants, hsamp=[2, 1, 1], vsamp=[2, 1, 1], colorspace=3, image_size=(1920, 1080),
+                           result=res)   # bytes: the JPEG file libjpeg 9 writes from the smoothed arrays
+
+entropy-codes them on the device (qs_hip_encode_device_batch); encode_scan leaves the segment in device memory.
+
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
@@ -306,3 +311,204 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
         _check_stop(stop, len(images), dev, who, torch)
     px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who)
     return dict(images=px, workspace=workspace)
+
+
+# ---- entropy coding to JPEG bytes (qs_hip_encode_device_batch) ----------------------------------------------------------
+
+def _huff_tables(hip, huffman, n, who):
+    """huffman: None, one dict(dc={index: (bits, huffval)}, ac={...}) for every image, or a list of such dicts / None"""
+    if huffman is None:
+        return None, b""
+    per = huffman if isinstance(huffman, (list, tuple)) else [huffman] * n
+    if len(per) != n:
+        raise ValueError(f"{who}: one huffman entry (or None) per image")
+    tabs = [None if h is None else hip.huff_tables(h.get("dc"), h.get("ac")) for h in per]
+    return tabs, b"|".join(b"" if t is None else bytes(t) for t in tabs)
+
+
+def _encode_jobs(images, result, who, torch):
+    if not isinstance(images, (list, tuple)) or not images:
+        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    if result is not None and len(result["images"]) != len(images):
+        raise ValueError(f"{who}: result holds {len(result['images'])} images, the batch {len(images)}")
+    hip = _hip()
+    dev, jobs = None, []
+    for i, im in enumerate(images):
+        if not isinstance(im, dict) or "coefs" not in im:
+            raise ValueError(f"{who}: image {i} must be a dict with coefs")
+        if im.get("image_size") is None:
+            raise ValueError(f"{who}: image {i} has no image_size: the encoder needs (width, height)")
+        res = None if result is None else result["images"][i]
+        d = _check_tensors(im["coefs"], torch, who=f"{who}: image {i}")
+        if dev is None:
+            dev = d
+        elif d != dev:
+            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
+        quants = im.get("quants") if im.get("quants") is not None else [None] * len(im["coefs"])
+        jobs.append(_decode_job(hip, im["coefs"], quants, im, res, f"{who}: image {i}", torch))
+    stop = None
+    if result is not None:
+        stop = result["stop"]
+        _check_stop(stop, len(images), dev, who, torch)
+    return jobs, dev, stop
+
+
+def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch):
+    hip = _hip()
+    per, total = hip.encode_batch_info(jobs)
+    key = ("encode", tabkey) + tuple(_key(job, 0, 0) for job in jobs)
+    if workspace is None:
+        workspace = Workspace()
+    if workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
+                               f"geometry and tables (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.encode_batch_prepare(jobs, tabs, workspace.buf.data_ptr(), workspace.nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        workspace.key = key
+    return per, workspace
+
+
+def encode_scan_batch(images, *, result=None, huffman=None, outs=None, workspace: Workspace | None = None) -> dict:
+    """The entropy-coded segment of each image's baseline scan, exactly the bytes libjpeg 9 writes between the SOS header
+    and EOI for jpeg_write_coefficients on these arrays, on the current stream and without host synchronisation.
+
+    images[i]: decode_batch's per-image dict (coefs, hsamp, vsamp, colorspace, image_size; quants are not needed).
+    result: what quantsmooth_batch_ returned (the replacement chroma is coded when its stop reads 0, the original
+    arrays when it reads 1, chosen on the device).  huffman: None (the standard tables), or a dict(dc={0: (bits[17],
+    huffval), ...}, ac={...}) for all images, or a list with one such dict or None per image.  outs: preallocated
+    contiguous uint8 buffers (their size is the capacity); by default 32 bytes per block.  workspace: as decode_batch.
+    Returns dict(segments=[uint8 tensors], len=int64 tensor, status=int32 tensor, workspace): segment i is
+    segments[i][:len[i]] when status[i] is 0; status 2: the buffer holds less than len[i] bytes (retry with that
+    size); 1: a coefficient out of libjpeg's range; 3: a symbol without a code in `huffman` (len is 0 for both)."""
+    return _encode_scan_batch(images, result, huffman, outs, workspace, "encode_scan_batch")
+
+
+def _encode_scan_batch(images, result, huffman, outs, workspace, who):
+    import torch
+    jobs, dev, stop = _encode_jobs(images, result, who, torch)
+    hip = _hip()
+    tabs, tabkey = _huff_tables(hip, huffman, len(jobs), who)
+    per, workspace = _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch)
+    if outs is None:
+        outs = [None] * len(jobs)
+    if len(outs) != len(jobs):
+        raise ValueError(f"{who}: one output (or None) per image")
+    bufs = []
+    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
+        if o is None:
+            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
+            o = torch.empty(min(inf["max_segment_bytes"], 4096 + 32 * blocks), dtype=torch.uint8, device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
+                or not o.is_contiguous() or o.numel() < 1:
+            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
+        bufs.append(o)
+    length = torch.empty(len(jobs), dtype=torch.int64, device=dev)
+    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    hip.encode_batch(jobs, None if stop is None else stop.data_ptr(), [o.data_ptr() for o in bufs],
+                     [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(), workspace.buf.data_ptr(),
+                     workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    return dict(segments=bufs, len=length, status=status, workspace=workspace)
+
+
+def encode_scan(coefs, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, huffman=None, out=None,
+                workspace: Workspace | None = None) -> dict:
+    """encode_scan_batch on one image -> dict(segment, len, status, workspace); len and status are device tensors of
+    one element"""
+    r = _encode_scan_batch([dict(coefs=coefs, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace, image_size=image_size)],
+                           None if result is None else dict(stop=result["stop"], images=[result]), huffman,
+                           None if out is None else [out], workspace, "encode_scan")
+    return dict(segment=r["segments"][0], len=r["len"], status=r["status"], workspace=r["workspace"])
+
+
+def encode_histogram_batch(images, *, result=None, workspace: Workspace | None = None) -> dict:
+    """The symbol counts of each image's scan (qs_hip_encode_device_batch_histogram) -> dict(counts: int32 tensor
+    (len(images), 4, 257) in the order DC 0, DC 1, AC 0, AC 1 -- entry 256 is libjpeg's reserved symbol and reads 1 --,
+    status: int32 tensor, 1 where a coefficient is out of range; workspace).  No host synchronisation."""
+    import torch
+    who = "encode_histogram_batch"
+    jobs, dev, stop = _encode_jobs(images, result, who, torch)
+    _per, workspace = _encode_workspace(jobs, dev, None, b"", workspace, who, torch)
+    counts = torch.empty((len(jobs), 4, 257), dtype=torch.int32, device=dev)
+    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    _hip().encode_batch_histogram(jobs, None if stop is None else stop.data_ptr(), counts.data_ptr(), status.data_ptr(),
+                                  workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    return dict(counts=counts, status=status, workspace=workspace)
+
+
+_STATUS_TEXT = {1: "DCT coefficient out of range", 3: "Missing Huffman code table entry"}     # libjpeg's wording
+
+
+def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
+    """Complete baseline JPEG files (bytes) of the images, byte for byte what libjpeg 9 writes for jpeg_write_coefficients
+    on a fresh compress object with these arrays, tables and sampling factors (jpeg_file.compose has the marker rules).
+
+    images[i]: coefs, quants, hsamp, vsamp, colorspace, image_size; result: what quantsmooth_batch_ returned for them
+    (its output tables, replacement chroma and stop decide what is written).  optimize: libjpeg's optimize_coding -- the
+    histogram on the device, qs_hip_huff_optimal on the host.  huffman: caller tables instead (see encode_scan_batch).
+    Reads len / status, which synchronises; a buffer that proved too small is retried once with the exact size.  Raises
+    ValueError with libjpeg's message where libjpeg would stop."""
+    import torch
+    from . import jpeg_file
+    who = "encode_batch"
+    hip = _hip()
+    n = len(images)
+    stops = [0] * n if result is None else [int(v) for v in result["stop"].cpu().tolist()]
+    # what each file's header describes: the smoothing's output tables and, for a standing UPSAMPLE_UV, 1x1 chroma
+    desc = []
+    for i, im in enumerate(images):
+        res = None if result is None else result["images"][i]
+        ncomp = len(im["coefs"])
+        hs = list(im.get("hsamp") or [1] * ncomp)
+        vs = list(im.get("vsamp") or [1] * ncomp)
+        if res is not None and res.get("coef_up") is not None and stops[i] == 0:
+            hs, vs = [int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)
+        quants = res["quants"] if res is not None else im.get("quants")
+        if quants is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
+        desc.append(dict(quants=quants, hsamp=hs, vsamp=vs, colorspace=cs, image_size=tuple(im["image_size"]),
+                         tbl=jpeg_file.table_assignment(cs, ncomp)))
+    std = dict(dc={t: hip.huff_standard(0, t) for t in (0, 1)}, ac={t: hip.huff_standard(1, t) for t in (0, 1)})
+    if optimize:
+        if huffman is not None:
+            raise ValueError(f"{who}: optimize and huffman exclude each other")
+        h = encode_histogram_batch(images, result=result)
+        bad = [i for i, s in enumerate(h["status"].cpu().tolist()) if s]
+        if bad:
+            raise ValueError(f"{who}: image {bad[0]}: {_STATUS_TEXT[1]}")
+        counts = h["counts"].cpu().numpy()
+        huffman = []
+        for i, d in enumerate(desc):
+            used = sorted(set(d["tbl"]))
+            huffman.append(dict(dc={t: hip.huff_optimal(counts[i, t]) for t in used},
+                                ac={t: hip.huff_optimal(counts[i, 2 + t]) for t in used}))
+    per = huffman if isinstance(huffman, (list, tuple)) else [huffman] * n
+    r = _encode_scan_batch(images, result, huffman, None, None, who)
+    lens, status = r["len"].cpu().tolist(), r["status"].cpu().tolist()
+    if any(s == 2 for s in status):
+        outs = [torch.empty(max(1, int(l)), dtype=torch.uint8, device=o.device) if s == 2 else o
+                for o, l, s in zip(r["segments"], lens, status)]
+        r = _encode_scan_batch(images, result, huffman, outs, r["workspace"], who)
+        lens, status = r["len"].cpu().tolist(), r["status"].cpu().tolist()
+    files = []
+    for i, (d, seg, l, s) in enumerate(zip(desc, r["segments"], lens, status)):
+        if s:
+            raise ValueError(f"{who}: image {i}: {_STATUS_TEXT.get(s, f'status {s}')}")
+        h = per[i] or {}
+        dc = {t: (h.get("dc") or {}).get(t, std["dc"][t]) for t in (0, 1)}
+        ac = {t: (h.get("ac") or {}).get(t, std["ac"][t]) for t in (0, 1)}
+        files.append(jpeg_file.compose(seg[:int(l)].cpu().numpy().tobytes(), d["quants"], d["hsamp"], d["vsamp"],
+                                       d["colorspace"], d["image_size"], dc, ac))
+    return files
+
+
+def encode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, optimize=False,
+           huffman=None) -> bytes:
+    """encode_batch on one image -> the JPEG file as bytes"""
+    return encode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
+                              image_size=image_size)],
+                        result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
+                        huffman=huffman)[0]

@@ -1,0 +1,413 @@
+"""The device entropy coder (torch_qs.encode / encode_scan and their batch forms, qs_hip_encode_device_batch) on the GPU,
+against libjpeg 9 itself writing the same arrays (tests/libjpeg9_encode.c)."""
+import hashlib
+
+import numpy as np
+import pytest
+
+import jpegqs_pkg
+from decode_oracle import GOLD, LibJpeg9, synth_image
+from encode_oracle import (GOLDEN, LAYOUTS, SIZES, LibJpeg9Enc, LibjpegError, block_bit_counts, encode_scan, histogram,
+                           parse_jpeg, scan_bit_count, synth_scan_image)
+
+pkg = jpegqs_pkg.load()
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+jpeg_file = pkg.jpeg_file
+MARGIN = 4096
+
+
+@pytest.fixture(scope="module")
+def enc(tmp_path_factory):
+    return LibJpeg9Enc(tmp_path_factory.mktemp("lj9enc"))
+
+
+@pytest.fixture(scope="module")
+def lj9(tmp_path_factory):
+    return LibJpeg9(tmp_path_factory.mktemp("lj9"))
+
+
+@pytest.fixture(scope="module")
+def tq():
+    if not torch.cuda.is_available():
+        pytest.fail("no HIP device visible to torch")
+    return pkg.torch_qs
+
+
+@pytest.fixture(scope="module")
+def std():
+    hip = pkg.HipQS()
+    return {t: tuple(hip.huff_standard(0, t)) for t in (0, 1)}, {t: tuple(hip.huff_standard(1, t)) for t in (0, 1)}
+
+
+class Guarded:
+    """a device buffer of n bytes between two sentinel margins"""
+
+    def __init__(self, n, dtype=torch.uint8):
+        self.item = torch.empty(0, dtype=dtype).element_size()
+        self.raw = torch.full((2 * MARGIN + n * self.item,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.view = self.raw[MARGIN:MARGIN + n * self.item].view(dtype)
+
+    def check(self, untouched_from=None):
+        host = self.raw.cpu().numpy()
+        assert (host[:MARGIN] == 0xA5).all() and (host[len(host) - MARGIN:] == 0xA5).all(), "a sentinel margin changed"
+        if untouched_from is not None:
+            assert (host[MARGIN + untouched_from:] == 0xA5).all(), "bytes at or beyond the capacity changed"
+
+
+def _dev(im):
+    """the arrays on the device, each between margins"""
+    out = []
+    for c in im["coefs"]:
+        g = Guarded(c.size, torch.int16)
+        g.view.copy_(torch.from_numpy(np.ascontiguousarray(c).reshape(-1)))
+        out.append((g, g.view.view(c.shape)))
+    return out
+
+
+def _kw(im):
+    return dict(hsamp=im["hsamp"], vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"])
+
+
+def _batch(ims):
+    devs = [_dev(im) for im in ims]
+    return devs, [dict(coefs=[t for _g, t in d], quants=im["quants"], **_kw(im)) for d, im in zip(devs, ims)]
+
+
+def _check_inputs(devs, ims):
+    for d, im in zip(devs, ims):
+        for (g, t), c in zip(d, im["coefs"]):
+            g.check()
+            assert np.array_equal(t.cpu().numpy(), c), "the encoder changed an input array"
+
+
+def _scan(tq, ims, caps=None, **kw):
+    """encode_scan_batch with every buffer between margins -> (segments as bytes or None, len, status, guards)"""
+    devs, batch = _batch(ims)
+    hip = pkg.HipQS()
+    jobs = [hip.device_job([0] * len(im["coefs"]), [c.shape[:2] for c in im["coefs"]], [None] * len(im["coefs"]), **_kw(im))
+            for im in ims]
+    per, _total = hip.encode_batch_info(jobs)
+    if caps is None:
+        caps = [min(p["max_segment_bytes"], 4096 + 64 * sum(c.shape[0] * c.shape[1] for c in im["coefs"]))
+                for p, im in zip(per, ims)]
+    outs = [Guarded(c) for c in caps]
+    r = tq.encode_scan_batch(batch, outs=[o.view for o in outs], **kw)
+    torch.cuda.synchronize()
+    lens, status = r["len"].cpu().tolist(), r["status"].cpu().tolist()
+    for o, c in zip(outs, caps):
+        o.check()
+    _check_inputs(devs, ims)
+    segs = [o.view[:l].cpu().numpy().tobytes() if s == 0 else None for o, l, s in zip(outs, lens, status)]
+    return segs, lens, status, outs
+
+
+def _tiny_images():
+    rng = np.random.default_rng(77)
+    one_block = synth_scan_image(rng, (5, 3), [1], [1], 1)
+    one_mcu = [synth_scan_image(rng, (16, 16), [2, 1, 1], [2, 1, 1], 3), synth_scan_image(rng, (9, 2), [2, 1, 1], [2, 1, 1], 3),
+               synth_scan_image(rng, (32, 8), [4, 1, 1], [1, 1, 1], 3), synth_scan_image(rng, (3, 3), [1, 1, 1, 1], [1, 1, 1, 1], 4)]
+    return [("one block", one_block)] + [(f"one MCU {k}", im) for k, im in enumerate(one_mcu)]
+
+
+@pytest.fixture(scope="module")
+def corpus(lj9):
+    ims = [(n, lj9.read(GOLD / f"{n}.jpg")) for n in GOLDEN]
+    for li, (hs, vs, cs) in enumerate(LAYOUTS):
+        for size in SIZES:
+            ims.append((f"layout {li} at {size}", synth_scan_image(np.random.default_rng(li * 1000 + size[0]), size, hs, vs, cs)))
+    return ims + _tiny_images()
+
+
+def test_whole_files_equal_libjpeg_in_one_mixed_batch(tq, enc, corpus):
+    """golden images, every layout x odd sizes, one-block and one-MCU images: more jobs than one launch chunk"""
+    assert len(corpus) > 32
+    _devs, batch = _batch([im for _n, im in corpus])
+    files = tq.encode_batch(batch)
+    for (name, im), f in zip(corpus, files):
+        assert f == enc.write(im), name
+
+
+def test_whole_files_equal_libjpeg_with_optimize(tq, enc, corpus):
+    _devs, batch = _batch([im for _n, im in corpus])
+    files = tq.encode_batch(batch, optimize=True)
+    for (name, im), f in zip(corpus, files):
+        assert f == enc.write(im, optimize=True), name
+
+
+def test_whole_files_equal_libjpeg_with_caller_tables(tq, enc, corpus):
+    """the tables of libjpeg's optimized file handed in as caller tables"""
+    want = [enc.write(im, optimize=True) for _n, im in corpus]
+    huff = [dict(dc=parse_jpeg(w)["dc"], ac=parse_jpeg(w)["ac"]) for w in want]
+    _devs, batch = _batch([im for _n, im in corpus])
+    files = tq.encode_batch(batch, huffman=huff)
+    for (name, _im), f, w in zip(corpus, files, want):
+        assert f == w, name
+
+
+def test_segments_between_sentinels(tq, enc, corpus):
+    ims = [im for _n, im in corpus]
+    segs, lens, status, _ = _scan(tq, ims)
+    assert status == [0] * len(ims)
+    for (name, im), s, l in zip(corpus, segs, lens):
+        assert s == parse_jpeg(enc.write(im))["segment"] and l == len(s), name
+
+
+def test_libjpeg_reads_the_arrays_back(tq, lj9, corpus, tmp_path):
+    _devs, batch = _batch([im for _n, im in corpus])
+    for k, ((name, im), f) in enumerate(zip(corpus, tq.encode_batch(batch))):
+        p = tmp_path / f"{k}.jpg"
+        p.write_bytes(f)
+        back = lj9.read(p)
+        assert back["image_size"] == tuple(im["image_size"]) and back["hsamp"] == list(im["hsamp"]), name
+        for a, b in zip(back["coefs"], im["coefs"]):
+            hb, wb = a.shape[:2]
+            assert np.array_equal(a[:b.shape[0], :b.shape[1]], b[:hb, :wb]), name
+
+
+def _ones_image(rng, wb, hb, dense=0.9):
+    """blocks full of 1023 (sixteen-bit code of one-bits, ten one-bits of value) among sparser ones: runs of 0xFF"""
+    c = np.zeros((hb, wb, 64), np.int16)
+    full = rng.random((hb, wb)) < dense
+    c[full, 1:] = 1023
+    part = ~full
+    c[part, 1:] = rng.integers(0, 2, (int(part.sum()), 63)) * 1023
+    c[..., 0] = rng.integers(-3, 4, (hb, wb))
+    return dict(coefs=[c], quants=[np.ones(64, np.uint16)], hsamp=[1], vsamp=[1], colorspace=1, image_size=(8 * wb, 8 * hb))
+
+
+def test_stuffing_stress(tq, enc, std):
+    rng = np.random.default_rng(255)
+    dc, ac = std
+    # a padded final byte that reads 0xFF: a partial last byte whose bits are all ones
+    final = None
+    for v in range(1, 1024):
+        for pos in (1, 2, 3, 5):
+            c = np.zeros((1, 1, 64), np.int16)
+            c[0, 0, pos], c[0, 0, 63] = v, 1023                     # no EOB: the scan ends in the ones of 1023
+            im = dict(coefs=[c], quants=[np.ones(64, np.uint16)], hsamp=[1], vsamp=[1], colorspace=1, image_size=(8, 8))
+            if scan_bit_count(im, (0,), dc, ac) % 8 and encode_scan(im, (0,), dc, ac).endswith(b"\xff\x00"):
+                final = im
+                break
+        if final:
+            break
+    assert final is not None
+    # 512 x 512 blocks of ones: 0xFF at the edges of the 4 KiB stuffing chunks and of the 256-block workgroups
+    ims = [final, _ones_image(rng, 64, 64), _ones_image(rng, 37, 11, dense=0.5), _ones_image(rng, 256, 40, dense=1.0)]
+    segs, lens, status, _ = _scan(tq, ims, caps=[64, 64 * 64 * 420, 37 * 11 * 420, 256 * 40 * 420])
+    assert status == [0, 0, 0, 0]
+    for k, (im, s) in enumerate(zip(ims, segs)):
+        want = parse_jpeg(enc.write(im))["segment"]
+        assert s == want, f"image {k}"
+        assert want.count(b"\xff\x00") > (0 if k == 0 else 1000)
+    assert segs[0].endswith(b"\xff\x00")
+    raw = segs[3].replace(b"\xff\x00", b"\xff")
+    assert any(raw[i] == 0xFF for i in range(4095, len(raw), 4096)) and any(raw[i] == 0xFF for i in range(4096, len(raw), 4096))
+    # ... and in the byte where one workgroup's bits end and the next one's begin (256 blocks each), mid-byte
+    bits = np.cumsum(block_bit_counts(ims[3], (0,), dc, ac))
+    edges = [int(bits[k - 1]) for k in range(256, len(bits), 256)]
+    assert any(e % 8 and raw[e // 8] == 0xFF for e in edges) and any(e % 32 for e in edges)
+
+
+RANGE = [(0, 0), (1024, 0), (1023, 0), (0, 2048), (0, 2047), (-1024, 0), (-1023, 0), (0, -2048), (0, -2047)]
+
+
+def test_range_cases_inside_a_batch(tq, enc):
+    ims = []
+    for ac, dcdiff in RANGE:
+        im = synth_scan_image(np.random.default_rng(5), (40, 24), [1], [1], 1)
+        c = im["coefs"][0]
+        c[1, 2, 9] = ac
+        lo = -(abs(dcdiff) // 2) if dcdiff >= 0 else abs(dcdiff) // 2
+        c[2, 1, 0], c[2, 2, 0], c[2, 3, 0] = lo, lo + dcdiff, lo + dcdiff
+        ims.append(im)
+    want = []
+    for im in ims:
+        try:
+            want.append(parse_jpeg(enc.write(im))["segment"])
+        except LibjpegError:
+            want.append(None)
+    assert [w is None for w in want] == [abs(a) > 1023 or abs(d) > 2047 for a, d in RANGE]
+    segs, lens, status, _ = _scan(tq, ims)
+    assert status == [1 if w is None else 0 for w in want]
+    for k, (s, w, l) in enumerate(zip(segs, want, lens)):
+        assert s == w, f"job {k}"
+        assert l == (0 if w is None else len(w))
+    _devs, batch = _batch(ims)
+    with pytest.raises(ValueError, match="DCT coefficient out of range"):
+        tq.encode_batch(batch)
+
+
+def test_a_caller_table_without_a_needed_symbol(tq, enc):
+    a = synth_scan_image(np.random.default_rng(1), (24, 24), [1], [1], 1, amp=3)
+    b = synth_scan_image(np.random.default_rng(2), (24, 24), [1], [1], 1, amp=900)
+    f = parse_jpeg(enc.write(a, optimize=True))
+    assert set(np.flatnonzero(histogram(b, (0,))[2][:256])) - set(f["ac"][0][1])
+    segs, lens, status, _ = _scan(tq, [a, b, a], huffman=dict(dc=f["dc"], ac=f["ac"]))
+    assert status == [0, 3, 0] and lens[1] == 0
+    assert segs[0] == f["segment"] and segs[2] == f["segment"]
+
+
+def test_capacity(tq, enc):
+    ims = [synth_scan_image(np.random.default_rng(k), (141, 93), [2, 1, 1], [2, 1, 1], 3) for k in range(3)]
+    want = [parse_jpeg(enc.write(im))["segment"] for im in ims]
+    n = [len(w) for w in want]
+    caps = [n[0], n[1] - 1, 100]
+    segs, lens, status, outs = _scan(tq, ims, caps=caps)
+    assert lens == n and status == [0, 2, 2]
+    assert segs[0] == want[0]
+    for o, c, w in zip(outs, caps, want):
+        assert o.view.cpu().numpy().tobytes() == w[:c]              # the part that fits, and nothing beyond it
+    big = [Guarded(n[k] + 1000) for k in range(3)]
+    devs, batch = _batch(ims)
+    r = tq.encode_scan_batch(batch, outs=[g.view[:c] for g, c in zip(big, caps)])
+    torch.cuda.synchronize()
+    for g, c in zip(big, caps):
+        g.check(untouched_from=c)
+
+
+def _stop_images(lj9):
+    """UPSAMPLE_UV inputs: 4:2:0 and 4:2:2 goldens as they are (stop 0) and with a planted range-check trip in the last
+    component (stop 1), a grayscale and a 4:4:4 job between them"""
+    ims = [lj9.read(GOLD / f"{s}.jpg") for s in ("gray64", "rgb141x93_420", "rgb128x96_420", "rgb141x93_444",
+                                                 "rgb120x88_422_rst", "rgb141x93_420")]
+    for k in (2, 4):
+        im = ims[k]
+        im["quants"][2] = im["quants"][2].copy()
+        im["quants"][2][0] = max(int(im["quants"][2][0]), 3)
+        im["coefs"][2] = im["coefs"][2].copy()
+        im["coefs"][2][0, 0, 0] = 1000
+    return ims
+
+
+def _left_by_the_smoothing(im, coefs, res, stop):
+    """the image dict of what the smoothing left: the replacement chroma at 1x1 when it stood, else the original"""
+    host = [c.cpu().numpy() for c in coefs]
+    if res["coef_up"] is not None and stop == 0:
+        n = len(host)
+        return dict(coefs=[host[0]] + [u.cpu().numpy() for u in res["coef_up"]], quants=res["quants"], hsamp=[1] * n,
+                    vsamp=[1] * n, colorspace=im["colorspace"], image_size=im["image_size"])
+    return dict(coefs=host, quants=res["quants"], hsamp=im["hsamp"], vsamp=im["vsamp"], colorspace=im["colorspace"],
+                image_size=im["image_size"])
+
+
+@pytest.mark.parametrize("quality", [4, 6])
+def test_after_smoothing_both_stop_outcomes(tq, enc, lj9, quality):
+    ims = _stop_images(lj9)
+    devs, batch = _batch(ims)
+    res = tq.quantsmooth_batch_(batch, pkg.flags_for_quality(quality), 2)
+    files = tq.encode_batch(batch, result=res)
+    stops = res["stop"].cpu().tolist()
+    if quality == 6:
+        assert stops == [0, 0, 1, 0, 1, 0]
+        assert res["images"][1]["coef_up"] is not None and res["images"][2]["coef_up"] is not None
+    for k, (im, b, r, f) in enumerate(zip(ims, batch, res["images"], files)):
+        assert f == enc.write(_left_by_the_smoothing(im, b["coefs"], r, stops[k])), f"job {k} (stop {stops[k]})"
+    opt = tq.encode_batch(batch, result=res, optimize=True)
+    for k, (im, b, r, f) in enumerate(zip(ims, batch, res["images"], opt)):
+        assert f == enc.write(_left_by_the_smoothing(im, b["coefs"], r, stops[k]), optimize=True), f"job {k} optimized"
+
+
+def test_single_image_calls(tq, enc, lj9):
+    im = lj9.read(GOLD / "rgb141x93_420.jpg")
+    coefs = [torch.from_numpy(c).cuda() for c in im["coefs"]]
+    res = tq.quantsmooth_(coefs, im["quants"], pkg.flags_for_quality(6), 2, **_kw(im))
+    f = tq.encode(coefs, **_kw(im), result=res)
+    assert f == enc.write(_left_by_the_smoothing(im, coefs, res, int(res["stop"].item())))
+    r = tq.encode_scan(coefs, **_kw(im), result=res)
+    assert int(r["status"].item()) == 0
+    assert r["segment"][:int(r["len"].item())].cpu().numpy().tobytes() == parse_jpeg(f)["segment"]
+
+
+def test_smooth_and_encode_in_one_captured_graph(tq, lj9):
+    ims = _stop_images(lj9)[1:4]
+    for im in ims:
+        im["coefs"][2] = im["coefs"][2].copy()
+    ims[1]["coefs"][2][0, 0, 0] = int(lj9.read(GOLD / "rgb128x96_420.jpg")["coefs"][2][0, 0, 0])      # no trip to begin with
+    flags = pkg.flags_for_quality(6)
+    src = [[torch.from_numpy(np.ascontiguousarray(c)).cuda() for c in im["coefs"]] for im in ims]
+    work = [[t.clone() for t in s] for s in src]
+    batch = [dict(coefs=w, quants=im["quants"], **_kw(im)) for w, im in zip(work, ims)]
+    outs = [Guarded(200000) for _ in ims]
+    ws1, ws2 = None, tq.Workspace()
+
+    def step():
+        for w, s in zip(work, src):
+            for a, b in zip(w, s):
+                a.copy_(b)
+        res = tq.quantsmooth_batch_(batch, flags, 2, workspace=ws1)
+        return res, tq.encode_scan_batch(batch, result=res, outs=[o.view for o in outs], workspace=ws2)
+
+    res, out = step()                                          # eager: prepares both workspaces
+    ws1 = res["workspace"]
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        gres, gout = step()
+    rng = np.random.default_rng(3)
+    seen = set()
+    for rep in range(3):
+        for s, im in zip(src, ims):                            # new inputs: perturbed luma, a trip in one of them
+            base = torch.from_numpy(im["coefs"][0]).cuda()
+            noise = torch.from_numpy(rng.integers(-1, 2, im["coefs"][0].shape).astype(np.int16)).cuda()
+            s[0].copy_(base + noise * (base != 0).to(torch.int16))
+        src[rep % 3][2].view(-1)[0] = 1000 if rep == 1 else int(ims[rep % 3]["coefs"][2].reshape(-1)[0])
+        g.replay()
+        torch.cuda.synchronize()
+        glen, gstatus, gstop = gout["len"].cpu().tolist(), gout["status"].cpu().tolist(), gres["stop"].cpu().tolist()
+        got = [o.view[:l].cpu().numpy().tobytes() for o, l in zip(outs, glen)]
+        eres, eout = step()                                    # eager on the same inputs
+        torch.cuda.synchronize()
+        assert eres["stop"].cpu().tolist() == gstop and gstatus == [0, 0, 0] == eout["status"].cpu().tolist()
+        assert eout["len"].cpu().tolist() == glen
+        for k, (a, o, l) in enumerate(zip(got, outs, glen)):
+            assert a == o.view[:l].cpu().numpy().tobytes(), f"replay {rep}, image {k}"
+            o.check()
+        seen.add(tuple(gstop))
+    assert len(seen) > 1                                       # the stop outcome changed across replays
+
+
+@pytest.mark.parametrize("hs,vs,cs", [([1], [1], 1), ([2, 1, 1], [2, 1, 1], 3)])
+def test_large_image_against_a_hash_of_libjpegs_file(tq, enc, hs, vs, cs):
+    im = synth_image(np.random.default_rng(8192), (8192, 8192), hs, vs, cs, amp=30)
+    want = enc.write(im)
+    got = tq.encode([torch.from_numpy(c).cuda() for c in im["coefs"]], im["quants"], **_kw(im))
+    assert len(got) == len(want)
+    assert hashlib.sha256(got).hexdigest() == hashlib.sha256(want).hexdigest()
+
+
+def test_histogram_equals_the_restatements_counts(tq, corpus):
+    ims = [im for _n, im in corpus]
+    devs, batch = _batch(ims)
+    r = tq.encode_histogram_batch(batch)
+    torch.cuda.synchronize()
+    got = r["counts"].cpu().numpy()
+    assert r["status"].cpu().tolist() == [0] * len(ims)
+    for (name, im), h in zip(corpus, got):
+        want = histogram(im, jpeg_file.table_assignment(im["colorspace"], len(im["coefs"])))
+        assert np.array_equal(h[:, :256], want[:, :256]), name
+        assert (h[:, 256] == 1).all()                          # libjpeg's reserved symbol
+    _check_inputs(devs, ims)
+
+
+def test_device_route_beats_the_coefficient_copy():
+    """tools/bench_device_batch.py --encode exits non-zero unless, for 8192^2 gray, 8192^2 4:2:0 and 32 x 1080p, the
+    encode plus the copy of the segment to the host is faster than the copy of the coefficient arrays alone, and the
+    segments are libjpeg's.
+
+    This is the one test here that starts a second process on the device and asserts on time.  Both sides of the
+    comparison are medians of five windows taken in that one process, so a busy host slows them together; the measured
+    margin is 2.8x to 3.9x.  The 900 s limit is a backstop, not a wait: the tool takes
+    under a minute, most of it libjpeg writing the 8192^2 files on one core for the identity check."""
+    import json
+    import subprocess
+    import sys
+    root = GOLD.parent.parent.parent
+    r = subprocess.run([sys.executable, str(root / "tools" / "bench_device_batch.py"), "--encode"], capture_output=True,
+                       text=True, timeout=900)
+    print(r.stdout[-3000:], r.stderr[-2000:])
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = json.loads(r.stdout.strip().splitlines()[-1])["results"]
+    assert len(rows) == 3
+    for row in rows:
+        assert row["identical"] and row["device_encode_plus_copy_ms"] < row["host_coef_copy_ms"], row

@@ -16,7 +16,14 @@ written; and, for 8192^2 4:2:0, the host alternative it replaces: the copy of th
 libjpeg 9's single-thread decode (tests/libjpeg9_decode.c, whose time includes writing the coefficients to an in-memory
 JPEG first).
 
-    python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5] [--decode]"""
+--encode times the device entropy coder (torch_qs.encode_scan_batch with the standard tables) on the same three cases:
+the encode plus the device-to-host copy of `len` bytes, next to the host alternative it replaces -- the copy of the
+coefficient arrays to the host (a lower bound of that route by itself) plus libjpeg 9's jpeg_write_coefficients on one
+core (tests/libjpeg9_encode.c on a staged input file: its time includes reading the arrays and writing the file).
+Medians of --repeats windows; exits non-zero unless the device route gives libjpeg's bytes and beats the copy alone.
+
+    python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
+                                       [--decode | --encode]"""
 import argparse
 import json
 import sys
@@ -37,9 +44,12 @@ def main():
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--decode", action="store_true", help="time the device decode to pixels instead")
+    ap.add_argument("--encode", action="store_true", help="time the device entropy coder instead")
     a = ap.parse_args()
     if a.decode:
         return bench_decode(a)
+    if a.encode:
+        return bench_encode(a)
 
     import numpy as np
     import torch
@@ -191,6 +201,92 @@ def bench_decode(a):
                                            identical=bool(np.array_equal(px, outs[0].cpu().numpy())))
         out["results"].append(row)
     print(json.dumps(out), flush=True)
+
+
+def bench_encode(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import synth_image
+    from encode_oracle import LibJpeg9Enc, parse_jpeg
+    torch_qs = jpegqs_pkg.load().torch_qs
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1, amp=30)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
+             (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
+    out = dict(tool="bench_device_batch", leg="encode", device=torch.cuda.get_device_name(dev), results=[])
+    for name, ims in cases:
+        images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], hsamp=im["hsamp"], vsamp=im["vsamp"],
+                       colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
+        ws = torch_qs.Workspace()
+        r = torch_qs.encode_scan_batch(images, workspace=ws)
+        outs, lens = r["segments"], [int(v) for v in r["len"].cpu().tolist()]
+        assert r["status"].cpu().tolist() == [0] * len(images), "the default capacity did not hold the segment"
+        pinned = [torch.empty(l, dtype=torch.uint8).pin_memory() for l in lens]
+        coef_bytes = sum(sum(c.numel() * 2 for c in im["coefs"]) for im in images)
+
+        def device_route():
+            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws)
+            for p, o, l in zip(pinned, outs, lens):
+                p.copy_(o[:l], non_blocking=True)
+            torch.cuda.synchronize()
+
+        def kernels_only():
+            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws)
+            torch.cuda.synchronize()
+
+        host_pinned = [[torch.empty(c.shape, dtype=torch.int16).pin_memory() for c in im["coefs"]] for im in images]
+
+        def coef_copy():
+            for hp, im in zip(host_pinned, images):
+                for h, c in zip(hp, im["coefs"]):
+                    h.copy_(c, non_blocking=True)
+            torch.cuda.synchronize()
+
+        def med(fn, calls):
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                ms.append((time.perf_counter() - t0) * 1e3 / calls)
+            return round(float(np.median(ms)), 3), [round(m, 3) for m in ms]
+
+        dev_ms, dev_all = med(device_route, 10)
+        k_ms, _ = med(kernels_only, 10)
+        copy_ms, copy_all = med(coef_copy, 5)
+        row = dict(case=name, images=len(images), coef_mbytes=round(coef_bytes / 1e6, 1), segment_bytes=sum(lens),
+                   device_encode_plus_copy_ms=dev_ms, device_windows=dev_all, device_encode_ms=k_ms,
+                   host_coef_copy_ms=copy_ms, host_copy_windows=copy_all, device_faster_than_copy=bool(dev_ms < copy_ms))
+        with tempfile.TemporaryDirectory() as td:                   # the helper on a staged input: libjpeg reads the
+            enc = LibJpeg9Enc(Path(td))                             # arrays, writes the file; one warm-up, then windows
+            unit = [np.ones(64, np.uint16)] * len(ims[0]["coefs"])
+            staged = enc.stage(dict(ims[0], quants=unit))
+            want = enc.run(staged)
+            ts = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                enc.run(staged)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row["host_libjpeg9_write_ms_per_image"] = round(float(np.median(ts)), 1)
+            row["host_libjpeg9_windows"] = [round(t, 1) for t in ts]
+            seg = parse_jpeg(want)["segment"]
+            row["identical"] = all(seg == p.numpy().tobytes() for p, im in zip(pinned, ims) if im is ims[0])
+        row["host_route_ms"] = round(copy_ms + row["host_libjpeg9_write_ms_per_image"] * len(images), 1)
+        out["results"].append(row)
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not (r["identical"] and r["device_faster_than_copy"])]
+    if bad:                                                         # the bound of DESIGN.md section 13
+        raise SystemExit(f"bench_device_batch --encode: {bad}: the device route must give libjpeg's bytes and be faster "
+                         f"than the copy of the coefficient arrays alone")
 
 
 if __name__ == "__main__":
