@@ -108,3 +108,23 @@ def wrap_expected(ci, c, q):
     """what the reference leaves for one WRAP_PLANTS entry after stopping at component 0"""
     v = int(np.int16(np.int32(c) * np.int32(q)))             # JCOEF arithmetic: the product wraps to int16
     return max(-1023, min(1023, v)) if ci == 0 else v
+
+
+MARGIN = 4096
+
+
+class Guarded:
+    """a device buffer of n elements between two sentinel margins of MARGIN bytes (GPU tests: needs torch)"""
+
+    def __init__(self, n, dtype=None):
+        import torch
+        dtype = torch.uint8 if dtype is None else dtype
+        self.item = torch.empty(0, dtype=dtype).element_size()
+        self.raw = torch.full((2 * MARGIN + n * self.item,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.view = self.raw[MARGIN:MARGIN + n * self.item].view(dtype)
+
+    def check(self, untouched_from=None):
+        host = self.raw.cpu().numpy()
+        assert (host[:MARGIN] == 0xA5).all() and (host[len(host) - MARGIN:] == 0xA5).all(), "a sentinel margin changed"
+        if untouched_from is not None:
+            assert (host[MARGIN + untouched_from:] == 0xA5).all(), "bytes at or beyond the capacity changed"

@@ -9,12 +9,12 @@ import jpegqs_pkg
 from decode_oracle import GOLD, LibJpeg9, synth_image
 from encode_oracle import (GOLDEN, LAYOUTS, SIZES, LibJpeg9Enc, LibjpegError, block_bit_counts, encode_scan, histogram,
                            parse_jpeg, scan_bit_count, synth_scan_image)
+from helpers import Guarded
 
 pkg = jpegqs_pkg.load()
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 jpeg_file = pkg.jpeg_file
-MARGIN = 4096
 
 
 @pytest.fixture(scope="module")
@@ -38,21 +38,6 @@ def tq():
 def std():
     hip = pkg.HipQS()
     return {t: tuple(hip.huff_standard(0, t)) for t in (0, 1)}, {t: tuple(hip.huff_standard(1, t)) for t in (0, 1)}
-
-
-class Guarded:
-    """a device buffer of n bytes between two sentinel margins"""
-
-    def __init__(self, n, dtype=torch.uint8):
-        self.item = torch.empty(0, dtype=dtype).element_size()
-        self.raw = torch.full((2 * MARGIN + n * self.item,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.view = self.raw[MARGIN:MARGIN + n * self.item].view(dtype)
-
-    def check(self, untouched_from=None):
-        host = self.raw.cpu().numpy()
-        assert (host[:MARGIN] == 0xA5).all() and (host[len(host) - MARGIN:] == 0xA5).all(), "a sentinel margin changed"
-        if untouched_from is not None:
-            assert (host[MARGIN + untouched_from:] == 0xA5).all(), "bytes at or beyond the capacity changed"
 
 
 def _dev(im):
