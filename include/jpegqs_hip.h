@@ -273,7 +273,8 @@ int qs_hip_decode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t
 
 /* ---- device entropy coder (the coefficient arrays of device-resident jobs -> the bytes of a baseline JPEG scan) ----
  * What libjpeg 9 writes between the SOS header and EOI when jpeg_write_coefficients gets the same arrays (jchuff.c:
- * sequential Huffman, no scan script, no restart interval, 8-bit precision), byte for byte: one interleaved scan over all
+ * sequential Huffman, no scan script, 8-bit precision; restart intervals through the _opts calls below), byte for
+ * byte: one interleaved scan over all
  * components (MCUs in raster order; blocks an edge MCU lacks are coded as jctrans.c's dummy blocks), or one
  * non-interleaved scan for a one-component image; the last byte padded with one-bits, 0x00 after every 0xFF.  Jobs are
  * qs_hip_job records over DEVICE arrays as the decode takes them: each array contiguous and 16-byte aligned
@@ -318,6 +319,32 @@ int qs_hip_encode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t
 		const size_t *out_capacity, uint64_t *d_len, int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
 int qs_hip_encode_device_batch_histogram(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint32_t *d_counts,
 		int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
+/* Restart intervals, as libjpeg 9 writes them for cinfo.restart_interval / cinfo.restart_in_rows (jpegtran -restart
+ * N[B]): restart_interval in MCUs, 0 .. 65535, 0 = none; restart_in_rows > 0 wins and means min(restart_in_rows * MCUs per row,
+ * 65535), worked out for each of a job's geometries (an MCU of a one-component scan is one block).  Before MCU k * Ri
+ * (k >= 1) the pending bits are padded to a byte with one-bits (a padded byte of 0xFF is followed by 0x00 like any
+ * other), FF D0+((k-1) & 7) follows unstuffed, and every component's DC prediction starts again at 0 -- in the segment
+ * and in the histogram alike.  An interval that covers the scan writes no marker: the segment of a job without one.
+ * (The DRI marker of the file is the caller's: libjpeg writes FF DD 00 04 Ri in front of SOS whenever Ri is not 0.)
+ *   info_opts / prepare_opts   info / prepare with opts[i] for job i; opts NULL or opts[i] NULL: no restarts, which is
+ *              what info / prepare do.  max_segment_bytes and *workspace_bytes cover the options (at most 4 bytes per
+ *              interval end; the intervals' offsets live in the workspace), so a workspace sized for other options may
+ *              be too small: QS_HIP_EINVAL, as for any short workspace.  A negative value or restart_interval > 65535:
+ *              QS_HIP_EINVAL.
+ * The run and histogram calls keep their signatures: they work with the intervals the last prepare on d_workspace
+ * wrote there.  The library remembers, per workspace address, what prepare saw (the 4096 workspaces prepared last).
+ * A workspace the run finds no prepare for -- a copy of a prepared one at another address, say -- runs without
+ * restarts, as before; a job of it whose descriptor has a restart interval then ends with d_status 4 and d_len 0
+ * (prepare the workspace at the address it runs at).  A run with another number of jobs than that prepare saw:
+ * QS_HIP_EINVAL.  A launch chunk without a restart job enqueues exactly the kernels it would without options; one
+ * with a restart job enqueues seven as well, in their restart variants. */
+typedef struct {
+	int32_t restart_interval, restart_in_rows;
+} qs_hip_encode_opts;
+int qs_hip_encode_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_encode_opts *const *opts,
+		qs_hip_encode_info *per_job, size_t *workspace_bytes);
+int qs_hip_encode_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_huff_tables *const *tables,
+		const qs_hip_encode_opts *const *opts, void *d_workspace, size_t bytes, void *stream);
 /* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
  * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT. */
 int qs_hip_huff_optimal(const uint32_t freq[257], uint8_t bits[17], uint8_t huffval[256]);

@@ -10,10 +10,13 @@
 #define QS_ENC_MAXBITS (27 + 63 * 26)
 // words the emit kernel stages per workgroup: 256 blocks of QS_ENC_MAXBITS behind up to 31 bits of the word they start in
 #define QS_ENC_LDS_WORDS ((31 + QS_ENC_WG * QS_ENC_MAXBITS + 31) / 32)
+// the restart variant: every lane can own an interval end, whose padding adds up to 7 bits to the workgroup's image
+#define QS_ENC_LDS_WORDS_RST (QS_ENC_LDS_WORDS + (7 * QS_ENC_WG + 31) / 32)
 #define QS_ENC_SCHUNK 4096         // bytes of the unstuffed stream per stuffing step (16 per lane)
 #define QS_ENC_SWG_MAX 1024        // workgroups a job's stuffing kernels get at most (they stride over the chunks)
 
 // status bits collected per job while it runs (QsEncState.flags); the caller sees 1, 3 or 2 in this order of precedence
+// (4, before all of them: descriptors with a restart interval under the kernels without -- QsEncArgs.restart)
 #define QS_ENC_F_BADCOEF 1u
 #define QS_ENC_F_NOCODE 2u
 
@@ -37,6 +40,7 @@ struct QsEncJob {
   int32_t tbl[4];                  // Huffman table (0 / 1) of each component
   int32_t wg0, nwg;                // sizing / emit workgroups of this job in its chunk's launches
   int32_t swg0, nswg;              // the same for the stuffing kernels
+  int32_t ri[2];                   // restart interval of each variant in MCUs; 0: none (also when it covers the scan)
   int32_t pad;
   uint64_t off_bits;               // uint16[nwg * 256]: code length of each scan block
   uint64_t off_wgsum;              // uint32[nwg]: bits of each workgroup's blocks
@@ -45,12 +49,16 @@ struct QsEncJob {
   uint64_t off_ffcnt;              // uint32[raw_cap / QS_ENC_SCHUNK]: 0xFF bytes per stuffing chunk
   uint64_t off_ffoff;              // uint64[...]: their exclusive scan
   uint64_t off_state;              // QsEncState
+  // restart intervals (used by the restart kernels only; an interval = ri MCUs, the whole scan where ri is 0)
+  uint64_t off_rrel;               // uint32[intervals]: bits of the workgroup's blocks before the interval's first block
+  uint64_t off_rd;                 // uint64[intervals + 1]: padding bits of all intervals before this one
+  uint64_t off_rp;                 // uint64[intervals + 1]: the byte of the unstuffed stream the interval starts at
   uint32_t dc[2][16];              // (size << 16) | code by category; size 0 = the table has no such symbol
   uint32_t ac[2][256];             // the same by run/size symbol
 };
 
 struct QsEncState {
-  uint64_t total_bits;             // of the unstuffed stream
+  uint64_t total_bits;             // of the unstuffed stream (restart kernels: the interval paddings included)
   uint64_t raw_bytes;              // ceil(total_bits / 8)
   uint32_t flags;                  // QS_ENC_F_*
   uint32_t dead;                   // 1: flags were set when the scan ran; the later kernels leave the job alone
@@ -71,6 +79,7 @@ struct QsEncArgs {
   int32_t* d_status;
   uint32_t* d_counts;              // histogram run: uint32[njobs][4][257], else null
   int32_t job0, n;
+  int32_t restart;                 // 1: the restart instantiations run (else a job with an interval ends with status 4)
   int32_t wg0[QS_ENC_CHUNK];       // each job's first workgroup in the block kernels' launch (QsEncJob.wg0) ...
   int32_t swg0[QS_ENC_CHUNK];      // ... and in the stuffing kernels': a workgroup finds its job without touching memory
   QsEncPtrs p[QS_ENC_CHUNK];

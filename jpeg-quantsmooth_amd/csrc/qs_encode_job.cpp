@@ -1,20 +1,26 @@
 // qs_encode_job.cpp -- the device entropy coder of the flat C ABI (include/jpegqs_hip.h):
-// qs_hip_encode_device_batch_info / _prepare / qs_hip_encode_device_batch / _histogram, and the host-only
+// qs_hip_encode_device_batch_info[_opts] / _prepare[_opts] / qs_hip_encode_device_batch / _histogram, and the host-only
 // qs_hip_huff_optimal / qs_hip_huff_standard.  What libjpeg 9 writes between the SOS header and EOI for
-// jpeg_write_coefficients on the arrays of qs_hip_job records (no scan script, no restart interval, 8 bits), computed
-// on the device (qs_kernels_encode.hip).
+// jpeg_write_coefficients on the arrays of qs_hip_job records (no scan script, 8 bits; restart intervals through the
+// _opts calls), computed on the device (qs_kernels_encode.hip).
 //
 // Workspace: the QsEncJob descriptors of the batch, then per job its scratch arrays (block code lengths, workgroup
-// sums and offsets, the unstuffed stream at its worst-case size, the stuffing counts) -- a function of the jobs'
-// geometry alone; the code tables in the descriptors come from prepare's `tables`.
+// sums and offsets, the unstuffed stream at its worst-case size, the stuffing counts, the restart intervals' offsets)
+// -- a function of the jobs' geometry and restart options alone; the code tables in the descriptors come from prepare's
+// `tables`.  The run calls have no options: every prepare notes, under the workspace's address, the batch size, which
+// launch chunks hold a restart job and how large the workspace must be (prepared()); the run looks that up.  A
+// workspace it does not find there runs as one without restart jobs, as every workspace did before there were options;
+// should its descriptors hold an interval after all, the kernels end those jobs with status 4.
 #include "qs_common.h"
 #include "qs_encode.h"
 
 #include <algorithm>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 #include <vector>
 
-void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, hipStream_t s);
+void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, bool restart, hipStream_t s);
 
 namespace {
 
@@ -181,9 +187,49 @@ struct Who {
 
 uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QsEncJob), 256); }
 
+// jcmaster.c (per_scan_setup): restart_in_rows wins and is counted in the geometry's MCU rows, limited to 16 bits.
+// -> the interval the kernels work with: 0 where no marker is written (none asked for, or one interval covers the scan)
+int restart_interval(const qs_hip_encode_opts* o, const QsEncGeom& g) {
+  if (!o) return 0;
+  const long long ri = o->restart_in_rows > 0 ? std::min<long long>((long long)o->restart_in_rows * g.mcus_x, 65535)
+                                              : o->restart_interval;
+  return ri >= g.mcus ? 0 : (int)ri;
+}
+
+// what every prepare leaves for the run calls, by workspace address: the launch chunks that hold a restart job (empty:
+// none), and the workspace size the options need.  At most QS_ENC_PREPARED_MAX entries: the one prepared longest ago
+// goes first, and runs from then on as a workspace without restart jobs (status 4 for a job that has one) until it is
+// prepared again
+#define QS_ENC_PREPARED_MAX 4096
+struct Prepared {
+  int njobs;
+  uint64_t total;
+  uint64_t age;
+  std::vector<uint8_t> chunk_restart;
+};
+std::mutex g_prepared_mutex;
+uint64_t g_prepared_clock = 0;
+std::unordered_map<const void*, Prepared>& prepared() {
+  static std::unordered_map<const void*, Prepared> m;
+  return m;
+}
+void remember(const void* d_workspace, Prepared p) {
+  std::lock_guard<std::mutex> lock(g_prepared_mutex);
+  auto& m = prepared();
+  p.age = ++g_prepared_clock;
+  m[d_workspace] = std::move(p);
+  if (m.size() > QS_ENC_PREPARED_MAX) {
+    auto oldest = m.begin();
+    for (auto it = m.begin(); it != m.end(); ++it)
+      if (it->second.age < oldest->second.age) oldest = it;
+    m.erase(oldest);
+  }
+}
+
 // the descriptors of a batch with their workspace layout; returns the workspace size in *total
-int describe_all(qs_hip_job* const* jobs, int njobs, bool need_arrays, std::vector<QsEncJob>& D, std::vector<QsEncPtrs>* P,
-                 qs_hip_encode_info* info, uint64_t* total, const char* who) {
+int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* const* opts, bool need_arrays,
+                 std::vector<QsEncJob>& D, std::vector<QsEncPtrs>* P, qs_hip_encode_info* info, uint64_t* total,
+                 const char* who) {
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   D.assign((size_t)njobs, QsEncJob());
   if (P) P->assign((size_t)njobs, QsEncPtrs());
@@ -195,13 +241,24 @@ int describe_all(qs_hip_job* const* jobs, int njobs, bool need_arrays, std::vect
     QsEncJob& J = D[i];
     if (i % QS_ENC_CHUNK == 0) wgs = swgs = 0;
     const int nblocks = std::max(J.g[0].nblocks, J.two ? J.g[1].nblocks : 0);
+    const qs_hip_encode_opts* o = opts ? opts[i] : nullptr;
+    if (o && (o->restart_interval < 0 || o->restart_interval > 65535 || o->restart_in_rows < 0))
+      return qs_fail(QS_HIP_EINVAL, "%s: job %d: restart_interval %d (0 .. 65535), restart_in_rows %d (0 or more)", who, i,
+                     o->restart_interval, o->restart_in_rows);
+    uint64_t nint = 1;                                              // restart intervals of the scan, at most
+    for (int v = 0; v < (J.two ? 2 : 1); ++v) {
+      J.ri[v] = restart_interval(o, J.g[v]);
+      if (J.ri[v]) nint = std::max<uint64_t>(nint, (uint64_t)ceil_div(J.g[v].mcus, J.ri[v]));
+    }
     J.nwg = ceil_div(nblocks, QS_ENC_WG);
     J.wg0 = (int)wgs;
     wgs += J.nwg;
     const uint64_t slots = (uint64_t)J.nwg * QS_ENC_WG;
-    J.raw_cap = align_up((slots * QS_ENC_MAXBITS + 7) / 8, 16) + 16;
+    // (the launch grid of the stuffing kernels does not depend on the options: the run calls do not see them)
+    const uint64_t plain_cap = align_up((slots * QS_ENC_MAXBITS + 7) / 8, 16) + 16;
+    J.raw_cap = plain_cap + align_up(nint - 1, 16);                 // less than a byte of padding per interval end
     const uint64_t chunks = (J.raw_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK;
-    J.nswg = (int)std::min<uint64_t>(chunks, QS_ENC_SWG_MAX);
+    J.nswg = (int)std::min<uint64_t>((plain_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK, QS_ENC_SWG_MAX);
     J.swg0 = (int)swgs;
     swgs += J.nswg;
     if (wgs > 0x7fffffffLL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
@@ -213,7 +270,11 @@ int describe_all(qs_hip_job* const* jobs, int njobs, bool need_arrays, std::vect
     J.off_raw = take(J.raw_cap);
     J.off_ffcnt = take(chunks * 4);
     J.off_ffoff = take(chunks * 8);
-    if (info) info[i].max_segment_bytes = 2 * (((uint64_t)nblocks * QS_ENC_MAXBITS + 7) / 8);   // every byte stuffed
+    J.off_rrel = take(nint * 4);
+    J.off_rd = take((nint + 1) * 8);
+    J.off_rp = take((nint + 1) * 8);
+    // every byte stuffed; per interval end a pad byte that may be stuffed, and the two bytes of the marker
+    if (info) info[i].max_segment_bytes = 2 * (((uint64_t)nblocks * QS_ENC_MAXBITS + 7) / 8) + 4 * (nint - 1);
   }
   *total = off;
   return QS_HIP_OK;
@@ -249,13 +310,29 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
   std::vector<QsEncJob> D;
   std::vector<QsEncPtrs> P;
   uint64_t total = 0;
-  if (int r = describe_all(jobs, njobs, true, D, &P, nullptr, &total, who)) return r;
+  if (int r = describe_all(jobs, njobs, nullptr, true, D, &P, nullptr, &total, who)) return r;
   if (!d_counts) {
     if (!d_out || !out_capacity || !d_len || !d_status) return qs_fail(QS_HIP_EINVAL, "%s: null output argument", who);
     for (int i = 0; i < njobs; ++i) {
       if (!d_out[i]) return qs_fail(QS_HIP_EINVAL, "%s: job %d has no output buffer", who, i);
       P[(size_t)i].out = d_out[i];
       P[(size_t)i].cap = out_capacity[i];
+    }
+  }
+  if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+  // the kernels to launch follow what prepare wrote at this address.  An address not known here (a copy of a prepared
+  // workspace, or one of more than QS_ENC_PREPARED_MAX) runs without restarts, as it always did; the kernels give
+  // status 4 to a job whose descriptor has an interval nevertheless, so a lost marker is never silent
+  std::vector<uint8_t> chunk_restart;
+  {
+    std::lock_guard<std::mutex> lock(g_prepared_mutex);
+    auto it = prepared().find(d_workspace);
+    if (it != prepared().end()) {
+      if (it->second.njobs != njobs)
+        return qs_fail(QS_HIP_EINVAL, "%s: the workspace was prepared for %d jobs, the call has %d", who, it->second.njobs,
+                       njobs);
+      total = it->second.total;
+      chunk_restart = it->second.chunk_restart;
     }
   }
   if (int r = check_ws(total, d_workspace, bytes, who)) return r;
@@ -278,35 +355,32 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
       a.swg0[k] = D[(size_t)j0 + k].swg0;
     }
     const QsEncJob& last = D[(size_t)j0 + a.n - 1];
-    qs_launch_encode(a, last.wg0 + last.nwg, last.swg0 + last.nswg, s);
+    const bool restart = !chunk_restart.empty() && chunk_restart[(size_t)(j0 / QS_ENC_CHUNK)];
+    a.restart = restart ? 1 : 0;
+    qs_launch_encode(a, last.wg0 + last.nwg, last.swg0 + last.nswg, restart, s);
   }
   HIP_TRY(hipGetLastError());
   return QS_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" int qs_hip_encode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_encode_info* per_job,
-                                               size_t* bytes) {
+int info_opts(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* const* opts, qs_hip_encode_info* per_job,
+              size_t* bytes, const char* who) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_encode_device_batch_info";
     if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
     std::vector<QsEncJob> D;
     uint64_t total = 0;
-    if (int r = describe_all(jobs, njobs, false, D, nullptr, per_job, &total, who)) return r;
+    if (int r = describe_all(jobs, njobs, opts, false, D, nullptr, per_job, &total, who)) return r;
     *bytes = (size_t)total;
     return QS_HIP_OK;
   });
 }
 
-extern "C" int qs_hip_encode_device_batch_prepare(qs_hip_job* const* jobs, int njobs,
-                                                  const qs_hip_huff_tables* const* tables, void* d_workspace,
-                                                  size_t bytes, void* stream) {
+int prepare_opts(qs_hip_job* const* jobs, int njobs, const qs_hip_huff_tables* const* tables,
+                 const qs_hip_encode_opts* const* opts, void* d_workspace, size_t bytes, void* stream, const char* who) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_encode_device_batch_prepare";
     std::vector<QsEncJob> D;
     uint64_t total = 0;
-    if (int r = describe_all(jobs, njobs, false, D, nullptr, nullptr, &total, who)) return r;
+    if (int r = describe_all(jobs, njobs, opts, false, D, nullptr, nullptr, &total, who)) return r;
     for (int i = 0; i < njobs; ++i) {
       const qs_hip_huff_tables* T = tables ? tables[i] : nullptr;
       for (int t = 0; t < 2; ++t) {
@@ -325,8 +399,38 @@ extern "C" int qs_hip_encode_device_batch_prepare(qs_hip_job* const* jobs, int n
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsEncJob), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
+    Prepared p{njobs, total, 0, std::vector<uint8_t>((size_t)ceil_div(njobs, QS_ENC_CHUNK), 0)};
+    for (int i = 0; i < njobs; ++i)
+      if (D[(size_t)i].ri[0] || D[(size_t)i].ri[1]) p.chunk_restart[(size_t)(i / QS_ENC_CHUNK)] = 1;
+    remember(d_workspace, std::move(p));
     return QS_HIP_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int qs_hip_encode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_encode_info* per_job,
+                                               size_t* bytes) {
+  return info_opts(jobs, njobs, nullptr, per_job, bytes, "qs_hip_encode_device_batch_info");
+}
+
+extern "C" int qs_hip_encode_device_batch_info_opts(qs_hip_job* const* jobs, int njobs,
+                                                    const qs_hip_encode_opts* const* opts, qs_hip_encode_info* per_job,
+                                                    size_t* bytes) {
+  return info_opts(jobs, njobs, opts, per_job, bytes, "qs_hip_encode_device_batch_info_opts");
+}
+
+extern "C" int qs_hip_encode_device_batch_prepare(qs_hip_job* const* jobs, int njobs,
+                                                  const qs_hip_huff_tables* const* tables, void* d_workspace,
+                                                  size_t bytes, void* stream) {
+  return prepare_opts(jobs, njobs, tables, nullptr, d_workspace, bytes, stream, "qs_hip_encode_device_batch_prepare");
+}
+
+extern "C" int qs_hip_encode_device_batch_prepare_opts(qs_hip_job* const* jobs, int njobs,
+                                                       const qs_hip_huff_tables* const* tables,
+                                                       const qs_hip_encode_opts* const* opts, void* d_workspace,
+                                                       size_t bytes, void* stream) {
+  return prepare_opts(jobs, njobs, tables, opts, d_workspace, bytes, stream, "qs_hip_encode_device_batch_prepare_opts");
 }
 
 extern "C" int qs_hip_encode_device_batch(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop,

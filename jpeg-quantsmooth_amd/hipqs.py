@@ -106,6 +106,11 @@ class EncodeInfo(C.Structure):
                 ("max_segment_bytes", C.c_uint64)]
 
 
+class EncodeOpts(C.Structure):
+    """qs_hip_encode_opts: the restart interval of one job (in MCUs, or in MCU rows when restart_in_rows > 0)"""
+    _fields_ = [("restart_interval", C.c_int32), ("restart_in_rows", C.c_int32)]
+
+
 MAX_PLANES = 56
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -149,6 +154,13 @@ ABI = {
                                               C.c_void_p]),
     "qs_hip_encode_device_batch_histogram": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_encode_device_batch_info_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                        C.POINTER(C.POINTER(EncodeOpts)), C.POINTER(EncodeInfo),
+                                                        C.POINTER(C.c_size_t)]),
+    "qs_hip_encode_device_batch_prepare_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                           C.POINTER(C.POINTER(HuffTables)),
+                                                           C.POINTER(C.POINTER(EncodeOpts)), C.c_void_p, C.c_size_t,
+                                                           C.c_void_p]),
     "qs_hip_huff_optimal": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_huff_standard": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_free": (None, [C.c_void_p]),
@@ -476,12 +488,29 @@ class HipQS:
                                                         d_workspace, nbytes, stream))
 
     # -- device entropy coder (a list of device_job() Jobs) -------------------------------
-    def encode_batch_info(self, jobs):
-        """qs_hip_encode_device_batch_info (no device needed) -> (list of dict(dc_tbl, ac_tbl, blocks_in_mcu,
-        max_segment_bytes), the batch's workspace bytes)"""
+    @staticmethod
+    def _opt_ptrs(opts, n):
+        """opts: None, or one (restart_interval, restart_in_rows) / None per job -> (the pointer array or None, what it
+        points to: keep it alive over the call)"""
+        if opts is None:
+            return None, None
+        if len(opts) != n:
+            raise ValueError("one options entry (or None) per job")
+        recs = [None if o is None else EncodeOpts(int(o[0]), int(o[1])) for o in opts]
+        return (C.POINTER(EncodeOpts) * max(1, n))(*[None if r is None else C.pointer(r) for r in recs]), recs
+
+    def encode_batch_info(self, jobs, opts=None):
+        """qs_hip_encode_device_batch_info, or _info_opts when opts is given (one (restart_interval, restart_in_rows) or
+        None per job); no device needed -> (list of dict(dc_tbl, ac_tbl, blocks_in_mcu, max_segment_bytes), the batch's
+        workspace bytes)"""
         per = (EncodeInfo * max(1, len(jobs)))()
         total = C.c_size_t(0)
-        self._check(self.lib.qs_hip_encode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        if opts is None:
+            self._check(self.lib.qs_hip_encode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        else:
+            optr, _keep = self._opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_encode_device_batch_info_opts(self._job_ptrs(jobs), len(jobs), optr, per,
+                                                                      C.byref(total)))
         return [dict(dc_tbl=list(per[i].dc_tbl[:jobs[i].ncomp]), ac_tbl=list(per[i].ac_tbl[:jobs[i].ncomp]),
                      blocks_in_mcu=list(per[i].blocks_in_mcu), max_segment_bytes=int(per[i].max_segment_bytes))
                 for i in range(len(jobs))], int(total.value)
@@ -500,14 +529,20 @@ class HipQS:
                 has[k] = 1
         return t
 
-    def encode_batch_prepare(self, jobs, tables, d_workspace: int, nbytes: int, stream=None) -> None:
-        """qs_hip_encode_device_batch_prepare: geometry and code tables into the workspace (synchronises `stream`; not
-        inside a capture); tables: None or one HuffTables / None per job"""
+    def encode_batch_prepare(self, jobs, tables, d_workspace: int, nbytes: int, stream=None, opts=None) -> None:
+        """qs_hip_encode_device_batch_prepare, or _prepare_opts when opts is given (as encode_batch_info): geometry, code
+        tables and restart intervals into the workspace (synchronises `stream`; not inside a capture); tables: None or
+        one HuffTables / None per job"""
         ptrs = None
         if tables is not None:
             ptrs = (C.POINTER(HuffTables) * max(1, len(jobs)))(*[C.pointer(t) if t is not None else None for t in tables])
-        self._check(self.lib.qs_hip_encode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), ptrs, d_workspace,
-                                                                nbytes, stream))
+        if opts is None:
+            self._check(self.lib.qs_hip_encode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), ptrs, d_workspace,
+                                                                    nbytes, stream))
+        else:
+            optr, _keep = self._opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_encode_device_batch_prepare_opts(self._job_ptrs(jobs), len(jobs), ptrs, optr,
+                                                                         d_workspace, nbytes, stream))
 
     def encode_batch(self, jobs, d_stop, d_out, capacity, d_len: int, d_status: int, d_workspace: int, nbytes: int,
                      stream=None) -> None:

@@ -1,6 +1,7 @@
 """The markers of a baseline JPEG file around one entropy-coded segment, as libjpeg 9 writes them for a fresh compress
 object after jpeg_write_coefficients (jcmarker.c): SOI, JFIF APP0 or Adobe APP14, one DQT per component, SOF0 (SOF1
-when a quantiser exceeds 8 bits), one DHT per table the scan uses, SOS, the segment, EOI.  Host only, no device.
+when a quantiser exceeds 8 bits), one DHT per table the scan uses, DRI when the scan has a restart interval, SOS, the
+segment, EOI.  Host only, no device.
 
 Conventions of the library's encoder (include/jpegqs_hip.h): component ci uses quant table ci and the Huffman tables
 jpeg_set_colorspace assigns.  Extra markers of a source file (jcopy_markers) are not written."""
@@ -42,9 +43,13 @@ def _dht(index: int, table) -> bytes:
     return _marker(0xC4, bytes([index]) + bytes(bits[1:17]) + bytes(int(v) for v in huffval[:n]))
 
 
-def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, dc_tables, ac_tables) -> bytes:
+def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, dc_tables, ac_tables,
+            restart_interval: int = 0) -> bytes:
     """-> the whole file.  quants[ci]: 64 quantisers in natural order (None: all ones); dc_tables / ac_tables: the two
-    (bits[17], huffval) pairs each; only the tables the components use are written"""
+    (bits[17], huffval) pairs each; only the tables the components use are written.  restart_interval: the scan's
+    interval in MCUs; libjpeg writes DRI behind the last DHT whenever it is not 0, also when it exceeds the MCU count"""
+    if not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval {restart_interval}: 0 .. 65535")
     n = len(quants)
     ids, tbl, jfif, adobe = COLORSPACES[colorspace][0], table_assignment(colorspace, n), *COLORSPACES[colorspace][2:]
     w, h = image_size
@@ -69,6 +74,8 @@ def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, d
             if (is_ac, tbl[ci]) not in sent:
                 sent.add((is_ac, tbl[ci]))
                 out.append(_dht((is_ac << 4) | tbl[ci], tabs[tbl[ci]]))
+    if restart_interval:
+        out.append(_marker(0xDD, struct.pack(">H", int(restart_interval))))
     sos = bytes([n]) + b"".join(bytes([ids[ci], (tbl[ci] << 4) | tbl[ci]]) for ci in range(n)) + bytes([0, 63, 0])
     out.append(_marker(0xDA, sos))
     out.append(bytes(segment))

@@ -353,10 +353,44 @@ def _encode_jobs(images, result, who, torch):
     return jobs, dev, stop
 
 
-def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch):
+def _restart_opts(restart_interval, restart_in_rows, n, who):
+    """the restart keywords of the encode calls -> None (neither given: the calls without options), or one
+    (restart_interval, restart_in_rows) per image"""
+    if restart_interval is None and restart_in_rows is None:
+        return None
+    cols = []
+    for name, v in (("restart_interval", restart_interval), ("restart_in_rows", restart_in_rows)):
+        if v is None:
+            v = 0
+        if hasattr(v, "tolist"):                                    # numpy arrays and tensors, of one value or of many
+            v = v.tolist()
+        vals = [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)] * n
+        if len(vals) != n:
+            raise ValueError(f"{who}: {name} must be an int or hold one per image")
+        cols.append(vals)
+    return list(zip(*cols))
+
+
+def _mcu_geometry(hsamp, vsamp, image_size):
+    """(MCUs per row, MCUs) of libjpeg's scan over these components: one block per MCU in a one-component scan"""
+    w, h = image_size
+    mh, mv = (1, 1) if len(hsamp) == 1 else (max(hsamp), max(vsamp))
+    mx, my = -(-int(w) // (8 * mh)), -(-int(h) // (8 * mv))
+    return mx, mx * my
+
+
+def _scan_interval(opt, hsamp, vsamp, image_size):
+    """the restart_interval libjpeg arrives at for a scan of this geometry (jcmaster.c): what DRI carries"""
+    ri, rows = opt
+    if rows > 0:
+        return min(rows * _mcu_geometry(hsamp, vsamp, image_size)[0], 65535)
+    return ri
+
+
+def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts=None):
     hip = _hip()
-    per, total = hip.encode_batch_info(jobs)
-    key = ("encode", tabkey) + tuple(_key(job, 0, 0) for job in jobs)
+    per, total = hip.encode_batch_info(jobs, opts)
+    key = ("encode", tabkey) + tuple(_key(job, 0, 0) for job in jobs) + (() if opts is None else ("restart", tuple(opts)))
     if workspace is None:
         workspace = Workspace()
     if workspace.key != key:
@@ -366,12 +400,13 @@ def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch):
         if workspace.nbytes < total or workspace.buf.device != dev:
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
         hip.encode_batch_prepare(jobs, tabs, workspace.buf.data_ptr(), workspace.nbytes,
-                                 torch.cuda.current_stream(dev).cuda_stream)
+                                 torch.cuda.current_stream(dev).cuda_stream, opts)
         workspace.key = key
     return per, workspace
 
 
-def encode_scan_batch(images, *, result=None, huffman=None, outs=None, workspace: Workspace | None = None) -> dict:
+def encode_scan_batch(images, *, result=None, huffman=None, outs=None, workspace: Workspace | None = None,
+                      restart_interval=None, restart_in_rows=None) -> dict:
     """The entropy-coded segment of each image's baseline scan, exactly the bytes libjpeg 9 writes between the SOS header
     and EOI for jpeg_write_coefficients on these arrays, on the current stream and without host synchronisation.
 
@@ -380,18 +415,24 @@ def encode_scan_batch(images, *, result=None, huffman=None, outs=None, workspace
     arrays when it reads 1, chosen on the device).  huffman: None (the standard tables), or a dict(dc={0: (bits[17],
     huffval), ...}, ac={...}) for all images, or a list with one such dict or None per image.  outs: preallocated
     contiguous uint8 buffers (their size is the capacity); by default 32 bytes per block.  workspace: as decode_batch.
+    restart_interval / restart_in_rows: libjpeg's fields of these names, an int for all images or one per image -- RSTn
+    markers every restart_interval MCUs (0 .. 65535, 0: none), or every restart_in_rows MCU rows of the geometry the
+    scan has, which wins when > 0; DC prediction starts again behind each marker.  None for both: the call without
+    options (the same bytes as 0).
     Returns dict(segments=[uint8 tensors], len=int64 tensor, status=int32 tensor, workspace): segment i is
     segments[i][:len[i]] when status[i] is 0; status 2: the buffer holds less than len[i] bytes (retry with that
-    size); 1: a coefficient out of libjpeg's range; 3: a symbol without a code in `huffman` (len is 0 for both)."""
-    return _encode_scan_batch(images, result, huffman, outs, workspace, "encode_scan_batch")
+    size); 1: a coefficient out of libjpeg's range; 3: a symbol without a code in `huffman`; 4: the workspace was prepared
+    with a restart interval at another address than it runs at (len is 0 for these three)."""
+    return _encode_scan_batch(images, result, huffman, outs, workspace, "encode_scan_batch",
+                              _restart_opts(restart_interval, restart_in_rows, len(images), "encode_scan_batch"))
 
 
-def _encode_scan_batch(images, result, huffman, outs, workspace, who):
+def _encode_scan_batch(images, result, huffman, outs, workspace, who, opts=None):
     import torch
     jobs, dev, stop = _encode_jobs(images, result, who, torch)
     hip = _hip()
     tabs, tabkey = _huff_tables(hip, huffman, len(jobs), who)
-    per, workspace = _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch)
+    per, workspace = _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts)
     if outs is None:
         outs = [None] * len(jobs)
     if len(outs) != len(jobs):
@@ -400,7 +441,8 @@ def _encode_scan_batch(images, result, huffman, outs, workspace, who):
     for i, (inf, o, im) in enumerate(zip(per, outs, images)):
         if o is None:
             blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
-            o = torch.empty(min(inf["max_segment_bytes"], 4096 + 32 * blocks), dtype=torch.uint8, device=dev)
+            o = torch.empty(min(inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks), dtype=torch.uint8,
+                            device=dev)
         elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
                 or not o.is_contiguous() or o.numel() < 1:
             raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
@@ -414,23 +456,27 @@ def _encode_scan_batch(images, result, huffman, outs, workspace, who):
 
 
 def encode_scan(coefs, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, huffman=None, out=None,
-                workspace: Workspace | None = None) -> dict:
+                workspace: Workspace | None = None, restart_interval=None, restart_in_rows=None) -> dict:
     """encode_scan_batch on one image -> dict(segment, len, status, workspace); len and status are device tensors of
     one element"""
     r = _encode_scan_batch([dict(coefs=coefs, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace, image_size=image_size)],
                            None if result is None else dict(stop=result["stop"], images=[result]), huffman,
-                           None if out is None else [out], workspace, "encode_scan")
+                           None if out is None else [out], workspace, "encode_scan",
+                           _restart_opts(restart_interval, restart_in_rows, 1, "encode_scan"))
     return dict(segment=r["segments"][0], len=r["len"], status=r["status"], workspace=r["workspace"])
 
 
-def encode_histogram_batch(images, *, result=None, workspace: Workspace | None = None) -> dict:
+def encode_histogram_batch(images, *, result=None, workspace: Workspace | None = None, restart_interval=None,
+                           restart_in_rows=None) -> dict:
     """The symbol counts of each image's scan (qs_hip_encode_device_batch_histogram) -> dict(counts: int32 tensor
     (len(images), 4, 257) in the order DC 0, DC 1, AC 0, AC 1 -- entry 256 is libjpeg's reserved symbol and reads 1 --,
-    status: int32 tensor, 1 where a coefficient is out of range; workspace).  No host synchronisation."""
+    status: int32 tensor, 1 where a coefficient is out of range; workspace).  restart_interval / restart_in_rows as
+    encode_scan_batch: the DC differences are those of the restart scan.  No host synchronisation."""
     import torch
     who = "encode_histogram_batch"
     jobs, dev, stop = _encode_jobs(images, result, who, torch)
-    _per, workspace = _encode_workspace(jobs, dev, None, b"", workspace, who, torch)
+    opts = _restart_opts(restart_interval, restart_in_rows, len(jobs), who)
+    _per, workspace = _encode_workspace(jobs, dev, None, b"", workspace, who, torch, opts)
     counts = torch.empty((len(jobs), 4, 257), dtype=torch.int32, device=dev)
     status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
     _hip().encode_batch_histogram(jobs, None if stop is None else stop.data_ptr(), counts.data_ptr(), status.data_ptr(),
@@ -438,16 +484,19 @@ def encode_histogram_batch(images, *, result=None, workspace: Workspace | None =
     return dict(counts=counts, status=status, workspace=workspace)
 
 
-_STATUS_TEXT = {1: "DCT coefficient out of range", 3: "Missing Huffman code table entry"}     # libjpeg's wording
+_STATUS_TEXT = {1: "DCT coefficient out of range", 3: "Missing Huffman code table entry",     # libjpeg's wording
+                4: "the workspace holds a restart interval, but the run does not know it: prepare it at the address it runs at"}
 
 
-def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
+def encode_batch(images, *, result=None, optimize=False, huffman=None, restart_interval=None, restart_in_rows=None) -> list:
     """Complete baseline JPEG files (bytes) of the images, byte for byte what libjpeg 9 writes for jpeg_write_coefficients
     on a fresh compress object with these arrays, tables and sampling factors (jpeg_file.compose has the marker rules).
 
     images[i]: coefs, quants, hsamp, vsamp, colorspace, image_size; result: what quantsmooth_batch_ returned for them
     (its output tables, replacement chroma and stop decide what is written).  optimize: libjpeg's optimize_coding -- the
     histogram on the device, qs_hip_huff_optimal on the host.  huffman: caller tables instead (see encode_scan_batch).
+    restart_interval / restart_in_rows: as encode_scan_batch; the file gets the DRI marker of the geometry written, and
+    optimize counts the symbols of the restart scan.
     Reads len / status, which synchronises; a buffer that proved too small is retried once with the exact size.  Raises
     ValueError with libjpeg's message where libjpeg would stop."""
     import torch
@@ -455,6 +504,7 @@ def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
     who = "encode_batch"
     hip = _hip()
     n = len(images)
+    opts = _restart_opts(restart_interval, restart_in_rows, n, who)
     stops = [0] * n if result is None else [int(v) for v in result["stop"].cpu().tolist()]
     # what each file's header describes: the smoothing's output tables and, for a standing UPSAMPLE_UV, 1x1 chroma
     desc = []
@@ -475,7 +525,8 @@ def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
     if optimize:
         if huffman is not None:
             raise ValueError(f"{who}: optimize and huffman exclude each other")
-        h = encode_histogram_batch(images, result=result)
+        h = encode_histogram_batch(images, result=result, restart_interval=restart_interval,
+                                   restart_in_rows=restart_in_rows)
         bad = [i for i, s in enumerate(h["status"].cpu().tolist()) if s]
         if bad:
             raise ValueError(f"{who}: image {bad[0]}: {_STATUS_TEXT[1]}")
@@ -486,12 +537,12 @@ def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
             huffman.append(dict(dc={t: hip.huff_optimal(counts[i, t]) for t in used},
                                 ac={t: hip.huff_optimal(counts[i, 2 + t]) for t in used}))
     per = huffman if isinstance(huffman, (list, tuple)) else [huffman] * n
-    r = _encode_scan_batch(images, result, huffman, None, None, who)
+    r = _encode_scan_batch(images, result, huffman, None, None, who, opts)
     lens, status = r["len"].cpu().tolist(), r["status"].cpu().tolist()
     if any(s == 2 for s in status):
         outs = [torch.empty(max(1, int(l)), dtype=torch.uint8, device=o.device) if s == 2 else o
                 for o, l, s in zip(r["segments"], lens, status)]
-        r = _encode_scan_batch(images, result, huffman, outs, r["workspace"], who)
+        r = _encode_scan_batch(images, result, huffman, outs, r["workspace"], who, opts)
         lens, status = r["len"].cpu().tolist(), r["status"].cpu().tolist()
     files = []
     for i, (d, seg, l, s) in enumerate(zip(desc, r["segments"], lens, status)):
@@ -501,14 +552,15 @@ def encode_batch(images, *, result=None, optimize=False, huffman=None) -> list:
         dc = {t: (h.get("dc") or {}).get(t, std["dc"][t]) for t in (0, 1)}
         ac = {t: (h.get("ac") or {}).get(t, std["ac"][t]) for t in (0, 1)}
         files.append(jpeg_file.compose(seg[:int(l)].cpu().numpy().tobytes(), d["quants"], d["hsamp"], d["vsamp"],
-                                       d["colorspace"], d["image_size"], dc, ac))
+                                       d["colorspace"], d["image_size"], dc, ac,
+                                       0 if opts is None else _scan_interval(opts[i], d["hsamp"], d["vsamp"], d["image_size"])))
     return files
 
 
 def encode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, optimize=False,
-           huffman=None) -> bytes:
+           huffman=None, restart_interval=None, restart_in_rows=None) -> bytes:
     """encode_batch on one image -> the JPEG file as bytes"""
     return encode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                               image_size=image_size)],
                         result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
-                        huffman=huffman)[0]
+                        huffman=huffman, restart_interval=restart_interval, restart_in_rows=restart_in_rows)[0]

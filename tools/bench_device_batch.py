@@ -45,6 +45,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--decode", action="store_true", help="time the device decode to pixels instead")
     ap.add_argument("--encode", action="store_true", help="time the device entropy coder instead")
+    ap.add_argument("--restart", type=int, default=None, metavar="N",
+                    help="--encode: write a restart marker every N MCUs (libjpeg's restart_interval)")
+    ap.add_argument("--restart-rows", type=int, default=None, metavar="N",
+                    help="--encode: write a restart marker every N MCU rows (libjpeg's restart_in_rows)")
     a = ap.parse_args()
     if a.decode:
         return bench_decode(a)
@@ -203,6 +207,20 @@ def bench_decode(a):
     print(json.dumps(out), flush=True)
 
 
+def host_writer(workdir, restart=None, restart_rows=None):
+    """libjpeg 9 as the host side of --encode: (the helper that stages the input, write(staged) -> the file's bytes);
+    with a restart option the helper that sets cinfo.restart_interval / restart_in_rows, so that the file compared and
+    the write timed have the same markers as the device's segment"""
+    sys.path.insert(0, str(ROOT / "tests"))
+    if restart or restart_rows:
+        from encode_rst_oracle import LibJpeg9EncRst
+        enc = LibJpeg9EncRst(workdir)
+        return enc, lambda staged: enc.run(staged, restart or 0, restart_rows or 0)
+    from encode_oracle import LibJpeg9Enc
+    enc = LibJpeg9Enc(workdir)
+    return enc, enc.run
+
+
 def bench_encode(a):
     import tempfile
     import numpy as np
@@ -210,7 +228,10 @@ def bench_encode(a):
     import jpegqs_pkg
     sys.path.insert(0, str(ROOT / "tests"))
     from decode_oracle import synth_image
-    from encode_oracle import LibJpeg9Enc, parse_jpeg
+    from encode_oracle import parse_jpeg
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows) if a.restart or a.restart_rows else {}
+    if rst:
+        from encode_rst_oracle import parse_rst
     torch_qs = jpegqs_pkg.load().torch_qs
     if not torch.cuda.is_available():
         raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
@@ -221,24 +242,26 @@ def bench_encode(a):
              ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
              (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
     out = dict(tool="bench_device_batch", leg="encode", device=torch.cuda.get_device_name(dev), results=[])
+    if rst:
+        out["restart"] = rst
     for name, ims in cases:
         images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], hsamp=im["hsamp"], vsamp=im["vsamp"],
                        colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
         ws = torch_qs.Workspace()
-        r = torch_qs.encode_scan_batch(images, workspace=ws)
+        r = torch_qs.encode_scan_batch(images, workspace=ws, **rst)
         outs, lens = r["segments"], [int(v) for v in r["len"].cpu().tolist()]
         assert r["status"].cpu().tolist() == [0] * len(images), "the default capacity did not hold the segment"
         pinned = [torch.empty(l, dtype=torch.uint8).pin_memory() for l in lens]
         coef_bytes = sum(sum(c.numel() * 2 for c in im["coefs"]) for im in images)
 
         def device_route():
-            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws)
+            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws, **rst)
             for p, o, l in zip(pinned, outs, lens):
                 p.copy_(o[:l], non_blocking=True)
             torch.cuda.synchronize()
 
         def kernels_only():
-            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws)
+            torch_qs.encode_scan_batch(images, outs=outs, workspace=ws, **rst)
             torch.cuda.synchronize()
 
         host_pinned = [[torch.empty(c.shape, dtype=torch.int16).pin_memory() for c in im["coefs"]] for im in images]
@@ -267,18 +290,18 @@ def bench_encode(a):
                    device_encode_plus_copy_ms=dev_ms, device_windows=dev_all, device_encode_ms=k_ms,
                    host_coef_copy_ms=copy_ms, host_copy_windows=copy_all, device_faster_than_copy=bool(dev_ms < copy_ms))
         with tempfile.TemporaryDirectory() as td:                   # the helper on a staged input: libjpeg reads the
-            enc = LibJpeg9Enc(Path(td))                             # arrays, writes the file; one warm-up, then windows
-            unit = [np.ones(64, np.uint16)] * len(ims[0]["coefs"])
+            enc, write = host_writer(Path(td), a.restart, a.restart_rows)   # arrays, writes the file; one warm-up, then
+            unit = [np.ones(64, np.uint16)] * len(ims[0]["coefs"])          # windows -- with the same restart interval
             staged = enc.stage(dict(ims[0], quants=unit))
-            want = enc.run(staged)
+            want = write(staged)
             ts = []
             for _ in range(a.repeats):
                 t0 = time.perf_counter()
-                enc.run(staged)
+                write(staged)
                 ts.append((time.perf_counter() - t0) * 1e3)
             row["host_libjpeg9_write_ms_per_image"] = round(float(np.median(ts)), 1)
             row["host_libjpeg9_windows"] = [round(t, 1) for t in ts]
-            seg = parse_jpeg(want)["segment"]
+            seg = (parse_rst if rst else parse_jpeg)(want)["segment"]
             row["identical"] = all(seg == p.numpy().tobytes() for p, im in zip(pinned, ims) if im is ims[0])
         row["host_route_ms"] = round(copy_ms + row["host_libjpeg9_write_ms_per_image"] * len(images), 1)
         out["results"].append(row)
