@@ -389,7 +389,7 @@ size_t qs_hip_plane_row_offset(int wblk, int y);
 int qs_hip_consts_build(void *host_out, const uint16_t quant[64], int flags);
 
 /* pass A: [first: dequantise + range check ->*d_status |= 1] IDCT into the plane
- * (reference :2589-2620).  rep_top/rep_bot: fill the y=-1 / y=h apron rows by
+ * (reference :2589-2620).  first: 0, 1, or 1 | QS_HIP_FIRST_DEFER (see QS_HIP_PLANE_DEFER below).  rep_top/rep_bot: fill the y=-1 / y=h apron rows by
  * replication (0 when they are halo rows owned by a neighbouring band). */
 int qs_hip_idct_plane(const void *d_consts, int16_t *d_coef, uint8_t *d_plane,
 		int wblk, int hblk, int first, int rep_top, int rep_bot,
@@ -422,8 +422,21 @@ typedef struct {
 	int32_t *d_status;
 	int32_t wblk, hblk, luma;
 	int32_t band;  /* 0: a whole plane.  Bit 0 / bit 1: the plane is a band of block rows whose top /
-	                * bottom apron row is a halo row received from the neighbouring band (pass A leaves it alone) */
+	                * bottom apron row is a halo row received from the neighbouring band (pass A leaves it alone).
+	                * Bit 2 (QS_HIP_PLANE_DEFER): deferred dequantisation, see below */
 } qs_hip_plane_ref;   /* 48 bytes, unchanged since the plane-set calls appeared: every field must be set by the caller */
+/* Deferred dequantisation (opt-in, per plane).  By default pass A of iteration 0 (first = 1) stores the dequantised
+ * coefficients back to d_coef, and whoever looks at d_coef afterwards sees them.  A caller that runs the first pass A
+ * and then, with NO reader of d_coef in between, the first qs_hip_smooth_planes[_next] launch over the same plane can
+ * set QS_HIP_PLANE_DEFER in `band` for exactly these two calls: pass A then dequantises, range-checks (*d_status)
+ * and writes the pixel plane as always but leaves d_coef as it found it (a third of the pass's memory traffic less),
+ * and the smoothing launch forms the same products while it loads the coefficients.  What is in d_coef and in the
+ * planes after the smoothing launch is byte for byte what the default gives.  The bit means "d_coef is still
+ * quantised" to the smoothing launch: it must be clear in every later call.  qs_hip_idct_planes ignores it when
+ * first = 0.  The single-plane pass A takes the same request as first = 1 | QS_HIP_FIRST_DEFER (the launch that
+ * consumes it is a plane-set launch with QS_HIP_PLANE_DEFER; the single-plane smoothing calls have no such form). */
+#define QS_HIP_PLANE_DEFER 4
+#define QS_HIP_FIRST_DEFER 2
 int qs_hip_idct_planes(const qs_hip_plane_ref *refs, int n, int first, void *stream);
 int qs_hip_smooth_planes(const qs_hip_plane_ref *refs, int n, int flags, int final_clamp, void *stream);
 /* qs_hip_smooth_planes that ALSO writes the next iteration's pixel planes (see qs_hip_smooth_plane_next):

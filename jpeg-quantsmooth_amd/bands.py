@@ -252,6 +252,11 @@ def run_bands_batched(engines, topo: BandTopology, niter: int, exchange_many) ->
             e.smooth(it == niter - 1)
 
 
+def defer_bit() -> int:
+    """QS_HIP_PLANE_DEFER for the plane-set schedules below, 0 with QS_BANDS_DEFER=0 (A/B runs, tests of both forms)"""
+    return 0 if os.environ.get("QS_BANDS_DEFER", "1") == "0" else 4
+
+
 def run_bands_batched_sets(hip, engines, topo: BandTopology, niter: int, exchange_many, stream=None, mark=None, fused=True) -> None:
     """run_bands_batched with ONE launch per pass for all planes of the batch (plane sets,
     qs_hip_idct_planes / qs_hip_smooth_planes): a 1/8 band of an 8192^2 plane is 2048 waves, two per
@@ -269,14 +274,18 @@ def run_bands_batched_sets(hip, engines, topo: BandTopology, niter: int, exchang
         for e in engines:
             e.ensure_plane2()
     for it in range(niter):
+        # Deferred dequantisation (include/jpegqs_hip.h: QS_HIP_PLANE_DEFER): the first pass A leaves the coefficients
+        # quantised and the first pass B, which follows on the same stream over the same planes, multiplies while it
+        # loads them.  Only pixel rows are exchanged in between; nothing reads the coefficients.
+        q = defer_bit() if it == 0 else 0
         if it == 0 or not fused:
             refs = hip.plane_refs([(e.cst.data_ptr(), e.coef.data_ptr(), e.plane.data_ptr(), e.status.data_ptr(),
-                                    e.wblk, e.hblk, e.luma, band) for e in engines])
+                                    e.wblk, e.hblk, e.luma, band | q) for e in engines])
             hip.idct_planes(refs, it == 0, s)
         exchange_many()
         nxt = fused and it < niter - 1
         refs = hip.plane_refs([(e.cst.data_ptr(), e.coef.data_ptr(), e.plane.data_ptr(), e.status.data_ptr(),
-                                e.wblk, e.hblk, e.luma, band, e.plane2.data_ptr() if nxt else None) for e in engines])
+                                e.wblk, e.hblk, e.luma, band | q, e.plane2.data_ptr() if nxt else None) for e in engines])
         if mark:
             mark(0)                                  # (bench.py: HIP events around the pass-B launch)
         hip.smooth_planes(refs, flags, it == niter - 1, s)
@@ -307,17 +316,20 @@ def run_band_edge_first(hip, e, topo: BandTopology, niter: int, exchange, main, 
     pitch, wb, hb = e.pitch, e.wblk, e.hblk
     row_bytes = wb * 128
 
-    def views(cur, nxt):
-        """(edge set, interior set) for planes cur -> nxt (nxt None on the last iteration)"""
+    def views(cur, nxt, q):
+        """(edge set, interior set) for planes cur -> nxt (nxt None on the last iteration); q: defer_bit() in iteration 0"""
         c0, p0 = e.coef.data_ptr(), cur.data_ptr()
         n0 = nxt.data_ptr() if nxt is not None else None
         at = lambda base, r: base + r * 8 * pitch if base is not None else None
-        top = (e.cst.data_ptr(), c0, p0, e.status.data_ptr(), wb, 1, e.luma, band_top | 2, n0)
-        bot = (e.cst.data_ptr(), c0 + (hb - 1) * row_bytes, at(p0, hb - 1), e.status.data_ptr(), wb, 1, e.luma, 1 | band_bot, at(n0, hb - 1))
-        mid = (e.cst.data_ptr(), c0 + row_bytes, at(p0, 1), e.status.data_ptr(), wb, hb - 2, e.luma, 3, at(n0, 1))
+        top = (e.cst.data_ptr(), c0, p0, e.status.data_ptr(), wb, 1, e.luma, band_top | 2 | q, n0)
+        bot = (e.cst.data_ptr(), c0 + (hb - 1) * row_bytes, at(p0, hb - 1), e.status.data_ptr(), wb, 1, e.luma, 1 | band_bot | q, at(n0, hb - 1))
+        mid = (e.cst.data_ptr(), c0 + row_bytes, at(p0, 1), e.status.data_ptr(), wb, hb - 2, e.luma, 3 | q, at(n0, 1))
         return hip.plane_refs([top, bot]), hip.plane_refs([mid])
     ev_main, ev_edge = torch.cuda.Event(), torch.cuda.Event()
-    whole = hip.plane_refs([(e.cst.data_ptr(), e.coef.data_ptr(), e.plane.data_ptr(), e.status.data_ptr(), wb, hb, e.luma, band_top | band_bot)])
+    # deferred dequantisation: the three launches of iteration 0 together cover every block of the band exactly once, and
+    # each multiplies the rows it loads (only pixel rows travel in between)
+    whole = hip.plane_refs([(e.cst.data_ptr(), e.coef.data_ptr(), e.plane.data_ptr(), e.status.data_ptr(), wb, hb, e.luma,
+                             band_top | band_bot | (defer_bit() if niter > 0 else 0))])
     hip.idct_planes(whole, True, main.cuda_stream)
     ev_main.record(main)
     side.wait_event(ev_main)
@@ -325,7 +337,7 @@ def run_band_edge_first(hip, e, topo: BandTopology, niter: int, exchange, main, 
         exchange()                                       # halo rows of the first planes
     for it in range(niter):
         last = it == niter - 1
-        edge, mid = views(e.plane, None if last else e.plane2)
+        edge, mid = views(e.plane, None if last else e.plane2, defer_bit() if it == 0 else 0)
         # edge rows: behind the previous interior launch (their neighbours' pixels) and, in stream order, the exchange
         if it:
             side.wait_event(ev_main)

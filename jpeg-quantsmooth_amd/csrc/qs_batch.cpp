@@ -150,7 +150,9 @@ static int run_coupled(qs_hip_job* const* jobs, const std::vector<int>& which, i
   auto plane_of = [&](int g, int ci) { return plane_at(g, ci, cur[(size_t)g * 3 + ci]); };
   auto lowres_of = [&](int g) { return cj[g].sub ? px.as<uint8_t>() + cj[g].l_off : plane_of(g, 0); };
   // next(g, ci): does the coming pass B write this plane's successor?
-  auto make_set = [&](QsPlaneSet& set, int ci0, int ci1, const std::function<bool(int, int)>& next) {
+  // quant: deferred dequantisation (qs_device.h: QS_PLANE_QUANT) -- the set of a first pass A and of the first pass B
+  // behind it, where nothing reads the coefficients in between
+  auto make_set = [&](QsPlaneSet& set, int ci0, int ci1, const std::function<bool(int, int)>& next, bool quant = false) {
     memset(&set, 0, sizeof set);
     int w = 0, n = 0;
     for (int g = 0; g < G; ++g)
@@ -165,7 +167,8 @@ static int run_coupled(qs_hip_job* const* jobs, const std::vector<int>& which, i
         R.plane_next = next(g, ci) ? plane_at(g, ci, !cur[(size_t)g * 3 + ci]) : nullptr;
         R.status = status.as<int32_t>() + g * 3 + ci;
         R.wblk = job->wblk[ci]; R.hblk = job->hblk[ci]; R.pitch = qs_plane_pitch(job->wblk[ci]);
-        R.mode = QS_PLANE_REP_TOP | QS_PLANE_REP_BOT | (comp_rebalance(job, ci, flags) ? QS_PLANE_REBALANCE : 0);
+        R.mode = QS_PLANE_REP_TOP | QS_PLANE_REP_BOT | (comp_rebalance(job, ci, flags) ? QS_PLANE_REBALANCE : 0) |
+                 (quant ? QS_PLANE_QUANT : 0);
       }
     set.n = n;
     for (int i = n; i < QS_MAX_PLANES + 2; ++i) set.wave0[i] = w;
@@ -179,10 +182,11 @@ static int run_coupled(qs_hip_job* const* jobs, const std::vector<int>& which, i
   // ---- luma: pass A once, niter iterations; the last one also writes the refresh the chroma stages read (reference
   // :2495, :2622) and carries the +-1023 clamp: the fused IDCT reads the unclamped coefficients the kernel holds, so
   // the refresh is that of the unclamped luma, as in the reference, whose clamp sits behind its loop (:2668-2689).
-  make_set(set, 0, 1, none);
+  const bool defer_y = niter > 0;
+  make_set(set, 0, 1, none, defer_y);
   qs_launch_idct_set(set, 1, s);
   for (int it = 0; it < niter; ++it) {
-    make_set(set, 0, 1, all);
+    make_set(set, 0, 1, all, defer_y && it == 0);
     qs_launch_smooth_set(set, diag, it == niter - 1, s);
     flip(0, 1, all);
   }
@@ -201,11 +205,13 @@ static int run_coupled(qs_hip_job* const* jobs, const std::vector<int>& which, i
   bool any_up = false;
   for (int g = 0; g < G; ++g) any_up |= cj[g].upsample;
   const std::function<bool(int, int)> ups = [&](int g, int) { return cj[g].upsample; };
-  make_set(set, 1, 3, none);
+  // (with JOINT_YUV the predictor step reads and writes the coefficients between pass A and pass B: eager)
+  const bool defer_c = niter > 0 && !joint;
+  make_set(set, 1, 3, none, defer_c);
   qs_launch_idct_set(set, 1, s);
   for (int it = 0; it < niter; ++it) {
     const std::function<bool(int, int)>& next = it < niter - 1 ? all : ups;
-    make_set(set, 1, 3, next);
+    make_set(set, 1, 3, next, defer_c && it == 0);
     if (joint)                                               // JOINT_YUV acts through the low-res luma plane (reference :2636)
       qs_launch_joint_set(set, lowres, 0, 0, s);
     qs_launch_smooth_set(set, diag, it == niter - 1, s);

@@ -31,6 +31,29 @@ __device__ __forceinline__ void interval(int c, int div, int x1, int sh, int& or
 }
 
 
+// Dequantisation of one 16-byte group of a block's coefficients (reference quantsmooth.h:2597-2603): the eight int16 of
+// eighth e of a block (natural indices 8e .. 8e + 7) times the file's quantiser q[0..7] = qraw[8e ..], each product
+// stored as JCOEF (int16 wrap).  CHECK: `bad` collects products outside [-2048, 2047] (the reference's range check).
+// Used where a wave moves coefficients as contiguous 16 B per lane: e = lane & 7 (pass A and the recovery kernels'
+// stage-in of a plane whose coefficients are still quantised, QS_PLANE_QUANT).
+__device__ __forceinline__ void qs_load_qraw8(const QsConsts* __restrict__ cst, int e, int (&q)[8]) {
+  const int4* qp = reinterpret_cast<const int4*>(cst->qraw) + e * 2;
+  const int4 a = qp[0], b = qp[1];
+  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
+}
+template <bool CHECK>
+__device__ __forceinline__ uint4 qs_dequant8(uint4 v, const int (&q)[8], int& bad) {
+  uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int lo = (int32_t)(int16_t)(d[c] & 0xffff) * q[c * 2];
+    const int hi = ((int32_t)d[c] >> 16) * q[c * 2 + 1];
+    if (CHECK) bad |= ((unsigned)(lo + 0x800) > 0xfffu) | ((unsigned)(hi + 0x800) > 0xfffu);
+    d[c] = ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+  }
+  return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
 // index of the plane that owns 64-block group `w` of a plane-set launch
 // (binary search over the prefix array; everything here is wave-uniform)
 __device__ __forceinline__ int qs_set_find(const QsPlaneSet& set, int w) {

@@ -88,7 +88,13 @@ struct QsPlaneRef {
 enum {
   QS_PLANE_REBALANCE = 1,  // pass B: run the rebalance step on this plane
   QS_PLANE_REP_TOP = 2,    // pass A: the y = -1 apron row is a replica of row 0 (image edge) ...
-  QS_PLANE_REP_BOT = 4     // ... / the y = h apron row of row h-1; clear = halo row owned by the neighbouring band
+  QS_PLANE_REP_BOT = 4,    // ... / the y = h apron row of row h-1; clear = halo row owned by the neighbouring band
+  // Deferred dequantisation: this plane's coefficients are STILL QUANTISED.  Pass A of iteration 0 (`first`) forms the
+  // products coef * qraw, range-checks them and runs the IDCT of their int16 wrap as always, but does not store them;
+  // the recovery launch that follows forms the same products, in the same wrap, when it stages the coefficients into
+  // LDS, and writes dequantised results as always.  Set by the routes that know that this launch follows pass A with
+  // no reader of `coef` in between, for the first pass A and the first recovery launch only.
+  QS_PLANE_QUANT = 8
 };
 // one more device pointer per plane of a set, for the stages that read a second plane
 // (JOINT_YUV: the low-res luma plane the chroma plane is predicted from)

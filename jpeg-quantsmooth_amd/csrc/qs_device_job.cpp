@@ -424,7 +424,10 @@ int run_sets(qs_hip_job* const* jobs, int njobs, int flags, const BatchPlan& B, 
   };
   const int diag = (flags & QS_DIAGONALS) != 0;
   // one stage over `ids`, cut into launches of at most QS_MAX_PLANES planes; next(d): the pass B writes d's next plane
-  auto stage = [&](const std::vector<Id>& ids, bool idct, bool joint, int final_clamp, auto next) {
+  // quant: deferred dequantisation (qs_device.h: QS_PLANE_QUANT) -- a first pass A and the first pass B behind it, where
+  // nothing reads the coefficients in between.  A job whose range check trips runs on all the same; the fix-up rebuilds
+  // its arrays from the snapshot afterwards.
+  auto stage = [&](const std::vector<Id>& ids, bool idct, bool joint, int final_clamp, auto next, bool quant = false) {
     for (size_t c0 = 0; c0 < ids.size(); c0 += QS_MAX_PLANES) {
       QsPlaneSet set;
       QsPlaneAux aux;
@@ -446,7 +449,7 @@ int run_sets(qs_hip_job* const* jobs, int njobs, int flags, const BatchPlan& B, 
         R.status = reinterpret_cast<int32_t*>(ws + B.region[d.job] + C.off_status);
         R.wblk = job->wblk[d.ci]; R.hblk = job->hblk[d.ci]; R.pitch = qs_plane_pitch(job->wblk[d.ci]);
         const int rebalance = !(flags & QS_NO_REBALANCE) && (comp_luma(job, d.ci) || !(flags & QS_NO_REBALANCE_UV));
-        R.mode = QS_PLANE_REP_TOP | QS_PLANE_REP_BOT | (rebalance ? QS_PLANE_REBALANCE : 0);
+        R.mode = QS_PLANE_REP_TOP | QS_PLANE_REP_BOT | (rebalance ? QS_PLANE_REBALANCE : 0) | (quant ? QS_PLANE_QUANT : 0);
         aux.p[k] = lowres_of(d.job);
       }
       set.n = n;
@@ -475,10 +478,11 @@ int run_sets(qs_hip_job* const* jobs, int njobs, int flags, const BatchPlan& B, 
   // independent planes and coupled luma: pass A, then niter passes B; each pass B but an independent plane's last
   // writes the next plane (coupled luma: the refresh the chroma stages read, reference :2495, :2622); the last carries
   // the +-1023 clamp
-  stage(first, true, false, 0, none);
+  const bool defer = niter > 0;
+  stage(first, true, false, 0, none, defer);
   for (int it = 0; it < niter; ++it) {
     const bool last = it == niter - 1;
-    stage(first, false, false, last, [&](const Id& d) { return !last || B.route[d.job] == ROUTE_COUPLED; });
+    stage(first, false, false, last, [&](const Id& d) { return !last || B.route[d.job] == ROUTE_COUPLED; }, defer && it == 0);
   }
   if (chroma.empty()) return QS_HIP_OK;
   for (int i = 0; i < njobs; ++i) {                          // image2 (reference :2753-2815)
@@ -489,10 +493,12 @@ int run_sets(qs_hip_job* const* jobs, int njobs, int flags, const BatchPlan& B, 
   }
   // chroma: a job upsampled afterwards needs one more refresh, which its last pass B writes
   const bool joint = (flags & QS_JOINT_YUV) != 0;
-  stage(chroma, true, false, 0, none);
+  // (with JOINT_YUV the predictor step reads and writes the coefficients between pass A and pass B: eager)
+  const bool defer_c = defer && !joint;
+  stage(chroma, true, false, 0, none, defer_c);
   for (int it = 0; it < niter; ++it) {
     const bool last = it == niter - 1;
-    stage(chroma, false, joint, last, [&](const Id& d) { return !last || B.P[d.job].c[d.ci].upsample; });
+    stage(chroma, false, joint, last, [&](const Id& d) { return !last || B.P[d.job].c[d.ci].upsample; }, defer_c && it == 0);
   }
   for (int i = 0; i < njobs; ++i) {                          // UPSAMPLE_UV (reference :2691-2752)
     if (B.route[i] != ROUTE_COUPLED || !B.P[i].up) continue;

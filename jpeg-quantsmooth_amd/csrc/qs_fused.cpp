@@ -224,6 +224,11 @@ int qsj::run_fused(qs_hip_job* const* jobs, const std::vector<int>& which, int f
     for (int i = np; i < QS_MAX_PLANES + 2; ++i) set.wave0[i] = w;
     // pass A once (dequantise, range check, first pixel planes); every pass B but the last writes the next
     // iteration's planes itself (fused pass A, ping-pong between the two planes of each FPlane)
+    // Deferred dequantisation (qs_device.h: QS_PLANE_QUANT): the first pass B follows on the same stream over the same
+    // planes and nothing reads the coefficients in between, so pass A leaves them quantised and that pass B multiplies
+    // while it loads them.  A group whose range check trips runs on all the same and is never written back (below).
+    const bool quant = niter > 0;
+    if (quant) for (int i = 0; i < np; ++i) set.ref[i].mode |= QS_PLANE_QUANT;
     qs_launch_idct_set(set, 1, G.s);
     if (plan) {                                              // the flags as pass A left them, for the progress calls (see FGroup)
       if (!G.hstatus0.alloc((size_t)np * sizeof(int32_t))) return qs_fail(QS_HIP_ENOMEM, "out of pinned host memory");
@@ -239,6 +244,7 @@ int qsj::run_fused(qs_hip_job* const* jobs, const std::vector<int>& which, int f
         set.ref[i].plane_next = it == niter - 1 ? nullptr : (it & 1) ? a : b;
       }
       qs_launch_smooth_set(set, diag, it == niter - 1, G.s);
+      if (it == 0) for (int i = 0; i < np; ++i) set.ref[i].mode &= ~QS_PLANE_QUANT;   // HBM holds dequantised coefficients from here on
       if (plan) {
         hipEvent_t e = nullptr;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));

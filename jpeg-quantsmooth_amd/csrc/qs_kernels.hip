@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "qs_device.h"
+#include "qs_devfn.h"
 
 /* QS_LDS_PITCH (65 dwords per coefficient-pair row: 64 lanes + 1 pad) comes from qs_device.h: the host packs LDS offsets into QsConsts::rec */
 
@@ -150,9 +151,13 @@ __device__ __forceinline__ float pix_from_byte(uint32_t v, int n) {
 // Kernel A: (dequantise +) IDCT every block into the pixel plane and write the
 // clamp-to-edge apron.  One block per lane; consecutive lanes take consecutive
 // blocks of a block row so the 8-byte pixel-row stores of a wave coalesce into
-// 512-byte segments.  Reference quantsmooth.h:2589-2620 (pass A + borders).
+// 512-byte segments; the coefficients reach the lanes through an LDS
+// transposition (idct_wave_to_plane), so that a wave's global loads are
+// contiguous too.  Reference quantsmooth.h:2589-2620 (pass A + borders).
 //   first   : iteration 0 -- multiply by the file's quantiser, flag
-//             out-of-range products (reference :2597-2603)
+//             out-of-range products (reference :2597-2603); the products go
+//             back to `coef` unless the plane defers its dequantisation
+//             (QS_PLANE_QUANT, qs_device.h)
 //   rep_top / rep_bot : write the y = -1 / y = h apron rows by replication
 //             (false for the interior edges of a multi-GPU band, whose apron
 //             rows are halo rows received from the neighbouring band)
@@ -199,65 +204,87 @@ idct_ws_to_plane(uint32_t (&ws)[64], uint8_t* __restrict__ plane, int wblk, int 
   }
 }
 
+// Pass A for the 64 consecutive blocks [base, base + 64) of a plane, one wave.  The wave's coefficients are 8 KiB
+// contiguous: they are moved as 16 B per lane, eight fully coalesced wave loads, and transposed through the wave's LDS
+// slice into one dword column per lane (pitch QS_LDS_PITCH: conflict-free both ways, the staging of the recovery
+// kernels).  Lane l then runs the IDCT of block base + l.  Iteration 0 (`first`) multiplies by the file's quantiser on
+// the way in, each lane its eighth of eight blocks (qs_dequant8), and -- unless the plane defers its dequantisation
+// (QS_PLANE_QUANT: the recovery launch that follows forms the same products itself) -- stores the products back the
+// way they came.
 __device__ __forceinline__ void
-idct_block_to_plane(const QsConsts* __restrict__ cst, int16_t* __restrict__ coef,
-                    uint8_t* __restrict__ plane, int wblk, int hblk, int pitch,
-                    int first, int rep_top, int rep_bot, int* __restrict__ status, int blk) {
-  uint4* cp = reinterpret_cast<uint4*>(coef) + (size_t)blk * 8;
-  uint32_t ws[64];
+idct_wave_to_plane(const QsConsts* __restrict__ cst, int16_t* __restrict__ coef,
+                   uint8_t* __restrict__ plane, int wblk, int hblk, int pitch,
+                   int first, int defer, int rep_top, int rep_bot, int* __restrict__ status, int base, uint32_t* lds) {
+  const int lane = threadIdx.x & 63;
+  const int nblk = wblk * hblk;
+  const int nvec = min(64, nblk - base) * 8;
+  uint4* gsrc = reinterpret_cast<uint4*>(coef) + (size_t)base * 8;
+  uint4 v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    uint4 v = cp[j];
-    uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      ws[j * 8 + c * 2] = (uint32_t)(int32_t)(int16_t)(d[c] & 0xffff);
-      ws[j * 8 + c * 2 + 1] = (uint32_t)((int32_t)d[c] >> 16);
-    }
+    const int idx = j * 64 + lane;
+    v[j] = make_uint4(0, 0, 0, 0);
+    if (idx < nvec) v[j] = gsrc[idx];
   }
-  if (first) {
-    int bad = 0;
+  if (first) {                                              // (wave-uniform)
+    int q[8], bad = 0;
+    qs_load_qraw8(cst, lane & 7, q);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      uint32_t d[4];
+    for (int j = 0; j < 8; ++j) v[j] = qs_dequant8<true>(v[j], q, bad);
+    if (!defer) {                                           // (wave-uniform)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        int lo = (int32_t)ws[j * 8 + c * 2] * cst->qraw[j * 8 + c * 2];
-        int hi = (int32_t)ws[j * 8 + c * 2 + 1] * cst->qraw[j * 8 + c * 2 + 1];
-        bad |= ((unsigned)(lo + 0x800) > 0xfffu) | ((unsigned)(hi + 0x800) > 0xfffu);
-        lo = (int16_t)lo; hi = (int16_t)hi;  // stored as JCOEF (reference :2599)
-        ws[j * 8 + c * 2] = (uint32_t)lo; ws[j * 8 + c * 2 + 1] = (uint32_t)hi;
-        d[c] = ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+      for (int j = 0; j < 8; ++j) {
+        const int idx = j * 64 + lane;
+        if (idx < nvec) gsrc[idx] = v[j];
       }
-      cp[j] = make_uint4(d[0], d[1], d[2], d[3]);
     }
     if (bad) atomicOr(status, 1);
   }
-  idct_ws_to_plane(ws, plane, wblk, hblk, pitch, rep_top, rep_bot, blk);
+  {
+    const int m0 = (lane & 7) * 4;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      uint32_t* dst = lds + m0 * QS_LDS_PITCH + (j * 8 + (lane >> 3));
+      dst[0] = v[j].x; dst[QS_LDS_PITCH] = v[j].y; dst[2 * QS_LDS_PITCH] = v[j].z; dst[3 * QS_LDS_PITCH] = v[j].w;
+    }
+  }
+  wave_lds_sync();
+  const uint32_t* col = lds + lane;
+  uint32_t ws[64];
+#pragma unroll
+  for (int r = 0; r < 32; ++r) {
+    const uint32_t d = col[r * QS_LDS_PITCH];
+    ws[r * 2] = (uint32_t)(int32_t)(int16_t)(d & 0xffff);
+    ws[r * 2 + 1] = (uint32_t)((int32_t)d >> 16);
+  }
+  if (base + lane < nblk) idct_ws_to_plane(ws, plane, wblk, hblk, pitch, rep_top, rep_bot, base + lane);
 }
 
+// first: bit 0 = iteration 0 (dequantise + range check), bit 1 = ... with deferred dequantisation (no store to coef)
 __global__ void __launch_bounds__(256)
 qs_idct_plane_kernel(const QsConsts* __restrict__ cst, int16_t* __restrict__ coef,
                      uint8_t* __restrict__ plane, int wblk, int hblk, int pitch,
                      int first, int rep_top, int rep_bot, int* __restrict__ status) {
-  const int blk = blockIdx.x * 256 + threadIdx.x;
-  if (blk >= wblk * hblk) return;
-  idct_block_to_plane(cst, coef, plane, wblk, hblk, pitch, first, rep_top, rep_bot, status, blk);
+  __shared__ uint32_t lds_all[4][32 * QS_LDS_PITCH];
+  const int wave = threadIdx.x >> 6;
+  const int base = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 256 + wave * 64));
+  if (base >= wblk * hblk) return;                          // (wave-uniform; the waves of a workgroup share nothing)
+  idct_wave_to_plane(cst, coef, plane, wblk, hblk, pitch, first & 1, first & 2, rep_top, rep_bot, status, base, lds_all[wave]);
 }
-
-#include "qs_devfn.h"
 
 // pass A over a set of planes (whole planes, or bands whose halo-side apron rows are left alone)
 __global__ void __launch_bounds__(256)
 qs_idct_set_kernel(const QsPlaneSet set, int first) {
-  const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  __shared__ uint32_t lds_all[4][32 * QS_LDS_PITCH];
+  const int wave = threadIdx.x >> 6;
+  const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + wave));
   if (w >= set.wave0[set.n]) return;
   const int i = qs_set_find(set, w);
   const QsPlaneRef& r = set.ref[i];
-  const int blk = (w - set.wave0[i]) * 64 + (threadIdx.x & 63);
-  if (blk >= r.wblk * r.hblk) return;
-  idct_block_to_plane(r.cst, r.coef, r.plane, r.wblk, r.hblk, r.pitch, first,
-                      r.mode & QS_PLANE_REP_TOP, r.mode & QS_PLANE_REP_BOT, r.status, blk);
+  const int base = (w - set.wave0[i]) * 64;
+  if (base >= r.wblk * r.hblk) return;
+  idct_wave_to_plane(r.cst, r.coef, r.plane, r.wblk, r.hblk, r.pitch, first, r.mode & QS_PLANE_QUANT,
+                     r.mode & QS_PLANE_REP_TOP, r.mode & QS_PLANE_REP_BOT, r.status, base, lds_all[wave]);
 }
 
 // --------------------------------------------------------------------------
@@ -490,8 +517,9 @@ qs_dequant_kernel(const QsConsts* __restrict__ cst, int16_t* __restrict__ coef, 
 void qs_launch_idct_plane(const QsConsts* cst, int16_t* coef, uint8_t* plane, int wblk, int hblk,
                           int first, int rep_top, int rep_bot, int* status, hipStream_t s) {
   const int nblk = wblk * hblk;
+  const int f = first == 3 ? 3 : first ? 1 : 0;   // 3: first pass with deferred dequantisation (QS_HIP_FIRST_DEFER); any other non-zero value: first pass
   hipLaunchKernelGGL(qs_idct_plane_kernel, dim3((nblk + 255) / 256), dim3(256), 0, s,
-                     cst, coef, plane, wblk, hblk, qs_plane_pitch(wblk), first, rep_top, rep_bot, status);
+                     cst, coef, plane, wblk, hblk, qs_plane_pitch(wblk), f, rep_top, rep_bot, status);
 }
 
 // Which form of pass B a launch of `groups` 64-block groups gets.  Measured on MI355X

@@ -114,7 +114,8 @@ static int build_plane_set(const qs_hip_plane_ref* refs, uint8_t* const* next, i
       return qs_fail(QS_HIP_EINVAL, "%s: d_plane_next must be a different buffer (other blocks still read d_plane)", who);
     R.wblk = r.wblk; R.hblk = r.hblk; R.pitch = qs_plane_pitch(r.wblk);
     R.mode = ((!(flags & QS_NO_REBALANCE) && (r.luma || !(flags & QS_NO_REBALANCE_UV))) ? QS_PLANE_REBALANCE : 0) |
-             ((r.band & 1) ? 0 : QS_PLANE_REP_TOP) | ((r.band & 2) ? 0 : QS_PLANE_REP_BOT);
+             ((r.band & 1) ? 0 : QS_PLANE_REP_TOP) | ((r.band & 2) ? 0 : QS_PLANE_REP_BOT) |
+             ((r.band & QS_HIP_PLANE_DEFER) ? QS_PLANE_QUANT : 0);
   }
   for (int i = n; i < QS_MAX_PLANES + 2; ++i) set.wave0[i] = w;
   return QS_HIP_OK;

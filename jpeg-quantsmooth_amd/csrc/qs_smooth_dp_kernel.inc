@@ -55,6 +55,25 @@ QS_DP_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ coef,
 
   // ---- stage the 64 blocks (8 KiB contiguous), each wave its share of the eight 1 KiB slices
   uint4* gsrc = reinterpret_cast<uint4*>(coef) + (size_t)base * 8;
+#ifdef QS_DP_SET
+  // a plane whose coefficients are still quantised (QS_PLANE_QUANT, workgroup-uniform): dequantise on the way into LDS,
+  // see qs_smooth_kernel.inc
+  if (set.ref[pi].mode & QS_PLANE_QUANT) {
+    const int m0 = (lane & 7) * 4;
+    int q[8], unused = 0;
+    qs_load_qraw8(cst, lane & 7, q);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j % NW != wave) continue;
+      const int idx = j * 64 + lane;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (idx < nvec) v = gsrc[idx];
+      v = qs_dequant8<false>(v, q, unused);
+      uint32_t* dst = lds + m0 * QS_LDS_PITCH + (j * 8 + (lane >> 3));
+      dst[0] = v.x; dst[QS_LDS_PITCH] = v.y; dst[2 * QS_LDS_PITCH] = v.z; dst[3 * QS_LDS_PITCH] = v.w;
+    }
+  } else
+#endif
   {
     const int m0 = (lane & 7) * 4;
 #pragma unroll

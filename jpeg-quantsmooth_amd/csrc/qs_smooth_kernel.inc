@@ -64,6 +64,27 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
   // ---- stage the wave's 64 blocks (8 KiB contiguous): 16 B per lane per
   // load, fully coalesced, transposed through LDS into per-lane columns.
   uint4* gsrc = reinterpret_cast<uint4*>(coef) + (size_t)base * 8;
+#ifdef QS_SMOOTH_SET
+  // A plane whose dequantisation pass A deferred (QS_PLANE_QUANT, wave-uniform): the coefficients in HBM are still the
+  // file's quantised ones, and the products pass A formed and range-checked -- coef * qraw, wrapped to int16 -- are
+  // formed again here, each lane on the eighth of a block it moves, before they go to LDS.  From there on nothing
+  // differs, and the write-back below stores dequantised results as always.  A copy of the loop of its own, so that
+  // the staging of every other launch stays the code it was.
+  if (set.ref[pi].mode & QS_PLANE_QUANT) {
+    const int m0 = (lane & 7) * 4;
+    int q[8], unused = 0;
+    qs_load_qraw8(cst, lane & 7, q);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int idx = j * 64 + lane;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (idx < nvec) v = gsrc[idx];
+      v = qs_dequant8<false>(v, q, unused);
+      uint32_t* dst = lds + m0 * QS_LDS_PITCH + (j * 8 + (lane >> 3));
+      dst[0] = v.x; dst[QS_LDS_PITCH] = v.y; dst[2 * QS_LDS_PITCH] = v.z; dst[3 * QS_LDS_PITCH] = v.w;
+    }
+  } else
+#endif
   {
     const int m0 = (lane & 7) * 4;
 #pragma unroll

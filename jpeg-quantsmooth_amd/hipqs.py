@@ -590,7 +590,8 @@ class HipQS:
     @staticmethod
     def plane_refs(planes):
         """[(d_consts, d_coef, d_plane, d_status, wblk, hblk, luma[, band[, d_plane_next]])] -> PlaneRefs for the
-        *_planes calls; band: bit 0 / bit 1 = the top / bottom apron row is a halo row (a band of a sharded plane);
+        *_planes calls; band: bit 0 / bit 1 = the top / bottom apron row is a halo row (a band of a sharded plane), bit 2 =
+        QS_HIP_PLANE_DEFER (deferred dequantisation: the first pass A and the first smoothing launch only, see the header);
         d_plane_next: the plane the smoothing launch writes the next iteration's pixels into (None: none) -- these go
         into the parallel array of qs_hip_smooth_planes_next, the struct itself has no such field"""
         arr = (PlaneRef * len(planes))()
