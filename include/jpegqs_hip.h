@@ -345,6 +345,55 @@ int qs_hip_encode_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, con
 		qs_hip_encode_info *per_job, size_t *workspace_bytes);
 int qs_hip_encode_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_huff_tables *const *tables,
 		const qs_hip_encode_opts *const *opts, void *d_workspace, size_t bytes, void *stream);
+/* ---- device scan reader (the bytes of a JPEG scan with restart intervals -> device-resident coefficient arrays) ----
+ * What libjpeg 9 leaves in its coefficient arrays after jpeg_read_coefficients (jdhuff.c decode_mcu: the DC prediction
+ * runs as int and is stored as JCOEF, AC values by HUFF_EXTEND, de-zigzagged), for ONE sequential Huffman scan (SOF0 /
+ * SOF1, 8 bits) that carries all components of the frame in frame order.  One lane reads one restart interval: the
+ * reader is parallel over the intervals and over nothing else, so a file without DRI is read by a single lane.
+ * Jobs are qs_hip_job records over the DEVICE arrays to fill: coef[ci] with wblk as the row stride and wblk x hblk
+ * blocks, contiguous and 16-byte aligned; each must hold at least libjpeg's width_in_blocks x height_in_blocks
+ * (QS_HIP_EINVAL otherwise).  Quant tables and the colour space are not looked at.  More than 10 blocks in an MCU:
+ * QS_HIP_ENOTSUP.  An interval -- restart_interval MCUs, or the whole scan when that is 0 or at least the MCU count --
+ * of more than QS_HIP_READ_MAX_INTERVAL_BLOCKS blocks: QS_HIP_ENOTSUP from info, before anything is enqueued (the cap
+ * is one MCU row of the widest legal JPEG, 65 500 pixels at 4:4:4 = 24 564 blocks, rounded up; it bounds how long one
+ * lane runs).  The same three-call pattern:
+ *   info     per_job[i] and *workspace_bytes; no device touched;
+ *   prepare  geometry and derived code tables into the workspace; opts[i] is required: tables by DHT id 0..3 (a table
+ *            whose has_* byte is 0 is the Annex K.3 table for ids 0 / 1; a component that uses an id 2 / 3 without
+ *            one: QS_HIP_EINVAL), Td / Ta of each component, the DRI value; may synchronise `stream`, never inside a
+ *            capture;
+ *   run      ENQUEUES five kernel launches per QS_HIP_READ_CHUNK jobs on `stream`: no allocation, no synchronisation,
+ *            no copy (graph-capturable, a linear graph).  It must see the geometry prepare saw.
+ * d_scan[i]: device memory (any alignment) holding the file from the first byte behind the SOS header; scan_bytes[i]:
+ * how many bytes may be read there.  The kernels find the end themselves -- the first FF xx with xx not in {00,
+ * D0..D7}; EOI and anything behind it are ignored -- and look no further than the longest segment the geometry can have.
+ * Every block the scan codes is written if its position lies inside the caller's array: in an interleaved scan the
+ * dummy blocks of edge MCUs count as coded, as jdcoefct.c keeps them in libjpeg's own padded virtual arrays (so an
+ * array with wblk > width_in_blocks receives them); a one-component scan codes width_in_blocks x height_in_blocks
+ * blocks.  Every other block of the array is set to 0: the output is a function of the input alone.
+ * d_status[i] (device int32): 0 ok; 1 the number or order of the RSTn markers does not match the restart interval
+ * (marker k must be RST((k - 1) & 7)); 2 an interval ran out of bytes before its blocks were done, or had one or more
+ * whole bytes left over; 3 a bit pattern without a code, or a zero run that passes coefficient 63.  With a non-zero
+ * status the arrays' content is unspecified, every store lies inside them, and other jobs are unaffected.  Matching
+ * libjpeg's output on corrupt data (it warns and carries on) is not attempted. */
+#define QS_HIP_READ_CHUNK 32
+#define QS_HIP_READ_MAX_INTERVAL_BLOCKS 32768
+typedef struct {
+	qs_hip_huff_table dc[4], ac[4];
+	uint8_t has_dc[4], has_ac[4];                        /* 0: the standard table (ids 0 / 1 only) */
+	int32_t dc_tbl[QS_HIP_MAXC], ac_tbl[QS_HIP_MAXC];    /* Td / Ta of each component */
+	int32_t restart_interval;                            /* MCUs, from DRI; 0: none */
+} qs_hip_read_opts;
+typedef struct {
+	int32_t blocks_in_mcu, mcus, intervals;
+	int64_t blocks_per_interval;
+} qs_hip_read_info;
+int qs_hip_read_device_batch_info(qs_hip_job *const *jobs, int njobs, const qs_hip_read_opts *const *opts,
+		qs_hip_read_info *per_job, size_t *workspace_bytes);
+int qs_hip_read_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const qs_hip_read_opts *const *opts,
+		void *d_workspace, size_t bytes, void *stream);
+int qs_hip_read_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_scan, const uint64_t *scan_bytes,
+		int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
 /* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
  * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT. */
 int qs_hip_huff_optimal(const uint32_t freq[257], uint8_t bits[17], uint8_t huffval[256]);
@@ -369,7 +418,7 @@ const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
- * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder).  A caller built against
+ * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

@@ -1,0 +1,230 @@
+// qs_read_job.cpp -- the device scan reader of the flat C ABI (include/jpegqs_hip.h): qs_hip_read_device_batch_info /
+// _prepare / qs_hip_read_device_batch.  The entropy-coded segment of one sequential Huffman scan with restart intervals,
+// in device memory, into the coefficient arrays of qs_hip_job records: what libjpeg 9's jpeg_read_coefficients leaves
+// there, computed on the device (qs_kernels_read.hip, one lane per restart interval).
+//
+// Workspace: the QrJob descriptors of the batch (geometry, derived code tables), then per job its state, the marker
+// counts per 4 KiB of scan with their scan, and the interval offsets -- a function of the jobs' geometry and options
+// alone.  The segment's length is not known before the run: the arrays that depend on it are sized for the longest
+// segment the geometry can have, and the kernels look no further.
+#include "qs_common.h"
+#include "qs_read.h"
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+void qs_launch_read(const QrArgs& a, int zwgs, int mwgs, int dwgs, hipStream_t s);
+
+static_assert(QS_RD_CHUNK == QS_HIP_READ_CHUNK && QS_RD_MAX_INTERVAL_BLOCKS == QS_HIP_READ_MAX_INTERVAL_BLOCKS,
+              "include/jpegqs_hip.h and qs_read.h disagree");
+
+namespace {
+
+int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QrJob), 256); }
+
+struct Who {
+  char s[96];
+  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
+};
+
+// geometry, tables and intervals of one job; the code tables themselves only when `tables`
+int describe(const qs_hip_job* job, const qs_hip_read_opts* o, bool tables, QrJob* D, qs_hip_read_info* info,
+             const char* who) {
+  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
+  if (!o) return qs_fail(QS_HIP_EINVAL, "%s: no options (the tables of each component and the restart interval)", who);
+  const int n = job->ncomp;
+  memset(D, 0, sizeof *D);
+  if (int rc = qr_geometry(n, job->image_width, job->image_height, job->hsamp, job->vsamp, job->wblk, job->hblk, &D->g)) {
+    if (rc == 2) return qs_fail(QS_HIP_ENOTSUP, "%s: more than 10 blocks in an MCU; libjpeg takes at most 10", who);
+    return qs_fail(QS_HIP_EINVAL, "%s: a %d x %d image needs sampling factors 1..4 and, per component, at least libjpeg's "
+                   "width_in_blocks x height_in_blocks blocks", who, job->image_width, job->image_height);
+  }
+  if (o->restart_interval < 0 || o->restart_interval > 65535)
+    return qs_fail(QS_HIP_EINVAL, "%s: restart_interval %d (0 .. 65535)", who, o->restart_interval);
+  qr_intervals(D->g, o->restart_interval, &D->ri, &D->intervals);
+  const long long per = (long long)D->ri * D->g.bpm;
+  if (per > QS_RD_MAX_INTERVAL_BLOCKS)
+    return qs_fail(QS_HIP_ENOTSUP, "%s: %lld blocks in a restart interval (restart_interval %d, %d MCUs); one lane reads "
+                   "an interval, of at most %d blocks", who, per, o->restart_interval, D->g.mcus, QS_RD_MAX_INTERVAL_BLOCKS);
+  for (int c = 0; c < n; ++c) {
+    const int td = o->dc_tbl[c], ta = o->ac_tbl[c];
+    if (td < 0 || td > 3 || ta < 0 || ta > 3)
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d names tables %d / %d (0 .. 3)", who, c, td, ta);
+    if ((td > 1 && !o->has_dc[td]) || (ta > 1 && !o->has_ac[ta]))
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d uses a table the options do not hold (only 0 and 1 have a "
+                     "standard table)", who, c);
+    D->dc_tbl[c] = td;
+    D->ac_tbl[c] = ta;
+    if ((long long)job->wblk[c] * job->hblk[c] > 0x7fffffffLL)
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d has more than 2^31 blocks", who, c);
+  }
+  if (tables) {
+    for (int t = 0; t < 8; ++t) {
+      const bool ac = t >= 4;
+      const int id = t & 3;
+      bool used = false;
+      for (int c = 0; c < n; ++c) used |= (ac ? D->ac_tbl[c] : D->dc_tbl[c]) == id;
+      if (!used) continue;                                          // (stays all zero: never looked at)
+      qs_hip_huff_table tb;
+      if (ac ? o->has_ac[id] : o->has_dc[id]) tb = ac ? o->ac[id] : o->dc[id];
+      else if (int rc = qs_hip_huff_standard(ac, id, tb.bits, tb.huffval)) return rc;
+      if (qr_build_table(tb.bits, tb.huffval, !ac, &D->tab[t]))
+        return qs_fail(QS_HIP_EINVAL, "%s: %s table %d is not a valid Huffman table", who, ac ? "AC" : "DC", id);
+    }
+  }
+  D->max_scan = qr_max_scan(D->g, D->intervals);
+  if (info) {
+    info->blocks_in_mcu = D->g.bpm;
+    info->mcus = D->g.mcus;
+    info->intervals = D->intervals;
+    info->blocks_per_interval = per;
+  }
+  return QS_HIP_OK;
+}
+
+int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_read_opts* const* opts, bool tables,
+                 std::vector<QrJob>& D, qs_hip_read_info* info, uint64_t* total, const char* who) {
+  if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
+  if (!opts) return qs_fail(QS_HIP_EINVAL, "%s: null opts", who);
+  D.assign((size_t)njobs, QrJob());
+  uint64_t off = descriptors_bytes(njobs);
+  for (int i = 0; i < njobs; ++i) {
+    if (int r = describe(jobs[i], opts[i], tables, &D[(size_t)i], info ? &info[i] : nullptr, Who(who, i).s)) return r;
+    QrJob& J = D[(size_t)i];
+    long long blocks = 0;
+    for (int c = 0; c < J.g.ncomp; ++c) blocks += (long long)jobs[i]->wblk[c] * jobs[i]->hblk[c];
+    J.nzwg = qr_zero_wgs(blocks);
+    const uint64_t chunks = (J.max_scan + 32) / QS_RD_MCHUNK + 2;
+    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += align_up(bytes, 256); return at; };
+    J.off_state = take(sizeof(QrState));
+    J.off_cnt = take(chunks * 4);
+    J.off_off = take(chunks * 4);
+    J.off_p = take(((uint64_t)J.intervals + 1) * 8);
+  }
+  *total = off;
+  return QS_HIP_OK;
+}
+
+int check_ws(uint64_t need, const void* d_workspace, size_t bytes, const char* who) {
+  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < need)
+    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %llu", who, bytes,
+                   (unsigned long long)need);
+  return QS_HIP_OK;
+}
+
+int device_ok() {
+  if (qs_hip_device_count() <= 0)
+    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+  return QS_HIP_OK;
+}
+
+template <class F> int guarded(F f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
+  } catch (...) {
+    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
+  }
+}
+
+}  // namespace
+
+extern "C" int qs_hip_read_device_batch_info(qs_hip_job* const* jobs, int njobs, const qs_hip_read_opts* const* opts,
+                                             qs_hip_read_info* per_job, size_t* bytes) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_read_device_batch_info";
+    if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
+    std::vector<QrJob> D;
+    uint64_t total = 0;
+    if (int r = describe_all(jobs, njobs, opts, false, D, per_job, &total, who)) return r;
+    *bytes = (size_t)total;
+    return QS_HIP_OK;
+  });
+}
+
+extern "C" int qs_hip_read_device_batch_prepare(qs_hip_job* const* jobs, int njobs, const qs_hip_read_opts* const* opts,
+                                                void* d_workspace, size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_read_device_batch_prepare";
+    std::vector<QrJob> D;
+    uint64_t total = 0;
+    if (int r = describe_all(jobs, njobs, opts, true, D, nullptr, &total, who)) return r;
+    if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+    if (int r = device_ok()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QrJob), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
+    return QS_HIP_OK;
+  });
+}
+
+// The run sees no options, and reads nothing back from the workspace: the launch sizes that depend on the restart
+// interval are bounded from the geometry instead (intervals <= MCUs).  A marker workgroup behind the descriptor's own
+// clamp of the scan and a decode workgroup behind the job's intervals return at once.
+extern "C" int qs_hip_read_device_batch(qs_hip_job* const* jobs, int njobs, const uint8_t* const* d_scan,
+                                        const uint64_t* scan_bytes, int32_t* d_status, void* d_workspace, size_t bytes,
+                                        void* stream) {
+  return guarded([&]() -> int {
+    const char* who = "qs_hip_read_device_batch";
+    if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
+    if (!d_scan || !scan_bytes || !d_status) return qs_fail(QS_HIP_EINVAL, "%s: null argument", who);
+    if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < descriptors_bytes(njobs))
+      return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned): not what prepare was given", who, bytes);
+    if (int r = device_ok()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int j0 = 0; j0 < njobs; j0 += QS_RD_CHUNK) {
+      QrArgs a;
+      memset(&a, 0, sizeof a);
+      a.jobs = static_cast<const QrJob*>(d_workspace) + j0;
+      a.ws = static_cast<uint8_t*>(d_workspace);
+      a.d_status = d_status;
+      a.job0 = j0;
+      a.n = std::min(QS_RD_CHUNK, njobs - j0);
+      long long zwgs = 0, mwgs = 0, dwgs = 0;
+      for (int k = 0; k < a.n; ++k) {
+        const qs_hip_job* job = jobs[j0 + k];
+        const Who w(who, j0 + k);
+        if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", w.s);
+        if (!d_scan[j0 + k]) return qs_fail(QS_HIP_EINVAL, "%s: no scan bytes", w.s);
+        QsEncGeom g;
+        if (int rc = qr_geometry(job->ncomp, job->image_width, job->image_height, job->hsamp, job->vsamp, job->wblk,
+                                 job->hblk, &g))
+          return qs_fail(rc == 2 ? QS_HIP_ENOTSUP : QS_HIP_EINVAL, "%s: not the geometry prepare saw", w.s);
+        long long blocks = 0;
+        QrPtrs& P = a.p[k];
+        for (int c = 0; c < job->ncomp; ++c) {
+          int16_t* arr = job->coef[c];
+          if (!arr || (reinterpret_cast<uintptr_t>(arr) & 15))
+            return qs_fail(QS_HIP_EINVAL, "%s: component %d has no data or is not 16-byte aligned", w.s, c);
+          if ((long long)job->wblk[c] * job->hblk[c] > 0x7fffffffLL)
+            return qs_fail(QS_HIP_EINVAL, "%s: component %d has more than 2^31 blocks", w.s, c);
+          P.coef[c] = arr;
+          P.nblk[c] = job->wblk[c] * job->hblk[c];
+          blocks += P.nblk[c];
+        }
+        P.scan = d_scan[j0 + k];
+        P.scan_bytes = scan_bytes[j0 + k];
+        a.zwg0[k] = (int)zwgs;
+        zwgs += qr_zero_wgs(blocks);                              // (the descriptor's nzwg: the same function)
+        // the marker launches: a workgroup per 4 KiB of aligned memory the scan touches, no further than the longest
+        // segment of the geometry (the intervals are at most the MCUs: an upper bound is all the clamp needs here; the
+        // kernels clamp with the descriptor's exact value and leave the units behind it alone)
+        const uint64_t n = std::min<uint64_t>(P.scan_bytes, qr_max_scan(g, g.mcus));
+        const uint64_t units = ((reinterpret_cast<uintptr_t>(P.scan) & 15) + n + 15) / 16;
+        a.mwg0[k] = (int)mwgs;
+        mwgs += (long long)((units + QS_RD_WG - 1) / QS_RD_WG);
+        a.dwg0[k] = (int)dwgs;
+        dwgs += ceil_div(g.mcus, QS_RD_DWG);
+        if (mwgs > 0x7fffffffLL || dwgs > 0x7fffffffLL)
+          return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
+      }
+      qs_launch_read(a, (int)zwgs, (int)mwgs, (int)dwgs, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return QS_HIP_OK;
+  });
+}

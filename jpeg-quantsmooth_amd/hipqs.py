@@ -111,6 +111,19 @@ class EncodeOpts(C.Structure):
     _fields_ = [("restart_interval", C.c_int32), ("restart_in_rows", C.c_int32)]
 
 
+class ReadOpts(C.Structure):
+    """qs_hip_read_opts: the Huffman tables of a file by DHT id (has_* 0: the standard table, ids 0 / 1), Td / Ta of each
+    component and the DRI value"""
+    _fields_ = [("dc", HuffTable * 4), ("ac", HuffTable * 4), ("has_dc", C.c_uint8 * 4), ("has_ac", C.c_uint8 * 4),
+                ("dc_tbl", C.c_int32 * MAXC), ("ac_tbl", C.c_int32 * MAXC), ("restart_interval", C.c_int32)]
+
+
+class ReadInfo(C.Structure):
+    """qs_hip_read_info: one job of the device scan reader (qs_hip_read_device_batch_info)"""
+    _fields_ = [("blocks_in_mcu", C.c_int32), ("mcus", C.c_int32), ("intervals", C.c_int32),
+                ("blocks_per_interval", C.c_int64)]
+
+
 MAX_PLANES = 56
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -161,6 +174,12 @@ ABI = {
                                                            C.POINTER(C.POINTER(HuffTables)),
                                                            C.POINTER(C.POINTER(EncodeOpts)), C.c_void_p, C.c_size_t,
                                                            C.c_void_p]),
+    "qs_hip_read_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
+                                                 C.POINTER(ReadInfo), C.POINTER(C.c_size_t)]),
+    "qs_hip_read_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
+                                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_read_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_huff_optimal": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_huff_standard": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_free": (None, [C.c_void_p]),
@@ -557,6 +576,54 @@ class HipQS:
         """qs_hip_encode_device_batch_histogram: symbol counts uint32[njobs][4][257] (DC 0, DC 1, AC 0, AC 1)"""
         self._check(self.lib.qs_hip_encode_device_batch_histogram(self._job_ptrs(jobs), len(jobs), d_stop, d_counts,
                                                                   d_status, d_workspace, nbytes, stream))
+
+    # -- device scan reader (a list of device_job() Jobs over the arrays to fill) ---------
+    @staticmethod
+    def read_opts(dc=None, ac=None, dc_tbl=(), ac_tbl=(), restart_interval=0) -> ReadOpts:
+        """a qs_hip_read_opts: dc / ac = {DHT id 0..3: (bits[17], huffval)} (a table left out is the standard one),
+        dc_tbl / ac_tbl = Td / Ta of each component, restart_interval = the DRI value"""
+        o = ReadOpts()
+        for tabs, arr, has in ((dc or {}, o.dc, o.has_dc), (ac or {}, o.ac, o.has_ac)):
+            for k, (bits, vals) in tabs.items():
+                if k not in (0, 1, 2, 3) or len(bits) != 17 or len(vals) > 256:
+                    raise ValueError("read_opts: table 0..3, bits[17], at most 256 symbols")
+                arr[k].bits[:] = [int(b) for b in bits]
+                for i, v in enumerate(vals):
+                    arr[k].huffval[i] = int(v)
+                has[k] = 1
+        for ci, (td, ta) in enumerate(zip(dc_tbl, ac_tbl)):
+            o.dc_tbl[ci], o.ac_tbl[ci] = int(td), int(ta)
+        o.restart_interval = int(restart_interval)
+        return o
+
+    @staticmethod
+    def _read_opt_ptrs(opts, n):
+        if len(opts) != n:
+            raise ValueError("one ReadOpts per job")
+        return (C.POINTER(ReadOpts) * max(1, n))(*[None if o is None else C.pointer(o) for o in opts])
+
+    def read_batch_info(self, jobs, opts):
+        """qs_hip_read_device_batch_info (no device needed) -> (list of dict(blocks_in_mcu, mcus, intervals,
+        blocks_per_interval), the batch's workspace bytes)"""
+        per = (ReadInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_read_device_batch_info(self._job_ptrs(jobs), len(jobs), self._read_opt_ptrs(opts, len(jobs)),
+                                                           per, C.byref(total)))
+        return [{f: int(getattr(per[i], f)) for f, _ in ReadInfo._fields_} for i in range(len(jobs))], int(total.value)
+
+    def read_batch_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_read_device_batch_prepare: geometry and derived code tables into the workspace (synchronises `stream`;
+        not inside a capture)"""
+        self._check(self.lib.qs_hip_read_device_batch_prepare(self._job_ptrs(jobs), len(jobs),
+                                                              self._read_opt_ptrs(opts, len(jobs)), d_workspace, nbytes, stream))
+
+    def read_batch(self, jobs, d_scan, scan_bytes, d_status: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_read_device_batch: enqueue the scan reader of every job; d_scan[i] = device address of job i's bytes
+        behind the SOS header, scan_bytes[i] = how many may be read, d_status = device int32[njobs]"""
+        scans = (C.c_void_p * max(1, len(d_scan)))(*d_scan)
+        lens = (C.c_uint64 * max(1, len(scan_bytes)))(*[int(v) for v in scan_bytes])
+        self._check(self.lib.qs_hip_read_device_batch(self._job_ptrs(jobs), len(jobs), scans, lens, d_status, d_workspace,
+                                                      nbytes, stream))
 
     def huff_optimal(self, freq):
         """qs_hip_huff_optimal (host only): symbol counts (256 or 257) -> (bits[17], huffval) as libjpeg's

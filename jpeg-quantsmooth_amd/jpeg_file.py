@@ -3,6 +3,9 @@ object after jpeg_write_coefficients (jcmarker.c): SOI, JFIF APP0 or Adobe APP14
 when a quantiser exceeds 8 bits), one DHT per table the scan uses, DRI when the scan has a restart interval, SOS, the
 segment, EOI.  Host only, no device.
 
+parse() is compose()'s inverse: the markers in front of one sequential Huffman scan, for the device scan reader
+(qs_hip_read_device_batch).
+
 Conventions of the library's encoder (include/jpegqs_hip.h): component ci uses quant table ci and the Huffman tables
 jpeg_set_colorspace assigns.  Extra markers of a source file (jcopy_markers) are not written."""
 from __future__ import annotations
@@ -81,3 +84,151 @@ def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, d
     out.append(bytes(segment))
     out.append(b"\xff\xd9")
     return b"".join(out)
+
+
+# ---- the inverse: the markers of a file in front of its one scan ----------------------------------------------------------
+
+_SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)",
+              0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding (SOF10)", 0xCB: "arithmetic coding (SOF11)",
+              0xCD: "arithmetic coding (SOF13)", 0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
+_MARKER_NAMES = {0xC4: "DHT", 0xDB: "DQT", 0xDA: "SOS (a second scan)", 0xDC: "DNL", 0xDD: "DRI", 0xCC: "DAC"}
+
+
+def _colorspace(ids, jfif, adobe):
+    """jdapimin.c default_decompress_parms of libjpeg 9: component ids first, then JFIF, then Adobe's transform"""
+    n = len(ids)
+    if n == 1:
+        return 1
+    if n == 3:
+        known = {(0x01, 0x02, 0x03): 3, (0x01, 0x22, 0x23): 7, (0x52, 0x47, 0x42): 2, (0x72, 0x67, 0x62): 6}
+        if tuple(ids) in known:
+            return known[tuple(ids)]
+        if jfif:
+            return 3
+        if adobe is not None:
+            return 2 if adobe == 0 else 3
+        return 3
+    if n == 4:
+        if adobe is not None:
+            return 4 if adobe == 0 else 5
+        return 4
+    return 0
+
+
+def parse(data, header_only: bool = False) -> dict:
+    """The markers of a JPEG file up to its scan -> dict(image_size, colorspace, hsamp, vsamp, quants (natural order, one
+    per component by its Tq), dc / ac ({DHT id: (bits[17], huffval)}), dc_tbl / ac_tbl (Td / Ta of each component),
+    restart_interval (DRI, 0 if absent), scan_offset (the first byte behind the SOS header), sof (0xC0 / 0xC1),
+    component_ids).  Looks at markers only, never at the entropy-coded bytes.
+
+    Accepted: SOF0 or SOF1, 8 bits, Huffman, exactly one scan that carries all components of the frame in frame order
+    with Ss = 0, Se = 63, Ah = Al = 0.  Everything else raises ValueError naming what it met: SOF2 and up, arithmetic
+    coding, 12 bits, more than one scan, a DHT or DQT between scans, a DNL.  header_only: `data` may end anywhere behind
+    the SOS header (what follows the scan is then not looked at)."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("parse: no SOI at the start")
+    pos, qt, dc, ac, dri, frame, jfif, adobe = 2, {}, {}, {}, 0, None, False, None
+    while True:
+        while pos < len(data) and data[pos] == 0xFF and pos + 1 < len(data) and data[pos + 1] == 0xFF:
+            pos += 1                                                   # fill bytes
+        if pos + 4 > len(data):
+            raise ValueError("parse: the data ends in front of SOS")
+        if data[pos] != 0xFF:
+            raise ValueError(f"parse: marker expected at byte {pos}")
+        code = data[pos + 1]
+        if code == 0xD9:
+            raise ValueError("parse: EOI in front of any scan")
+        if code == 0x01 or 0xD0 <= code <= 0xD7:
+            pos += 2
+            continue
+        n = struct.unpack_from(">H", data, pos + 2)[0]
+        if n < 2 or pos + 2 + n > len(data):
+            raise ValueError(f"parse: marker FF{code:02X} at byte {pos} runs past the data")
+        body = data[pos + 4:pos + 2 + n]
+        pos += 2 + n
+        if code in _SOF_NAMES:
+            raise ValueError(f"parse: {_SOF_NAMES[code]}: only baseline and extended sequential Huffman (SOF0, SOF1)")
+        if code == 0xCC:
+            raise ValueError("parse: arithmetic coding (DAC)")
+        if code == 0xDC:
+            raise ValueError("parse: DNL")
+        if code in (0xC0, 0xC1):
+            if frame is not None:
+                raise ValueError("parse: a second SOF")
+            prec, h, w, nc = struct.unpack_from(">BHHB", body, 0)
+            if prec != 8:
+                raise ValueError(f"parse: {prec}-bit samples: only 8")
+            if h == 0:
+                raise ValueError("parse: height 0 (DNL)")
+            if not 1 <= nc <= 4 or len(body) != 6 + 3 * nc:
+                raise ValueError(f"parse: {nc} components in the frame")
+            comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nc)]
+            frame = dict(sof=code, image_size=(w, h), comps=comps)
+        elif code == 0xDB:
+            p = 0
+            while p < len(body):
+                prec, idx = body[p] >> 4, body[p] & 15
+                if prec > 1 or idx > 3 or p + 1 + 64 * (prec + 1) > len(body):
+                    raise ValueError("parse: bad DQT")
+                vals = struct.unpack_from(">64H" if prec else "64B", body, p + 1)
+                q = np.zeros(64, np.uint16)
+                q[ZIGZAG] = vals
+                qt[idx] = q
+                p += 1 + 64 * (prec + 1)
+        elif code == 0xC4:
+            p = 0
+            while p < len(body):
+                if p + 17 > len(body):
+                    raise ValueError("parse: bad DHT")
+                idx = body[p]
+                bits = [0] + list(body[p + 1:p + 17])
+                cnt = sum(bits)
+                if (idx & 0xEF) > 3 or cnt > 256 or p + 17 + cnt > len(body):
+                    raise ValueError("parse: bad DHT")
+                (ac if idx & 0x10 else dc)[idx & 15] = (bits, list(body[p + 17:p + 17 + cnt]))
+                p += 17 + cnt
+        elif code == 0xDD:
+            dri = struct.unpack(">H", body)[0]
+        elif code == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif code == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif code == 0xDA:
+            if frame is None:
+                raise ValueError("parse: SOS in front of SOF")
+            comps = frame["comps"]
+            ns = body[0]
+            if len(body) != 4 + 2 * ns:
+                raise ValueError("parse: bad SOS")
+            sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(ns)]
+            if [c for c, _d, _a in sel] != [c[0] for c in comps]:
+                raise ValueError(f"parse: the scan carries components {[c for c, _d, _a in sel]} of the frame's "
+                                 f"{[c[0] for c in comps]}: more than one scan")
+            ss, se, ahal = body[1 + 2 * ns:4 + 2 * ns]
+            if (ss, se, ahal) != (0, 63, 0):
+                raise ValueError(f"parse: Ss {ss} Se {se} Ah/Al {ahal:#04x}: not a sequential scan")
+            break
+    for _c, _h, _v, tq in comps:
+        if tq not in qt:
+            raise ValueError(f"parse: quantisation table {tq} is used but not defined")
+    for _c, td, ta in sel:
+        if td not in dc or ta not in ac:
+            raise ValueError(f"parse: Huffman table DC {td} / AC {ta} is used but not defined")
+    if not header_only:
+        # behind the scan: the next marker that is not RSTn must be EOI (markers only: the bytes between are not decoded)
+        end = pos
+        while end + 1 < len(data) and not (data[end] == 0xFF and data[end + 1] != 0 and not 0xD0 <= data[end + 1] <= 0xD7):
+            end = data.find(b"\xff", end + 1)
+            if end < 0:
+                end = len(data)
+        if end + 1 < len(data) and data[end + 1] != 0xD9:
+            code = data[end + 1]
+            raise ValueError(f"parse: {_MARKER_NAMES.get(code, f'marker FF{code:02X}')} behind the first scan: more than "
+                             f"one scan, or tables between scans")
+    ids = [c[0] for c in comps]
+    return dict(image_size=frame["image_size"], colorspace=_colorspace(ids, jfif, adobe), hsamp=[c[1] for c in comps],
+                vsamp=[c[2] for c in comps], quants=[qt[c[3]].copy() for c in comps], dc=dc, ac=ac,
+                dc_tbl=[d for _c, d, _a in sel], ac_tbl=[a for _c, _d, a in sel], restart_interval=int(dri),
+                scan_offset=pos, sof=frame["sof"], component_ids=ids)

@@ -25,6 +25,11 @@ decodes coefficient tensors to pixels on the device (qs_hip_decode_device_batch)
 
 entropy-codes them on the device (qs_hip_encode_device_batch); encode_scan leaves the segment in device memory.
 
+    im = torch_qs.read(data)          # data: the bytes of a JPEG file with restart intervals, on the host or the device
+
+reads a file's scan into device coefficient tensors (qs_hip_read_device_batch, one lane per restart interval): the image
+dict the three calls above take.
+
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
@@ -48,6 +53,7 @@ class Workspace:
 
     def __init__(self, buf=None, key=None):
         self.buf, self.key = buf, key
+        self.headers = None          # read_batch: the parsed headers of the files it was prepared with
 
     @property
     def nbytes(self) -> int:
@@ -564,3 +570,135 @@ def encode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
                               image_size=image_size)],
                         result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
                         huffman=huffman, restart_interval=restart_interval, restart_in_rows=restart_in_rows)[0]
+
+
+# ---- reading a scan into coefficient tensors (qs_hip_read_device_batch) -----------------------------------------------------
+
+_HEADER_BYTES = 1 << 16          # what read() copies to the host at first to find the SOS header (doubled while short)
+
+
+def _read_header(data, torch, who):
+    """the parsed markers (jpeg_file.parse) of a file given as bytes or as a uint8 tensor: only its first bytes are
+    looked at, and only they are copied when the tensor is on the device"""
+    from . import jpeg_file
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return jpeg_file.parse(bytes(data), header_only=True)
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError(f"{who}: a file is bytes or a contiguous one-dimensional uint8 tensor")
+    n = _HEADER_BYTES
+    while True:
+        try:
+            return jpeg_file.parse(data[:n].cpu().numpy().tobytes(), header_only=True)
+        except ValueError:
+            if n >= data.numel():
+                raise
+            n *= 2
+
+
+def _huffman_of(p):
+    """the file's tables as encode(huffman=...) takes them, when every component uses DC and AC table Td == Ta in {0, 1}"""
+    if any(td != ta or td not in (0, 1) for td, ta in zip(p["dc_tbl"], p["ac_tbl"])):
+        return None
+    used = sorted(set(p["dc_tbl"]))
+    return dict(dc={t: p["dc"][t] for t in used}, ac={t: p["ac"][t] for t in used})
+
+
+def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=None) -> dict:
+    """Read the scans of JPEG files into device coefficient tensors on the current stream: what libjpeg 9's
+    jpeg_read_coefficients leaves in its arrays.  One lane reads one restart interval, so files with a small restart
+    interval (this package's encode(restart_interval=...), jpegtran -restart) are the workload; a file without DRI is
+    read by a single lane, and refused when it has more than 32 768 blocks.  Baseline or extended sequential Huffman,
+    8 bits, one scan over all components (jpeg_file.parse raises ValueError for anything else).
+
+    datas[i]: bytes, or a one-dimensional uint8 tensor on the host or the device.  Only the header -- the first bytes, up
+    to the SOS marker -- is parsed on the host; bytes and host tensors are uploaded whole, device tensors are read where
+    they lie.  outs[i]: preallocated contiguous int16 tensors (hblk, wblk, 64) per component, at least libjpeg's
+    width_in_blocks x height_in_blocks (blocks outside the scan are zeroed).  workspace: as decode_batch; it also keeps
+    the parsed headers: inside a graph capture nothing is copied to the host, the files must be device tensors and have
+    the headers of the files the workspace was prepared with (the same sizes, tables and offsets; the scan bytes and
+    what lies behind them may differ).  device: where to read when every file is on the host (default: the current one).
+    Returns dict(images, status, workspace): images[i] is the dict quantsmooth_batch_, decode_batch and encode_batch take
+    -- coefs, quants, hsamp, vsamp, colorspace, image_size -- with huffman (the file's tables in the form
+    encode(huffman=...) takes, or None when a component's Td != Ta or a table id above 1 is used), restart_interval and
+    status (a view of one element of `status`, the int32 tensor of the batch: 0 ok, 1 RSTn markers that do not match the
+    interval, 2 an interval with too few or too many bytes, 3 bits without a code; the arrays are then unspecified)."""
+    return _read_batch(datas, outs, workspace, device, "read_batch")
+
+
+def _read_batch(datas, outs, workspace, device, who):
+    import torch
+    if not isinstance(datas, (list, tuple)) or not datas:
+        raise ValueError(f"{who}: datas must be a non-empty list of files")
+    if outs is not None and len(outs) != len(datas):
+        raise ValueError(f"{who}: one output list (or None) per file")
+    capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        if workspace is None or getattr(workspace, "headers", None) is None or len(workspace.headers) != len(datas):
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on files with "
+                               f"the same headers (workspace=...): parsing a header copies it to the host")
+        if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
+            raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
+        headers = workspace.headers
+    else:
+        headers = [_read_header(d, torch, f"{who}: file {i}") for i, d in enumerate(datas)]
+    dev = next((d.device for d in datas if isinstance(d, torch.Tensor) and d.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    hip = _hip()
+    bufs, jobs, opts, images = [], [], [], []
+    for i, (d, p) in enumerate(zip(datas, headers)):
+        if isinstance(d, torch.Tensor):
+            if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_contiguous():
+                raise TypeError(f"{who}: file {i} must be a contiguous one-dimensional uint8 tensor")
+            if d.is_cuda and d.device != dev:
+                raise ValueError(f"{who}: file {i} is on {d.device}, the batch on {dev}")
+            buf = d if d.is_cuda else d.to(dev, non_blocking=True)
+        else:
+            buf = torch.frombuffer(bytearray(d), dtype=torch.uint8).to(dev)
+        if buf.numel() <= p["scan_offset"]:
+            raise ValueError(f"{who}: file {i} ends with its SOS header")
+        bufs.append(buf)
+        n = len(p["hsamp"])
+        w, h = p["image_size"]
+        mh, mv = max(p["hsamp"]), max(p["vsamp"])
+        shapes = [(-(-h * p["vsamp"][ci] // (8 * mv)), -(-w * p["hsamp"][ci] // (8 * mh))) for ci in range(n)]
+        if outs is None or outs[i] is None:
+            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
+        else:
+            coefs = list(outs[i])
+            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
+                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
+        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], [None] * n,
+                                   hsamp=p["hsamp"], vsamp=p["vsamp"], colorspace=p["colorspace"] or 1, image_size=(w, h)))
+        opts.append(hip.read_opts(p["dc"], p["ac"], p["dc_tbl"], p["ac_tbl"], p["restart_interval"]))
+        images.append(dict(coefs=coefs, quants=[q.copy() for q in p["quants"]], hsamp=list(p["hsamp"]),
+                           vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), huffman=_huffman_of(p),
+                           restart_interval=p["restart_interval"]))
+    _per, total = hip.read_batch_info(jobs, opts)
+    key = ("read",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o) for o in opts)
+    if workspace is None:
+        workspace = Workspace()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if workspace.key != key:
+        if capturing:
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
+                               f"geometry and tables (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.read_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream)
+        workspace.key = key
+    workspace.headers = headers
+    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    hip.read_batch(jobs, [b.data_ptr() + p["scan_offset"] for b, p in zip(bufs, headers)],
+                   [b.numel() - p["scan_offset"] for b, p in zip(bufs, headers)], status.data_ptr(), workspace.buf.data_ptr(),
+                   workspace.nbytes, stream)
+    for i, im in enumerate(images):
+        im["status"] = status[i:i + 1]
+    return dict(images=images, status=status, workspace=workspace)
+
+
+def read(data, *, out=None, workspace: Workspace | None = None, device=None) -> dict:
+    """read_batch on one file -> its image dict (coefs, quants, hsamp, vsamp, colorspace, image_size, huffman,
+    restart_interval, status) with the workspace used under `workspace`"""
+    r = _read_batch([data], None if out is None else [out], workspace, device, "read")
+    return dict(r["images"][0], workspace=r["workspace"])

@@ -22,8 +22,14 @@ coefficient arrays to the host (a lower bound of that route by itself) plus libj
 core (tests/libjpeg9_encode.c on a staged input file: its time includes reading the arrays and writing the file).
 Medians of --repeats windows; exits non-zero unless the device route gives libjpeg's bytes and beats the copy alone.
 
+--read times the device scan reader (torch_qs.read_batch) on the same three cases, on files the device coder wrote with
+--restart N / --restart-rows N: the upload of the file from pinned memory plus the read, and the read alone, next to the
+host route it replaces -- libjpeg 9's jpeg_read_coefficients on one core (tests/libjpeg9_decode.c read: its time
+includes writing the arrays to a file) plus the pinned upload of the coefficient arrays.  Parallelism is the number of
+restart intervals: the lanes of each case are reported.  Exits non-zero unless the arrays are the ones encoded.
+
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode]"""
+                                       [--decode | --encode | --read] [--restart N | --restart-rows N]"""
 import argparse
 import json
 import sys
@@ -49,7 +55,10 @@ def main():
                     help="--encode: write a restart marker every N MCUs (libjpeg's restart_interval)")
     ap.add_argument("--restart-rows", type=int, default=None, metavar="N",
                     help="--encode: write a restart marker every N MCU rows (libjpeg's restart_in_rows)")
+    ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     a = ap.parse_args()
+    if a.read:
+        return bench_read(a)
     if a.decode:
         return bench_decode(a)
     if a.encode:
@@ -310,6 +319,102 @@ def bench_encode(a):
     if bad:                                                         # the bound of DESIGN.md section 13
         raise SystemExit(f"bench_device_batch --encode: {bad}: the device route must give libjpeg's bytes and be faster "
                          f"than the copy of the coefficient arrays alone")
+
+
+def bench_read(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import LibJpeg9, synth_image
+    if not (a.restart or a.restart_rows):
+        raise SystemExit("bench_device_batch --read: give --restart N or --restart-rows N (one lane reads one interval)")
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows)
+    pkg = jpegqs_pkg.load()
+    torch_qs = pkg.torch_qs
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1, amp=30)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
+             (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
+    out = dict(tool="bench_device_batch", leg="read", device=torch.cuda.get_device_name(dev), restart=rst, results=[])
+    for name, ims in cases:
+        im = ims[0]
+        coefs = [torch.from_numpy(c).to(dev) for c in im["coefs"]]
+        data = torch_qs.encode(coefs, im["quants"], hsamp=im["hsamp"], vsamp=im["vsamp"], colorspace=im["colorspace"],
+                               image_size=im["image_size"], **rst)
+        pinned = [torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory() for _ in ims]
+        on_dev = [p.to(dev) for p in pinned]
+        ws = torch_qs.Workspace()
+        r = torch_qs.read_batch(on_dev, workspace=ws)
+        outs = [x["coefs"] for x in r["images"]]
+        status = r["status"].cpu().tolist()
+        identical = status == [0] * len(ims) and all(torch.equal(g, c) for o in outs for g, c in zip(o, coefs))
+        header = pkg.jpeg_file.parse(data, header_only=True)
+        per, _ = pkg.HipQS().read_batch_info(
+            [pkg.HipQS.device_job([1] * len(coefs), [tuple(c.shape[:2]) for c in coefs], [None] * len(coefs), hsamp=im["hsamp"],
+                                  vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"])],
+            [pkg.HipQS.read_opts(header["dc"], header["ac"], header["dc_tbl"], header["ac_tbl"], header["restart_interval"])])
+
+        def device_route():
+            up = [p.to(dev, non_blocking=True) for p in pinned]
+            torch_qs.read_batch(up, outs=outs, workspace=ws)
+            torch.cuda.synchronize()
+
+        def kernels_only():
+            torch_qs.read_batch(on_dev, outs=outs, workspace=ws)
+            torch.cuda.synchronize()
+
+        host_pinned = [[torch.from_numpy(c).pin_memory() for c in im["coefs"]] for _ in ims]
+        dst = [[torch.empty_like(c) for c in coefs] for _ in ims]
+
+        def coef_upload():
+            for hp, d in zip(host_pinned, dst):
+                for h, t in zip(hp, d):
+                    t.copy_(h, non_blocking=True)
+            torch.cuda.synchronize()
+
+        def med(fn, calls):
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                ms.append((time.perf_counter() - t0) * 1e3 / calls)
+            return round(float(np.median(ms)), 3), [round(m, 3) for m in ms]
+
+        dev_ms, dev_all = med(device_route, 3)
+        k_ms, k_all = med(kernels_only, 3)
+        up_ms, _ = med(coef_upload, 3)
+        row = dict(case=name, images=len(ims), file_bytes=len(data) * len(ims), coef_mbytes=round(sum(c.numel() * 2 for c in coefs) * len(ims) / 1e6, 1),
+                   restart_interval=header["restart_interval"], lanes=per[0]["intervals"] * len(ims),
+                   blocks_per_lane=per[0]["blocks_per_interval"], device_upload_plus_read_ms=dev_ms, device_windows=dev_all,
+                   device_read_ms=k_ms, device_read_windows=k_all, host_coef_upload_ms=up_ms, identical=bool(identical))
+        with tempfile.TemporaryDirectory() as td:
+            lj9 = LibJpeg9(Path(td))
+            f = Path(td) / "in.jpg"
+            f.write_bytes(data)
+            arrays = Path(td) / "out.bin"
+            lj9._run("read", f, arrays)                                 # the helper alone: it writes the arrays to a file
+            ts = []
+            for _ in range(min(a.repeats, 3)):
+                t0 = time.perf_counter()
+                lj9._run("read", f, arrays)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row["host_libjpeg9_read_ms_per_image"] = round(float(np.median(ts)), 1)
+        row["host_route_ms"] = round(up_ms + row["host_libjpeg9_read_ms_per_image"] * len(ims), 1)
+        row["device_faster_than_host_route"] = bool(dev_ms < row["host_route_ms"])
+        out["results"].append(row)
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    if bad:
+        raise SystemExit(f"bench_device_batch --read: {bad}: the arrays read are not the arrays encoded")
 
 
 if __name__ == "__main__":
