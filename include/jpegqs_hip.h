@@ -400,6 +400,47 @@ int qs_hip_huff_optimal(const uint32_t freq[257], uint8_t bits[17], uint8_t huff
 /* Host only.  The standard table of Annex K.3: is_ac 0 / 1, tbl 0 (luminance) / 1 (chrominance). */
 int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[256]);
 
+/* ---- device compress (interleaved uint8 pixels in device memory -> the quantised coefficient arrays of device-resident jobs) ----
+ * The inverse of the device decode: the arrays libjpeg 9 holds after jpeg_write_scanlines() -- what jpeg_read_coefficients()
+ * returns for the file it writes -- for the same pixels, quant tables, sampling factors and colour space, bit for bit, with
+ *   dct_method = JDCT_ISLOW (8x8 jpeg_fdct_islow for every component), smoothing_factor = 0 and
+ *   do_fancy_downsampling = FALSE (box-filter chroma downsampling, jcsample.c).
+ * OUT OF SCOPE: libjpeg 9's default do_fancy_downsampling = TRUE, which compresses 2x-subsampled chroma through 16-point
+ * scaled forward DCTs (jpeg_fdct_16x16, _16x8, _8x16) and gives other coefficients wherever chroma is subsampled.  The
+ * `fancy` argument of info / prepare is there for it: anything but 0 is QS_HIP_ENOTSUP today.
+ * Jobs are qs_hip_job records as the decode takes them, with coef[ci] the DEVICE arrays to FILL (wblk as the row stride,
+ * 16-byte aligned), quant tables required (1 .. 65535, natural order, one per component; a 0: QS_HIP_EINVAL) and
+ * image_width x image_height required.  Layouts, derived from ncomp and colorspace as in qs_hip_decode_info:
+ *   grayscale (1 component, colorspace 1, taken as 1x1)                              <- height x width x 1
+ *   RGB -> YCbCr (colorspace 3), chroma 1x1, luma 1x1, 2x1, 1x2, 2x2 or 4x1          <- height x width x 3
+ *   RGB without a colour transform (colorspace 2), the same sampling                 <- height x width x 3
+ * anything else: QS_HIP_ENOTSUP before anything is enqueued.  Each array must hold at least libjpeg's width_in_blocks x
+ * height_in_blocks (QS_HIP_EINVAL otherwise; info reports them); exactly these blocks are written -- the blocks of a
+ * larger array outside libjpeg's geometry (the dummy blocks of edge MCUs among them) are left as they are.  Edges follow
+ * libjpeg: the right edge is replicated before downsampling; at the bottom the image is padded to a multiple of
+ * max_v_samp rows with its last row, downsampled, and then the last DOWNSAMPLED row of each component is repeated.
+ * The same three-call pattern:
+ *   info     per_job[i] = input shape, layout and block geometry of jobs[i]; *workspace_bytes; no device touched;
+ *   prepare  writes the per-job descriptors (geometry, tables, their reciprocals) into the workspace; may synchronise
+ *            `stream`, never inside a capture; once per geometry + table set;
+ *   run      ENQUEUES the compress on `stream`: one kernel launch per QS_HIP_COMPRESS_CHUNK jobs (the pixels and arrays
+ *            travel in its arguments), no allocation, no synchronisation, no copy (graph-capturable).  It must see the
+ *            geometry and tables prepare saw.
+ * d_pixels[i]: device buffer (any alignment) of (height - 1) * pitch[i] + width * channels bytes, rows pitch[i] >= width *
+ * channels bytes apart; nothing else is read. */
+#define QS_HIP_COMPRESS_CHUNK 44
+typedef struct {
+	int32_t width, height, channels;   /* input of job i: height rows of width * channels samples */
+	int32_t layout;                    /* 0 grayscale, 1 RGB -> YCbCr, 2 RGB */
+	int32_t wblk[QS_HIP_MAXC], hblk[QS_HIP_MAXC];   /* libjpeg's width_in_blocks / height_in_blocks: what is written */
+} qs_hip_compress_info;
+int qs_hip_compress_device_batch_info(qs_hip_job *const *jobs, int njobs, int fancy, qs_hip_compress_info *per_job,
+		size_t *workspace_bytes);
+int qs_hip_compress_device_batch_prepare(qs_hip_job *const *jobs, int njobs, int fancy, void *d_workspace, size_t bytes,
+		void *stream);
+int qs_hip_compress_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_pixels, const size_t *pitch,
+		void *d_workspace, size_t bytes, void *stream);
+
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up
  * to 2 GiB) and HIP streams in process-wide caches, each entry tied to the device it was created
@@ -418,7 +459,7 @@ const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
- * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader).  A caller built against
+ * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

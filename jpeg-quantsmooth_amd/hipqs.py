@@ -90,6 +90,13 @@ class DecodeInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32)]
 
 
+class CompressInfo(C.Structure):
+    """qs_hip_compress_info: the input of one job of the device compress and the blocks it writes
+    (qs_hip_compress_device_batch_info)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32),
+                ("wblk", C.c_int32 * MAXC), ("hblk", C.c_int32 * MAXC)]
+
+
 class HuffTable(C.Structure):
     """qs_hip_huff_table: bits[l] = codes of length l, huffval = the symbols by increasing code length"""
     _fields_ = [("bits", C.c_uint8 * 17), ("huffval", C.c_uint8 * 256)]
@@ -125,6 +132,7 @@ class ReadInfo(C.Structure):
 
 
 MAX_PLANES = 56
+COMPRESS_CHUNK = 44              # QS_HIP_COMPRESS_CHUNK: jobs per launch of the device compress
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 # every symbol include/jpegqs_hip.h declares: (restype, argtypes)
@@ -180,6 +188,12 @@ ABI = {
                                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_read_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_compress_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.POINTER(CompressInfo),
+                                                     C.POINTER(C.c_size_t)]),
+    "qs_hip_compress_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p]),
+    "qs_hip_compress_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_huff_optimal": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_huff_standard": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "qs_hip_free": (None, [C.c_void_p]),
@@ -505,6 +519,35 @@ class HipQS:
         outs, pitches = self._outs(d_out, pitch)
         self._check(self.lib.qs_hip_decode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, pitches,
                                                         d_workspace, nbytes, stream))
+
+    # -- device compress of pixels (a list of device_job() Jobs over the arrays to fill) ---
+    def compress_batch_info(self, jobs, fancy: bool = False):
+        """qs_hip_compress_device_batch_info (no device needed) -> (list of dict(width, height, channels, layout, wblk,
+        hblk: libjpeg's block geometry per component), the batch's workspace bytes).  fancy: libjpeg 9's default
+        do_fancy_downsampling, not implemented (QS_HIP_ENOTSUP)"""
+        per = (CompressInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_compress_device_batch_info(self._job_ptrs(jobs), len(jobs), int(bool(fancy)), per,
+                                                               C.byref(total)))
+        out = []
+        for i, job in enumerate(jobs):
+            n = int(job.ncomp)
+            out.append(dict(width=int(per[i].width), height=int(per[i].height), channels=int(per[i].channels),
+                            layout=int(per[i].layout), wblk=list(per[i].wblk[:n]), hblk=list(per[i].hblk[:n])))
+        return out, int(total.value)
+
+    def compress_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, fancy: bool = False) -> None:
+        """qs_hip_compress_device_batch_prepare: geometry and tables into the workspace (synchronises `stream`; not
+        inside a capture)"""
+        self._check(self.lib.qs_hip_compress_device_batch_prepare(self._job_ptrs(jobs), len(jobs), int(bool(fancy)),
+                                                                  d_workspace, nbytes, stream))
+
+    def compress_batch(self, jobs, d_pixels, pitch, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_compress_device_batch: enqueue the compress of every job (one launch per 44 jobs); d_pixels[i] = device
+        address of job i's interleaved uint8 pixels, pitch[i] = bytes between its rows; the arrays are job.coef"""
+        pix, pitches = self._outs(d_pixels, pitch)
+        self._check(self.lib.qs_hip_compress_device_batch(self._job_ptrs(jobs), len(jobs), pix, pitches, d_workspace,
+                                                          nbytes, stream))
 
     # -- device entropy coder (a list of device_job() Jobs) -------------------------------
     @staticmethod

@@ -30,6 +30,11 @@ entropy-codes them on the device (qs_hip_encode_device_batch); encode_scan leave
 reads a file's scan into device coefficient tensors (qs_hip_read_device_batch, one lane per restart interval): the image
 dict the three calls above take.
 
+    im = torch_qs.compress(pixels, quality=85, hsamp=[2, 1, 1], vsamp=[2, 1, 1])   # pixels: uint8 (H, W, 3) on the device
+
+compresses pixels into the same image dict (qs_hip_compress_device_batch): libjpeg 9's jpeg_write_scanlines with
+JDCT_ISLOW and do_fancy_downsampling = FALSE; its default fancy downsampling is not implemented.
+
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
@@ -702,3 +707,123 @@ def read(data, *, out=None, workspace: Workspace | None = None, device=None) -> 
     restart_interval, status) with the workspace used under `workspace`"""
     r = _read_batch([data], None if out is None else [out], workspace, device, "read")
     return dict(r["images"][0], workspace=r["workspace"])
+
+
+# ---- compressing pixels into coefficient tensors (qs_hip_compress_device_batch) ---------------------------------------------
+
+def _compress_tables(im, n, who):
+    """the image's tables: quants as given, or libjpeg's jpeg_set_quality(quality, TRUE) tables -- luminance for component
+    0, chrominance for the others"""
+    from . import synth
+    quants, quality = im.get("quants"), im.get("quality")
+    if (quants is None) == (quality is None):
+        raise ValueError(f"{who}: give exactly one of quality and quants")
+    if quants is None:
+        if not 1 <= int(quality) <= 100:
+            raise ValueError(f"{who}: quality {quality} is not in 1..100")
+        return [synth.quality_table(synth.STD_LUMA if ci == 0 else synth.STD_CHROMA, int(quality)) for ci in range(n)]
+    qs = _check_quants(quants, n, who=who)
+    if any(q is None or q.min() < 1 for q in qs):
+        raise ValueError(f"{who}: every component needs a table of 64 values in 1..65535")
+    return [q.astype(np.uint16) for q in qs]
+
+
+def compress(pixels, *, quality=None, quants=None, hsamp=None, vsamp=None, colorspace=None, fancy=False, out=None,
+             workspace: Workspace | None = None) -> dict:
+    """Compress device pixels into quantised coefficient tensors on the current stream: exactly the arrays libjpeg 9
+    holds after jpeg_write_scanlines with JDCT_ISLOW, smoothing_factor 0 and do_fancy_downsampling = FALSE (8x8
+    jpeg_fdct_islow for every component, box-filter chroma downsampling), i.e. what jpeg_read_coefficients returns for
+    that file.  libjpeg 9's default, do_fancy_downsampling = TRUE (2x chroma through 16-point scaled DCTs), is out of
+    scope: fancy=True raises ValueError.  Where chroma is not subsampled the two modes agree.
+
+    pixels: a uint8 CUDA tensor (H, W, 1) or (H, W, 3) with contiguous rows (any row pitch, any base alignment): gray,
+    or RGB.  quality: libjpeg's jpeg_set_quality(q, TRUE) tables (luminance for component 0, chrominance for the
+    others); or quants: one table of 64 values in 1..65535 (natural order) per component.  hsamp / vsamp: default 1x1;
+    chroma must be 1x1 and luma 1x1, 2x1, 1x2, 2x2 or 4x1 (ValueError otherwise).  colorspace: 1 for one channel; 3
+    (RGB -> YCbCr, the default) or 2 (RGB kept) for three.  out: preallocated contiguous int16 tensors (hblk, wblk, 64),
+    at least libjpeg's width_in_blocks x height_in_blocks each; blocks outside that geometry are not written.
+    workspace: as decode's -- a Workspace, prepared in place when the geometry or tables change (outside a capture) and
+    reused as it is inside one.  Returns the image dict read returns, with exactly these keys -- coefs, quants, hsamp,
+    vsamp, colorspace, image_size -- so quantsmooth_(**im, ...), decode(**im) and encode(**im, restart_interval=...)
+    take it as it is."""
+    r = compress_batch([dict(pixels=pixels, quality=quality, quants=quants, hsamp=hsamp, vsamp=vsamp,
+                             colorspace=colorspace)], fancy=fancy, outs=None if out is None else [out],
+                       workspace=workspace, _who="compress")
+    return r["images"][0]
+
+
+def compress_batch(images, *, fancy=False, outs=None, workspace: Workspace | None = None, _who="compress_batch") -> dict:
+    """compress on many images in one call (one kernel launch for up to 44 images).  images[i]: a dict with compress's
+    per-image arguments (pixels, quality or quants, hsamp, vsamp, colorspace).  outs[i]: optional preallocated arrays.
+    Returns dict(images=[image dicts], workspace=Workspace)."""
+    import torch
+    who = _who
+    if not isinstance(images, (list, tuple)) or not images:
+        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    if fancy:
+        raise ValueError(f"{who}: fancy downsampling (libjpeg 9's default, 2x chroma through 16-point scaled DCTs) is not "
+                         f"implemented: the compress is libjpeg's with do_fancy_downsampling = FALSE")
+    if outs is not None and len(outs) != len(images):
+        raise ValueError(f"{who}: one output list (or None) per image")
+    hip = _hip()
+    dev, metas = None, []
+    for i, im in enumerate(images):
+        w_i = f"{who}: image {i}"
+        if not isinstance(im, dict) or "pixels" not in im:
+            raise ValueError(f"{w_i} must be a dict with pixels")
+        px = im["pixels"]
+        if not isinstance(px, torch.Tensor) or px.dtype != torch.uint8 or not px.is_cuda:
+            raise TypeError(f"{w_i}: pixels must be a uint8 CUDA (HIP) tensor")
+        if px.dim() != 3 or px.shape[2] not in (1, 3) or px.shape[0] < 1 or px.shape[1] < 1:
+            raise ValueError(f"{w_i}: pixels have shape {tuple(px.shape)}, expected (H, W, 1) or (H, W, 3)")
+        n = int(px.shape[2])
+        if px.stride(2) != 1 or px.stride(1) != n or (px.shape[0] > 1 and px.stride(0) < px.shape[1] * n):
+            raise ValueError(f"{w_i}: pixels must have contiguous rows (stride {px.stride()})")
+        if dev is None:
+            dev = px.device
+        elif px.device != dev:
+            raise ValueError(f"{w_i} is on {px.device}, image 0 on {dev}")
+        cs = im.get("colorspace")
+        cs = (1 if n == 1 else 3) if cs is None else int(cs)
+        if (n == 1 and cs != 1) or (n == 3 and cs not in (2, 3)):
+            raise ValueError(f"{w_i}: colour space {cs} for {n} channel(s): 1 (gray), or 3 (YCbCr) / 2 (RGB)")
+        hs = [int(v) for v in (im.get("hsamp") or [1] * n)]
+        vs = [int(v) for v in (im.get("vsamp") or [1] * n)]
+        if len(hs) != n or len(vs) != n:
+            raise ValueError(f"{w_i}: one sampling factor per component")
+        if n == 3 and (hs[1:] != [1, 1] or vs[1:] != [1, 1] or (hs[0], vs[0]) not in ((1, 1), (2, 1), (1, 2), (2, 2), (4, 1))):
+            raise ValueError(f"{w_i}: sampling {hs} x {vs}: chroma must be 1x1 and luma 1x1, 2x1, 1x2, 2x2 or 4x1")
+        qs = _compress_tables(im, n, w_i)
+        metas.append((px, n, cs, hs, vs, qs))
+    jobs, results = [], []
+    for i, (px, n, cs, hs, vs, qs) in enumerate(metas):
+        h, w = int(px.shape[0]), int(px.shape[1])
+        mh, mv = (1, 1) if n == 1 else (max(hs), max(vs))
+        shapes = [(-(-h * (1 if n == 1 else vs[ci]) // (8 * mv)), -(-w * (1 if n == 1 else hs[ci]) // (8 * mh)))
+                  for ci in range(n)]
+        if outs is None or outs[i] is None:
+            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
+        else:
+            coefs = list(outs[i])
+            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
+                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
+        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hs,
+                                   vsamp=vs, colorspace=cs, image_size=(w, h)))
+        results.append(dict(coefs=coefs, quants=[q.copy() for q in qs], hsamp=hs, vsamp=vs, colorspace=cs,
+                            image_size=(w, h)))
+    _per, total = hip.compress_batch_info(jobs)
+    key = ("compress",) + tuple(_key(job, 0, 0) for job in jobs)
+    if workspace is None:
+        workspace = Workspace()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
+                               f"geometry and tables (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.compress_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, stream)
+        workspace.key = key
+    pitches = [int(m[0].stride(0)) if m[0].shape[0] > 1 else int(m[0].shape[1]) * m[1] for m in metas]
+    hip.compress_batch(jobs, [m[0].data_ptr() for m in metas], pitches, workspace.buf.data_ptr(), workspace.nbytes, stream)
+    return dict(images=results, workspace=workspace)

@@ -28,8 +28,14 @@ host route it replaces -- libjpeg 9's jpeg_read_coefficients on one core (tests/
 includes writing the arrays to a file) plus the pinned upload of the coefficient arrays.  Parallelism is the number of
 restart intervals: the lanes of each case are reported.  Exits non-zero unless the arrays are the ones encoded.
 
+--compress times the device compress of pixels (torch_qs.compress_batch, one launch per batch, quality 50 tables) on the
+same three cases, as time per call and GB/s of pixels read plus coefficients written, next to the decode of the arrays
+it wrote (the same bytes the other way) and the host route it replaces: libjpeg 9's jpeg_write_scanlines on one core
+(tests/libjpeg9_compress.c on a staged input file: its time includes reading the pixels and writing the file) plus the
+pinned upload of the coefficient arrays.  Exits non-zero unless the arrays are libjpeg's.
+
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode | --read] [--restart N | --restart-rows N]"""
+                                       [--decode | --encode | --read | --compress] [--restart N | --restart-rows N]"""
 import argparse
 import json
 import sys
@@ -56,7 +62,10 @@ def main():
     ap.add_argument("--restart-rows", type=int, default=None, metavar="N",
                     help="--encode: write a restart marker every N MCU rows (libjpeg's restart_in_rows)")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
+    ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
     a = ap.parse_args()
+    if a.compress:
+        return bench_compress(a)
     if a.read:
         return bench_read(a)
     if a.decode:
@@ -415,6 +424,102 @@ def bench_read(a):
     bad = [r["case"] for r in out["results"] if not r["identical"]]
     if bad:
         raise SystemExit(f"bench_device_batch --read: {bad}: the arrays read are not the arrays encoded")
+
+
+def bench_compress(a):
+    import subprocess
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from compress_oracle import Compress9, pack, tables
+    pkg = jpegqs_pkg.load()
+    torch_qs, synth = pkg.torch_qs, pkg.synth
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def picture(w, h, n):
+        return np.stack([synth.synth_pixels(w, h, 1234, variant=c) for c in range(n)], axis=-1)
+
+    s420 = dict(hsamp=[2, 1, 1], vsamp=[2, 1, 1])
+    cases = [("8192x8192_gray", picture(8192, 8192, 1), dict(hsamp=[1], vsamp=[1]), 1),
+             ("8192x8192_420", picture(8192, 8192, 3), s420, 1),
+             (f"{a.images}x1920x1080_420", picture(1920, 1080, 3), s420, a.images)]
+    out = dict(tool="bench_device_batch", leg="compress", device=torch.cuda.get_device_name(dev), results=[])
+
+    def windows(fn, calls=20):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(calls):
+                fn()
+            e1.record(stream)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / calls)
+        return float(np.median(ms)), [round(m, 4) for m in ms]
+
+    for name, px, samp, count in cases:
+        n = px.shape[2]
+        on_dev = [torch.from_numpy(px).to(dev) for _ in range(count)]
+        images = [dict(pixels=t, quality=50, **samp) for t in on_dev]
+        ws, dws = torch_qs.Workspace(), torch_qs.Workspace()
+        res = torch_qs.compress_batch(images, workspace=ws)["images"]
+        outs = [im["coefs"] for im in res]
+        nbytes = sum(t.numel() for t in on_dev) + sum(c.numel() * 2 for o in outs for c in o)
+        med, ms = windows(lambda: torch_qs.compress_batch(images, outs=outs, workspace=ws))
+        back = torch_qs.decode_batch(res, workspace=dws)["images"]
+        dmed, dms = windows(lambda: torch_qs.decode_batch(res, outs=back, workspace=dws))
+        row = dict(case=name, images=count, mbytes=round(nbytes / 1e6, 1), ms=ms, median_ms=round(med, 4),
+                   gb_per_s=round(nbytes / (med * 1e-3) / 1e9, 1), decode_ms=dms, decode_median_ms=round(dmed, 4),
+                   compress_over_decode=round(med / dmed, 2))
+        # the host route: libjpeg 9 on one core, then the arrays up from pinned memory
+        host_pinned = [[c.cpu().pin_memory() for c in o] for o in outs]
+        dst = [[torch.empty_like(c) for c in o] for o in outs]
+
+        def upload():
+            for hp, d in zip(host_pinned, dst):
+                for h, t in zip(hp, d):
+                    t.copy_(h, non_blocking=True)
+            torch.cuda.synchronize()
+
+        for _ in range(2):
+            upload()
+        ts = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            upload()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        row["host_coef_upload_ms"] = round(float(np.median(ts)), 3)
+        with tempfile.TemporaryDirectory() as td:
+            c9 = Compress9(Path(td))
+            q = tables("q50", n, synth)
+            cs = 1 if n == 1 else 3
+            staged, jpg = Path(td) / "in.bin", Path(td) / "out.jpg"
+            staged.write_bytes(pack(px, q, samp["hsamp"], samp["vsamp"], cs))
+            ts = []
+            for _ in range(a.repeats + 1):                                 # (the first run warms the page cache)
+                t0 = time.perf_counter()
+                subprocess.run([str(c9.exe), "image", str(staged), str(jpg)], check=True)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row["host_libjpeg9_compress_ms_per_image"] = round(float(np.median(ts[1:])), 1)
+            want = c9.lj9.read(jpg)["coefs"]
+            row["identical"] = all(np.array_equal(w, c.cpu().numpy()) for o in outs for w, c in zip(want, o))
+        row["host_route_ms"] = round(row["host_coef_upload_ms"] + row["host_libjpeg9_compress_ms_per_image"] * count, 1)
+        out["results"].append(row)
+        del on_dev, images, res, outs, back, host_pinned, dst
+        torch.cuda.empty_cache()
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    if bad:
+        raise SystemExit(f"bench_device_batch --compress: {bad}: the arrays are not libjpeg's")
 
 
 if __name__ == "__main__":
