@@ -345,6 +345,51 @@ int qs_hip_encode_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, con
 		qs_hip_encode_info *per_job, size_t *workspace_bytes);
 int qs_hip_encode_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_huff_tables *const *tables,
 		const qs_hip_encode_opts *const *opts, void *d_workspace, size_t bytes, void *stream);
+/* ---- optimal tables and whole files on the device ----
+ * The device twin of qs_hip_huff_optimal (below): d_counts = device uint32[ntables][257] (entry 256 is ignored: the
+ * reserved symbol always counts 1), d_tables[ntables] receives bits / huffval as qs_hip_huff_optimal gives them,
+ * d_status[t] = 0, or 5 for a code length above 32 (libjpeg's JERR_HUFF_CLEN_OVERFLOW, where the host function returns
+ * QS_HIP_EINVAL; bits and huffval are then all 0).  One launch on `stream`, one wave per table, no workspace, no
+ * allocation, no synchronisation (graph-capturable). */
+int qs_hip_huff_optimal_device(const uint32_t *d_counts, int ntables, qs_hip_huff_table *d_tables,
+		int32_t *d_status, void *stream);
+/* Whole files: d_out[i] receives head | DHT markers | mid | segment | FF D9 -- the file libjpeg 9 writes -- and d_len[i]
+ * its length.  The bytes around the tables and the scan are the caller's (jpeg_file.compose_parts composes them), per
+ * job and per geometry variant (variant 1 is used where the coder uses its second geometry: a job with up_wblk > 0 whose
+ * d_stop reads non-zero); DEVICE memory, any alignment. */
+typedef struct {
+	const uint8_t *d_head[2]; uint32_t head_bytes[2];   /* SOI .. SOF (and, without optimize, the DHT markers) */
+	const uint8_t *d_mid[2];  uint32_t mid_bytes[2];    /* [DRI] SOS header */
+} qs_hip_encode_frame;
+/* The DHT markers are written by the run, and only with optimize != 0: one per table the job's components use, in
+ * jcmarker.c's order (per component DC then AC, each table once: DC 0, AC 0, DC 1, AC 1 for YCbCr), each FF C4, length,
+ * Tc/Th, 16 counts, the symbols; the tables are libjpeg's optimize_coding tables for the scan (qs_hip_huff_optimal on the
+ * histogram, both taken on the device), and the segment is coded with them.  optimize == 0: the segment of
+ * qs_hip_encode_device_batch, coded with prepare's tables, whose DHT markers the caller puts at the end of the head.
+ * frames == NULL: no head, no mid and no EOI -- d_out[i] receives the DHT markers (if any) and the segment.
+ * The workspace is the encode workspace, used exactly as qs_hip_encode_device_batch uses it: the same info and prepare
+ * calls (restart intervals through the _opts calls), the same size; the run does not write the tables prepare put there,
+ * so a plain qs_hip_encode_device_batch on the same workspace afterwards gives the bytes it gave before.  Everything new
+ * lives in d_scratch (256-byte aligned, qs_hip_encode_files_scratch_bytes(njobs) bytes): the counts, the derived code
+ * words, the tables, each job's prefix length and table status.
+ * Per QS_HIP_ENCODE_CHUNK jobs the run ENQUEUES, with optimize: the three launches of the histogram call (counting into
+ * the scratch), the table kernel (one wave per table, four per job; a table no component uses is skipped), the seven coder
+ * launches (reading their codes from the scratch) and one framing launch; without: the seven coder launches and the
+ * framing launch.  No allocation, no synchronisation, no copy from host memory, no other stream; a capture is a linear
+ * graph; nothing is stored at or beyond out_capacity[i], framing bytes included.
+ * d_len[i]: the length of the whole file.  d_status[i]: as qs_hip_encode_device_batch, plus 5 for a table with a code
+ * length above 32; precedence 4, 1, 5, 2 (3 cannot occur with optimize).  With 1, 3, 4 or 5 d_len[i] is 0 and the buffer
+ * unspecified; with 2 d_len[i] is exact and the buffer holds the file's first out_capacity[i] bytes.
+ * d_tables (device, [njobs], may be NULL): with optimize, the tables of each job; has_* is 0 for a table no component
+ * uses.  Untouched without optimize.
+ * QS_HIP_EINVAL before anything is enqueued: a job whose frames[i] lacks a variant it can take (no SOS header bytes, or a
+ * null pointer with a non-zero length; variant 1 counts for a job with two geometries when d_stop is given), and a
+ * scratch that is null, misaligned or short. */
+size_t qs_hip_encode_files_scratch_bytes(int njobs);
+int qs_hip_encode_device_batch_files(qs_hip_job *const *jobs, int njobs, const qs_hip_encode_frame *frames,
+		int optimize, const int32_t *d_stop, uint8_t *const *d_out, const size_t *out_capacity, uint64_t *d_len,
+		int32_t *d_status, qs_hip_huff_tables *d_tables /* device, [njobs], may be NULL */,
+		void *d_scratch, size_t scratch_bytes, void *d_workspace, size_t bytes, void *stream);
 /* ---- device scan reader (the bytes of a JPEG scan with restart intervals -> device-resident coefficient arrays) ----
  * What libjpeg 9 leaves in its coefficient arrays after jpeg_read_coefficients (jdhuff.c decode_mcu: the DC prediction
  * runs as int and is stored as JCOEF, AC values by HUFF_EXTEND, de-zigzagged), for ONE sequential Huffman scan (SOF0 /
@@ -395,7 +440,9 @@ int qs_hip_read_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const q
 int qs_hip_read_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_scan, const uint64_t *scan_bytes,
 		int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
 /* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
- * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT. */
+ * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT.  Counts
+ * that are all zero: bits all 0, no symbols, success.  A code length above 32: QS_HIP_EINVAL.  (csrc/qs_huff.h: the
+ * procedure of the table kernel, in its host form.) */
 int qs_hip_huff_optimal(const uint32_t freq[257], uint8_t bits[17], uint8_t huffval[256]);
 /* Host only.  The standard table of Annex K.3: is_ac 0 / 1, tbl 0 (luminance) / 1 (chrominance). */
 int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[256]);
@@ -459,7 +506,8 @@ const char *qs_hip_last_error(void);
 /* Version of this interface: bumped whenever a struct layout or the meaning of an argument changes (5: round 5 --
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
- * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress).  A caller built against
+ * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
+ * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

@@ -13,6 +13,7 @@
 // the restart variant: every lane can own an interval end, whose padding adds up to 7 bits to the workgroup's image
 #define QS_ENC_LDS_WORDS_RST (QS_ENC_LDS_WORDS + (7 * QS_ENC_WG + 31) / 32)
 #define QS_ENC_SCHUNK 4096         // bytes of the unstuffed stream per stuffing step (16 per lane)
+#define QS_ENC_CODES (2 * 16 + 2 * 256)   // code words of one job: dc[2][16], ac[2][256]
 #define QS_ENC_SWG_MAX 1024        // workgroups a job's stuffing kernels get at most (they stride over the chunks)
 
 // status bits collected per job while it runs (QsEncState.flags); the caller sees 1, 3 or 2 in this order of precedence
@@ -80,7 +81,45 @@ struct QsEncArgs {
   uint32_t* d_counts;              // histogram run: uint32[njobs][4][257], else null
   int32_t job0, n;
   int32_t restart;                 // 1: the restart instantiations run (else a job with an interval ends with status 4)
+  // the whole-file run (qs_hip_encode_device_batch_files, csrc/qs_kernels_huff.hip); all null / 0 in every other run
+  const uint32_t* codes;           // scratch: uint32[njobs][QS_ENC_CODES] -- the table kernel's code words instead of the
+                                   // descriptors' (dc[2][16] then ac[2][256], the same form); null: the descriptors'
+  uint64_t* prefix;                // scratch: uint64[njobs] -- bytes of the file in front of the segment; null: 0
+  const int32_t* tstatus;          // scratch: int32[njobs] -- not 0: a table of the job has a code length above 32 (status 5)
+  uint32_t tail;                   // bytes of the file behind the segment (EOI)
+  uint32_t fixed[QS_ENC_CHUNK][2]; // head + mid bytes of each variant: what qe_init makes the prefix when `codes` is null
+                                   // (with `codes` the table kernel wrote it: the DHT markers' bytes come on top)
   int32_t wg0[QS_ENC_CHUNK];       // each job's first workgroup in the block kernels' launch (QsEncJob.wg0) ...
   int32_t swg0[QS_ENC_CHUNK];      // ... and in the stuffing kernels': a workgroup finds its job without touching memory
   QsEncPtrs p[QS_ENC_CHUNK];
+};
+
+// ---- the whole-file run: optimal tables and framing (csrc/qs_kernels_huff.hip) ----
+#define QS_ENC_TABLE_BYTES 273     // sizeof(qs_hip_huff_table): bits[17], huffval[256]
+#define QS_ENC_TABLES_BYTES (4 * QS_ENC_TABLE_BYTES + 4)   // sizeof(qs_hip_huff_tables): dc[2], ac[2], has_dc[2], has_ac[2]
+#define QS_ENC_DHT_MAX (4 * (5 + 16 + 256))                 // the DHT markers of one job at most
+
+// the caller's memory of one job of the whole-file run
+struct QsFramePtrs {
+  const uint8_t* head[2];          // per variant: SOI .. SOF (without optimize: .. the DHT markers); null with 0 bytes
+  const uint8_t* mid[2];           // [DRI] SOS header
+  uint32_t head_bytes[2], mid_bytes[2];
+  uint8_t* out;
+  uint64_t cap;
+};
+// arguments of the table kernel (qh_tables) and the framing kernel (qh_frame), per chunk of jobs
+struct QsHuffArgs {
+  const QsEncJob* jobs;            // the chunk's descriptors (workspace)
+  const int32_t* d_stop;
+  const uint32_t* counts;          // scratch: uint32[njobs][4][257], indexed by job0 + i like everything below
+  uint32_t* codes;                 // scratch: uint32[njobs][QS_ENC_CODES]
+  uint8_t* tables;                 // scratch: qs_hip_huff_tables[njobs]
+  uint8_t* d_tables;               // the caller's qs_hip_huff_tables[njobs] or null
+  uint64_t* prefix;                // scratch: uint64[njobs]
+  int32_t* tstatus;                // scratch: int32[njobs]
+  const uint64_t* d_len;
+  const int32_t* d_status;
+  int32_t job0, n;
+  int32_t optimize, framed;        // framed 0: no head, mid or EOI (frames == NULL)
+  QsFramePtrs f[QS_ENC_CHUNK];
 };

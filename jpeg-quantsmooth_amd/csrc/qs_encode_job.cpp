@@ -3,6 +3,9 @@
 // qs_hip_huff_optimal / qs_hip_huff_standard.  What libjpeg 9 writes between the SOS header and EOI for
 // jpeg_write_coefficients on the arrays of qs_hip_job records (no scan script, 8 bits; restart intervals through the
 // _opts calls), computed on the device (qs_kernels_encode.hip).
+// qs_hip_encode_device_batch_files is the same run with the optimal tables made on the device and the file's markers
+// around the segment (qs_kernels_huff.hip): it shares enqueue() with the plain run and keeps its
+// own arrays in the caller's scratch, never in the workspace.  qs_hip_huff_optimal[_device]: csrc/qs_huff.h.
 //
 // Workspace: the QsEncJob descriptors of the batch, then per job its scratch arrays (block code lengths, workgroup
 // sums and offsets, the unstuffed stream at its worst-case size, the stuffing counts, the restart intervals' offsets)
@@ -13,6 +16,7 @@
 // should its descriptors hold an interval after all, the kernels end those jobs with status 4.
 #include "qs_common.h"
 #include "qs_encode.h"
+#include "qs_huff.h"
 
 #include <algorithm>
 #include <mutex>
@@ -21,6 +25,13 @@
 #include <vector>
 
 void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, bool restart, hipStream_t s);
+void qs_launch_huff_optimal(const uint32_t* d_counts, int ntables, uint8_t* d_tables, int32_t* d_status, hipStream_t s);
+void qs_launch_huff_tables(const QsHuffArgs& a, hipStream_t s);
+void qs_launch_huff_frame(const QsHuffArgs& a, hipStream_t s);
+
+static_assert(sizeof(qs_hip_huff_table) == QS_ENC_TABLE_BYTES && sizeof(qs_hip_huff_tables) == QS_ENC_TABLES_BYTES,
+              "the kernels address the tables by these sizes");
+static_assert(sizeof(QsEncArgs) <= 4096 && sizeof(QsHuffArgs) <= 4096, "kernel arguments: 4 KiB at most");
 
 namespace {
 
@@ -303,10 +314,35 @@ template <class F> int guarded(F f) {
   }
 }
 
-// what the run and the histogram call share: the chunks' kernel arguments and launches
+// the whole-file run's scratch (qs_hip_encode_files_scratch_bytes): byte offsets of its arrays
+struct FilesScratch {
+  uint64_t counts, codes, tables, prefix, tstatus, total;
+  explicit FilesScratch(int njobs) {
+    const uint64_t n = (uint64_t)std::max(njobs, 0);
+    uint64_t off = 0;
+    auto take = [&](uint64_t b) { const uint64_t at = off; off += align_up(b, 256); return at; };
+    counts = take(n * 4 * 257 * 4);
+    codes = take(n * QS_ENC_CODES * 4);
+    tables = take(n * QS_ENC_TABLES_BYTES);
+    prefix = take(n * 8);
+    tstatus = take(n * 4);
+    total = off;
+  }
+};
+
+// what the whole-file run adds to a run (null: the plain run)
+struct FilesRun {
+  const qs_hip_encode_frame* frames;
+  int optimize;
+  qs_hip_huff_tables* d_tables;
+  void* d_scratch;
+  size_t scratch_bytes;
+};
+
+// what the runs and the histogram call share: the chunks' kernel arguments and launches
 int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* const* d_out, const size_t* out_capacity,
             uint64_t* d_len, int32_t* d_status, uint32_t* d_counts, void* d_workspace, size_t bytes, void* stream,
-            const char* who) {
+            const char* who, const FilesRun* F = nullptr) {
   std::vector<QsEncJob> D;
   std::vector<QsEncPtrs> P;
   uint64_t total = 0;
@@ -318,6 +354,24 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
       P[(size_t)i].out = d_out[i];
       P[(size_t)i].cap = out_capacity[i];
     }
+  }
+  const FilesScratch FS(njobs);
+  if (F) {
+    if (F->frames)
+      for (int i = 0; i < njobs; ++i) {
+        const qs_hip_encode_frame& f = F->frames[i];
+        const int nv = (D[(size_t)i].two && d_stop) ? 2 : 1;        // the variants the device can choose for this job
+        for (int v = 0; v < nv; ++v) {
+          if ((f.head_bytes[v] && !f.d_head[v]) || (f.mid_bytes[v] && !f.d_mid[v]))
+            return qs_fail(QS_HIP_EINVAL, "%s: job %d: variant %d of the frame has a length but no bytes", who, i, v);
+          if (!f.d_mid[v] || !f.mid_bytes[v])
+            return qs_fail(QS_HIP_EINVAL, "%s: job %d: the frame lacks variant %d (no SOS header), which the job can take",
+                           who, i, v);
+        }
+      }
+    if (!F->d_scratch || (reinterpret_cast<uintptr_t>(F->d_scratch) & 255) || F->scratch_bytes < FS.total)
+      return qs_fail(QS_HIP_EINVAL, "%s: scratch of %zu bytes (256-byte aligned), %d jobs need %llu", who, F->scratch_bytes,
+                     njobs, (unsigned long long)FS.total);
   }
   if (int r = check_ws(total, d_workspace, bytes, who)) return r;
   // the kernels to launch follow what prepare wrote at this address.  An address not known here (a copy of a prepared
@@ -357,7 +411,56 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
     const QsEncJob& last = D[(size_t)j0 + a.n - 1];
     const bool restart = !chunk_restart.empty() && chunk_restart[(size_t)(j0 / QS_ENC_CHUNK)];
     a.restart = restart ? 1 : 0;
-    qs_launch_encode(a, last.wg0 + last.nwg, last.swg0 + last.nswg, restart, s);
+    const int wgs = last.wg0 + last.nwg, swgs = last.swg0 + last.nswg;
+    if (!F) {
+      qs_launch_encode(a, wgs, swgs, restart, s);
+      continue;
+    }
+    // the whole-file run: [histogram into the scratch, the table kernel,] the coder behind the prefix, the framing
+    uint8_t* sc = static_cast<uint8_t*>(F->d_scratch);
+    QsHuffArgs h;
+    memset(&h, 0, sizeof h);
+    h.jobs = a.jobs;
+    h.d_stop = d_stop;
+    h.counts = reinterpret_cast<uint32_t*>(sc + FS.counts);
+    h.codes = reinterpret_cast<uint32_t*>(sc + FS.codes);
+    h.tables = sc + FS.tables;
+    h.d_tables = reinterpret_cast<uint8_t*>(F->d_tables);
+    h.prefix = reinterpret_cast<uint64_t*>(sc + FS.prefix);
+    h.tstatus = reinterpret_cast<int32_t*>(sc + FS.tstatus);
+    h.d_len = d_len;
+    h.d_status = d_status;
+    h.job0 = j0;
+    h.n = a.n;
+    h.optimize = F->optimize ? 1 : 0;
+    h.framed = F->frames ? 1 : 0;
+    for (int k = 0; k < a.n; ++k) {
+      QsFramePtrs& f = h.f[k];
+      if (F->frames) {
+        const qs_hip_encode_frame& src = F->frames[j0 + k];
+        for (int v = 0; v < 2; ++v) {
+          f.head[v] = src.d_head[v];
+          f.mid[v] = src.d_mid[v];
+          f.head_bytes[v] = src.d_head[v] ? src.head_bytes[v] : 0;
+          f.mid_bytes[v] = src.d_mid[v] ? src.mid_bytes[v] : 0;
+          a.fixed[k][v] = f.head_bytes[v] + f.mid_bytes[v];
+        }
+      }
+      f.out = a.p[k].out;
+      f.cap = a.p[k].cap;
+    }
+    if (F->optimize) {
+      QsEncArgs hist = a;
+      hist.d_counts = reinterpret_cast<uint32_t*>(sc + FS.counts);
+      qs_launch_encode(hist, wgs, swgs, restart, s);
+      qs_launch_huff_tables(h, s);
+      a.codes = h.codes;
+      a.tstatus = h.tstatus;
+    }
+    a.prefix = h.prefix;
+    a.tail = F->frames ? 2 : 0;
+    qs_launch_encode(a, wgs, swgs, restart, s);
+    qs_launch_huff_frame(h, s);
   }
   HIP_TRY(hipGetLastError());
   return QS_HIP_OK;
@@ -452,6 +555,30 @@ extern "C" int qs_hip_encode_device_batch_histogram(qs_hip_job* const* jobs, int
   });
 }
 
+extern "C" size_t qs_hip_encode_files_scratch_bytes(int njobs) { return (size_t)FilesScratch(njobs).total; }
+
+extern "C" int qs_hip_encode_device_batch_files(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_frame* frames,
+                                                int optimize, const int32_t* d_stop, uint8_t* const* d_out,
+                                                const size_t* out_capacity, uint64_t* d_len, int32_t* d_status,
+                                                qs_hip_huff_tables* d_tables, void* d_scratch, size_t scratch_bytes,
+                                                void* d_workspace, size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    const FilesRun F{frames, optimize, d_tables, d_scratch, scratch_bytes};
+    return enqueue(jobs, njobs, d_stop, d_out, out_capacity, d_len, d_status, nullptr, d_workspace, bytes, stream,
+                   "qs_hip_encode_device_batch_files", &F);
+  });
+}
+
+extern "C" int qs_hip_huff_optimal_device(const uint32_t* d_counts, int ntables, qs_hip_huff_table* d_tables,
+                                          int32_t* d_status, void* stream) {
+  const char* who = "qs_hip_huff_optimal_device";
+  if (!d_counts || !d_tables || !d_status || ntables < 1) return qs_fail(QS_HIP_EINVAL, "%s: null argument or no table", who);
+  if (int r = device_ok()) return r;
+  qs_launch_huff_optimal(d_counts, ntables, reinterpret_cast<uint8_t*>(d_tables), d_status, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return QS_HIP_OK;
+}
+
 extern "C" int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[256]) {
   if (tbl < 0 || tbl > 1 || !bits || !huffval) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_standard: table 0 or 1");
   qs_hip_huff_table t;
@@ -468,52 +595,11 @@ extern "C" int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_
 extern "C" int qs_hip_huff_optimal(const uint32_t freq_in[257], uint8_t bits_out[17], uint8_t huffval[256]) {
   if (!freq_in || !bits_out || !huffval) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_optimal: null argument");
   return guarded([&]() -> int {
-  const int MAXLEN = 32;
-  long long freq[257];
-  int bits[MAXLEN + 1] = {0}, codesize[257] = {0}, others[257];
-  for (int i = 0; i < 256; ++i) freq[i] = freq_in[i];
-  freq[256] = 1;                                           // no real symbol gets the all-ones code
-  for (int i = 0; i < 257; ++i) others[i] = -1;
-  for (;;) {
-    int c1 = -1, c2 = -1;
-    long long v = 1000000000000LL;
-    for (int i = 0; i <= 256; ++i)                         // the least frequent symbol, the larger value in a tie
-      if (freq[i] && freq[i] <= v) { v = freq[i]; c1 = i; }
-    v = 1000000000000LL;
-    for (int i = 0; i <= 256; ++i)
-      if (freq[i] && freq[i] <= v && i != c1) { v = freq[i]; c2 = i; }
-    if (c2 < 0) break;
-    freq[c1] += freq[c2];
-    freq[c2] = 0;
-    for (++codesize[c1]; others[c1] >= 0;) { c1 = others[c1]; ++codesize[c1]; }
-    others[c1] = c2;
-    for (++codesize[c2]; others[c2] >= 0;) { c2 = others[c2]; ++codesize[c2]; }
-  }
-  for (int i = 0; i <= 256; ++i)
-    if (codesize[i]) {
-      if (codesize[i] > MAXLEN) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_optimal: code length overflow");
-      ++bits[codesize[i]];
-    }
-  int i;
-  for (i = MAXLEN; i > 16; --i)
-    while (bits[i] > 0) {
-      int j = i - 2;
-      while (bits[j] == 0) --j;
-      bits[i] -= 2;
-      ++bits[i - 1];
-      bits[j + 1] += 2;
-      --bits[j];
-    }
-  while (bits[i] == 0) --i;                                // the reserved symbol leaves the longest length
-  --bits[i];
-  bits_out[0] = 0;
-  for (int l = 1; l <= 16; ++l) bits_out[l] = (uint8_t)bits[l];
-  memset(huffval, 0, 256);
-  std::vector<int> syms;
-  for (int s = 0; s < 256; ++s)
-    if (freq_in[s]) syms.push_back(s);
-  std::stable_sort(syms.begin(), syms.end(), [&](int a, int b) { return freq_in[a] > freq_in[b]; });
-  for (size_t p = 0; p < syms.size(); ++p) huffval[p] = (uint8_t)syms[p];
-  return QS_HIP_OK;
+    // the procedure of csrc/qs_huff.h, the table kernel's, in its host form
+    static thread_local QsHuffShared S;
+    if (qs_huff_wave(freq_in, S) != QS_HF_OK) return qs_fail(QS_HIP_EINVAL, "qs_hip_huff_optimal: code length overflow");
+    memcpy(bits_out, S.outbits, 17);
+    memcpy(huffval, S.huffval, 256);
+    return QS_HIP_OK;
   });
 }

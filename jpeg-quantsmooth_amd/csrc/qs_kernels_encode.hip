@@ -17,6 +17,10 @@
 // (D) and the byte each one starts at (P), qe_emit shifts every block by its interval's D and appends the pad one-bits
 // behind an interval's last block, and the stuffing kernels put FF Dn in front of the byte an interval starts at.  A job
 // without an interval in such a chunk is one interval: the same bytes.
+//
+// The whole-file run (qs_kernels_huff.hip) drives the same kernels with three pointers into its
+// scratch set in QsEncArgs: qe_stage takes the code words from there, qe_ff_scan and qe_stuff place the segment behind a
+// per-job prefix.  All three are null in every other run, which reads the descriptors and a prefix of 0 as before.
 #include <hip/hip_runtime.h>
 #include "qs_encode.h"
 
@@ -71,9 +75,12 @@ __device__ void qe_stage(const QsEncArgs& a, const QsEncJob& J, int k, int varia
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&J.g[variant]);
   if (t < (int)(sizeof(QsEncGeom) / 4)) reinterpret_cast<uint32_t*>(&S.g)[t] = src[t];
   if (t == 0) S.p = a.p[k];
-  if (t < 32) S.dc[t >> 4][t & 15] = J.dc[t >> 4][t & 15];
-  S.ac[0][t] = J.ac[0][t];
-  S.ac[1][t] = J.ac[1][t];
+  // the code words: the descriptor's, or (whole-file run with optimize) what the table kernel left in the scratch
+  const uint32_t* dc = a.codes ? a.codes + (size_t)(a.job0 + k) * QS_ENC_CODES : &J.dc[0][0];
+  const uint32_t* ac = a.codes ? dc + 2 * 16 : &J.ac[0][0];
+  if (t < 32) S.dc[t >> 4][t & 15] = dc[t];
+  S.ac[0][t] = ac[t];
+  S.ac[1][t] = ac[256 + t];
   __syncthreads();
 }
 
@@ -244,6 +251,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qe_init(QsEncArgs a) {
   const int k = blockIdx.x, t = threadIdx.x;
   const QsEncJob& J = a.jobs[k];
   if (t < (int)(sizeof(QsEncState) / 4)) reinterpret_cast<uint32_t*>(qe_state(a, J))[t] = 0;
+  if (t == 0 && a.prefix && !a.codes) a.prefix[a.job0 + k] = a.fixed[k][qe_variant(a, J, k)];
   if (a.d_counts) {
     uint32_t* h = a.d_counts + (size_t)(a.job0 + k) * 4 * 257;
     for (int i = t; i < 4 * 257; i += QS_ENC_WG) h[i] = (i % 257 == 256) ? 1u : 0u;   // libjpeg's reserved symbol
@@ -541,10 +549,11 @@ __global__ void __launch_bounds__(QS_ENC_WG) qe_ff_scan(QsEncArgs a) {
     }
     return;
   }
-  if (st->dead) {
+  const bool clen = a.tstatus && a.tstatus[a.job0 + k] != 0;     // a table with a code length above 32: status 5
+  if (st->dead || clen) {
     if (t == 0) {
       a.d_len[a.job0 + k] = 0;
-      a.d_status[a.job0 + k] = (st->flags & QS_ENC_F_BADCOEF) ? 1 : 3;
+      a.d_status[a.job0 + k] = (st->flags & QS_ENC_F_BADCOEF) ? 1 : clen ? 5 : 3;
     }
     return;
   }
@@ -560,7 +569,8 @@ __global__ void __launch_bounds__(QS_ENC_WG) qe_ff_scan(QsEncArgs a) {
     carry += total;
   }
   if (t == 0) {
-    const uint64_t len = st->raw_bytes + carry;
+    // (whole-file run: the bytes in front of the segment and behind it count)
+    const uint64_t len = (a.prefix ? a.prefix[a.job0 + k] : 0) + st->raw_bytes + carry + a.tail;
     a.d_len[a.job0 + k] = len;
     a.d_status[a.job0 + k] = len > a.p[k].cap ? 2 : 0;
   }
@@ -576,8 +586,9 @@ __global__ void __launch_bounds__(QS_ENC_WG) qe_stuff(QsEncArgs a) {
   const int lw = wg - J.swg0;
   if (lw >= J.nswg) return;
   const QsEncState* st = qe_state(a, J);
-  if (st->dead) return;
+  if (st->dead || (a.tstatus && a.tstatus[a.job0 + k] != 0)) return;
   const uint64_t U = st->raw_bytes, cap = a.p[k].cap;
+  const uint64_t prefix = a.prefix ? a.prefix[a.job0 + k] : 0;    // whole-file run: where the segment starts in the buffer
   const uint32_t rem = (uint32_t)(st->total_bits & 7), padmask = rem ? (1u << (8 - rem)) - 1u : 0u;
   const uint8_t* raw = a.ws + J.off_raw;
   const uint64_t* ffoff = reinterpret_cast<const uint64_t*>(a.ws + J.off_ffoff);
@@ -624,7 +635,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qe_stuff(QsEncArgs a) {
       }
     __syncthreads();
     const uint64_t c0 = (uint64_t)c * QS_ENC_SCHUNK;
-    const uint64_t base = c0 + ffoff[c];
+    const uint64_t base = prefix + c0 + ffoff[c];
     uint64_t n = (U - c0 < QS_ENC_SCHUNK ? U - c0 : QS_ENC_SCHUNK) + total;
     if (base >= cap) n = 0;
     else if (n > cap - base) n = cap - base;                   // nothing is written at or beyond the capacity

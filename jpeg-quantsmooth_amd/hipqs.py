@@ -113,6 +113,12 @@ class EncodeInfo(C.Structure):
                 ("max_segment_bytes", C.c_uint64)]
 
 
+class EncodeFrame(C.Structure):
+    """qs_hip_encode_frame: the device bytes around the tables and the scan of one job, per geometry variant"""
+    _fields_ = [("d_head", C.c_void_p * 2), ("head_bytes", C.c_uint32 * 2), ("d_mid", C.c_void_p * 2),
+                ("mid_bytes", C.c_uint32 * 2)]
+
+
 class EncodeOpts(C.Structure):
     """qs_hip_encode_opts: the restart interval of one job (in MCUs, or in MCU rows when restart_in_rows > 0)"""
     _fields_ = [("restart_interval", C.c_int32), ("restart_in_rows", C.c_int32)]
@@ -182,6 +188,12 @@ ABI = {
                                                            C.POINTER(C.POINTER(HuffTables)),
                                                            C.POINTER(C.POINTER(EncodeOpts)), C.c_void_p, C.c_size_t,
                                                            C.c_void_p]),
+    "qs_hip_huff_optimal_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qs_hip_encode_files_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "qs_hip_encode_device_batch_files": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(EncodeFrame), C.c_int,
+                                                    C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
     "qs_hip_read_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
                                                  C.POINTER(ReadInfo), C.POINTER(C.c_size_t)]),
     "qs_hip_read_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
@@ -619,6 +631,41 @@ class HipQS:
         """qs_hip_encode_device_batch_histogram: symbol counts uint32[njobs][4][257] (DC 0, DC 1, AC 0, AC 1)"""
         self._check(self.lib.qs_hip_encode_device_batch_histogram(self._job_ptrs(jobs), len(jobs), d_stop, d_counts,
                                                                   d_status, d_workspace, nbytes, stream))
+
+    def huff_optimal_device(self, d_counts: int, ntables: int, d_tables: int, d_status: int, stream=None) -> None:
+        """qs_hip_huff_optimal_device: d_counts = device uint32[ntables][257] -> d_tables = device
+        qs_hip_huff_table[ntables] (273 bytes each: bits[17], huffval[256]), d_status = device int32[ntables] (0, or 5 for
+        a code length above 32); one launch, one wave per table"""
+        self._check(self.lib.qs_hip_huff_optimal_device(d_counts, int(ntables), d_tables, d_status, stream))
+
+    def encode_files_scratch_bytes(self, njobs: int) -> int:
+        """qs_hip_encode_files_scratch_bytes: what encode_batch_files needs as d_scratch for njobs jobs"""
+        return int(self.lib.qs_hip_encode_files_scratch_bytes(int(njobs)))
+
+    @staticmethod
+    def encode_frame(head=(None, None), mid=(None, None)) -> EncodeFrame:
+        """a qs_hip_encode_frame: head / mid = per variant None or (device address, bytes)"""
+        f = EncodeFrame()
+        for v in range(2):
+            for part, ptr, nb in ((head, f.d_head, f.head_bytes), (mid, f.d_mid, f.mid_bytes)):
+                if part[v] is not None:
+                    ptr[v], nb[v] = part[v][0] or None, int(part[v][1])
+        return f
+
+    def encode_batch_files(self, jobs, frames, optimize, d_stop, d_out, capacity, d_len: int, d_status: int, d_tables,
+                           d_scratch: int, scratch_bytes: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_encode_device_batch_files: enqueue whole files -- head, DHT markers (optimize), mid, segment, EOI -- into
+        d_out[i]; frames: None (markers and segment only) or one EncodeFrame per job; d_tables: device
+        qs_hip_huff_tables[njobs] or None; the workspace as encode_batch takes it"""
+        outs, caps = self._outs(d_out, capacity)
+        fr = None
+        if frames is not None:
+            if len(frames) != len(jobs):
+                raise ValueError("one EncodeFrame per job")
+            fr = (EncodeFrame * max(1, len(jobs)))(*frames)
+        self._check(self.lib.qs_hip_encode_device_batch_files(self._job_ptrs(jobs), len(jobs), fr, 1 if optimize else 0,
+                                                              d_stop, outs, caps, d_len, d_status, d_tables, d_scratch,
+                                                              scratch_bytes, d_workspace, nbytes, stream))
 
     # -- device scan reader (a list of device_job() Jobs over the arrays to fill) ---------
     @staticmethod

@@ -46,13 +46,16 @@ def _dht(index: int, table) -> bytes:
     return _marker(0xC4, bytes([index]) + bytes(bits[1:17]) + bytes(int(v) for v in huffval[:n]))
 
 
-def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, dc_tables, ac_tables,
-            restart_interval: int = 0) -> bytes:
-    """-> the whole file.  quants[ci]: 64 quantisers in natural order (None: all ones); dc_tables / ac_tables: the two
-    (bits[17], huffval) pairs each; only the tables the components use are written.  restart_interval: the scan's
-    interval in MCUs; libjpeg writes DRI behind the last DHT whenever it is not 0, also when it exceeds the MCU count"""
+def compose_parts(quants, hsamp, vsamp, colorspace: int, image_size, dc_tables=None, ac_tables=None,
+                  restart_interval: int = 0):
+    """-> (head, mid): the bytes of compose()'s file around its DHT markers and its segment.  head: SOI .. SOF, closed by
+    the DHT markers when dc_tables / ac_tables are given; mid: DRI (when restart_interval is not 0) and the SOS header.
+    head + [the DHT markers, where head has none] + mid + segment + FF D9 is compose()'s file: what the device's whole-file
+    run (qs_hip_encode_device_batch_files) takes as a qs_hip_encode_frame"""
     if not 0 <= int(restart_interval) <= 65535:
         raise ValueError(f"restart_interval {restart_interval}: 0 .. 65535")
+    if (dc_tables is None) != (ac_tables is None):
+        raise ValueError("compose_parts: dc_tables and ac_tables go together")
     n = len(quants)
     ids, tbl, jfif, adobe = COLORSPACES[colorspace][0], table_assignment(colorspace, n), *COLORSPACES[colorspace][2:]
     w, h = image_size
@@ -71,19 +74,28 @@ def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, d
         out.append(_marker(0xDB, bytes([(prec << 4) | ci]) + body))
     sof = struct.pack(">BHHB", 8, h, w, n) + b"".join(bytes([ids[ci], (hsamp[ci] << 4) | vsamp[ci], ci]) for ci in range(n))
     out.append(_marker(0xC1 if wide else 0xC0, sof))
-    sent = set()
-    for ci in range(n):
-        for is_ac, tabs in ((0, dc_tables), (1, ac_tables)):
-            if (is_ac, tbl[ci]) not in sent:
-                sent.add((is_ac, tbl[ci]))
-                out.append(_dht((is_ac << 4) | tbl[ci], tabs[tbl[ci]]))
+    if dc_tables is not None:
+        sent = set()
+        for ci in range(n):
+            for is_ac, tabs in ((0, dc_tables), (1, ac_tables)):
+                if (is_ac, tbl[ci]) not in sent:
+                    sent.add((is_ac, tbl[ci]))
+                    out.append(_dht((is_ac << 4) | tbl[ci], tabs[tbl[ci]]))
+    mid = []
     if restart_interval:
-        out.append(_marker(0xDD, struct.pack(">H", int(restart_interval))))
+        mid.append(_marker(0xDD, struct.pack(">H", int(restart_interval))))
     sos = bytes([n]) + b"".join(bytes([ids[ci], (tbl[ci] << 4) | tbl[ci]]) for ci in range(n)) + bytes([0, 63, 0])
-    out.append(_marker(0xDA, sos))
-    out.append(bytes(segment))
-    out.append(b"\xff\xd9")
-    return b"".join(out)
+    mid.append(_marker(0xDA, sos))
+    return b"".join(out), b"".join(mid)
+
+
+def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, dc_tables, ac_tables,
+            restart_interval: int = 0) -> bytes:
+    """-> the whole file.  quants[ci]: 64 quantisers in natural order (None: all ones); dc_tables / ac_tables: the two
+    (bits[17], huffval) pairs each; only the tables the components use are written.  restart_interval: the scan's
+    interval in MCUs; libjpeg writes DRI behind the last DHT whenever it is not 0, also when it exceeds the MCU count"""
+    head, mid = compose_parts(quants, hsamp, vsamp, colorspace, image_size, dc_tables, ac_tables, restart_interval)
+    return head + mid + bytes(segment) + b"\xff\xd9"
 
 
 # ---- the inverse: the markers of a file in front of its one scan ----------------------------------------------------------

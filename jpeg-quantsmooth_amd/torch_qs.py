@@ -23,7 +23,12 @@ decodes coefficient tensors to pixels on the device (qs_hip_decode_device_batch)
     data = torch_qs.encode(coefs, quants, hsamp=[2, 1, 1], vsamp=[2, 1, 1], colorspace=3, image_size=(1920, 1080),
                            result=res)   # bytes: the JPEG file libjpeg 9 writes from the smoothed arrays
 
-entropy-codes them on the device (qs_hip_encode_device_batch); encode_scan leaves the segment in device memory.
+entropy-codes them on the device (qs_hip_encode_device_batch); encode_scan leaves the segment in device memory, and
+
+    r = torch_qs.encode_file(coefs, quants, hsamp=[2, 1, 1], vsamp=[2, 1, 1], colorspace=3, image_size=(1920, 1080),
+                             result=res)   # r["file"][:r["len"]]: the whole file with optimized tables, in device memory
+
+builds the optimal Huffman tables and the whole file on the device (qs_hip_encode_device_batch_files), capturable.
 
     im = torch_qs.read(data)          # data: the bytes of a JPEG file with restart intervals, on the host or the device
 
@@ -59,6 +64,7 @@ class Workspace:
     def __init__(self, buf=None, key=None):
         self.buf, self.key = buf, key
         self.headers = None          # read_batch: the parsed headers of the files it was prepared with
+        self.files = None            # encode_file_batch: the frames' device bytes and the scratch (a captured graph refers to them)
 
     @property
     def nbytes(self) -> int:
@@ -575,6 +581,169 @@ def encode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
                               image_size=image_size)],
                         result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
                         huffman=huffman, restart_interval=restart_interval, restart_in_rows=restart_in_rows)[0]
+
+
+# ---- optimal tables and whole files on the device (qs_hip_huff_optimal_device, qs_hip_encode_device_batch_files) ----------
+
+TABLES_BYTES = 4 * 273 + 4       # sizeof(qs_hip_huff_tables): dc[2], ac[2] of bits[17] + huffval[256], has_dc[2], has_ac[2]
+
+
+def huff_optimal_device(counts) -> dict:
+    """The optimal Huffman tables of symbol counts, on the device and on the current stream (qs_hip_huff_optimal_device,
+    one wave per table): counts = a contiguous int32 device tensor (..., 257) or (257,), entry 256 ignored -- what
+    encode_histogram_batch returns.  -> dict(bits: uint8 (n, 17), huffval: uint8 (n, 256), status: int32 (n)) over the n
+    tables in order; status 5: a code length above 32 (bits and huffval are then 0), where HipQS.huff_optimal raises.  No
+    host synchronisation."""
+    import torch
+    who = "huff_optimal_device"
+    if not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int32 \
+            or not counts.is_contiguous() or counts.dim() < 1 or counts.shape[-1] != 257 or counts.numel() < 257:
+        raise ValueError(f"{who}: counts must be a contiguous int32 device tensor whose last dimension is 257")
+    n = counts.numel() // 257
+    dev = counts.device
+    tables = torch.empty((n, 273), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _hip().huff_optimal_device(counts.data_ptr(), n, tables.data_ptr(), status.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+    return dict(bits=tables[:, :17], huffval=tables[:, 17:], status=status)
+
+
+def huffman_of_tables(record) -> dict:
+    """one row of encode_file_batch's `tables` (a qs_hip_huff_tables record, uint8[1096]) -> the dict(dc={index: (bits,
+    huffval)}, ac={...}) encode_batch(huffman=...) takes; reads the tensor, which synchronises"""
+    b = bytes(record.cpu().numpy().tobytes()) if hasattr(record, "cpu") else bytes(record)
+    out = dict(dc={}, ac={})
+    for w, (kind, t) in enumerate((("dc", 0), ("dc", 1), ("ac", 0), ("ac", 1))):
+        if b[4 * 273 + w]:
+            bits = list(b[w * 273:w * 273 + 17])
+            out[kind][t] = (bits, list(b[w * 273 + 17:w * 273 + 17 + sum(bits)]))
+    return out
+
+
+def _file_frames(images, result, opts, optimize, huffman, who):
+    """per image and geometry variant the (head, mid) bytes of jpeg_file.compose_parts: variant 0 is what the device codes
+    when stop reads 0 (the replacement chroma at 1x1 when the smoothing made one), variant 1 the original sampling"""
+    from . import jpeg_file
+    hip = _hip()
+    n = len(images)
+    per = huffman if isinstance(huffman, (list, tuple)) else [huffman] * n
+    std = None
+    parts = []
+    for i, im in enumerate(images):
+        res = None if result is None else result["images"][i]
+        ncomp = len(im["coefs"])
+        hs, vs = list(im.get("hsamp") or [1] * ncomp), list(im.get("vsamp") or [1] * ncomp)
+        quants = res["quants"] if res is not None else im.get("quants")
+        if quants is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
+        size = tuple(im["image_size"])
+        variants = [(hs, vs)]
+        if res is not None and res.get("coef_up") is not None:
+            variants = [([int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)),
+                        (hs, vs)]
+        dc = ac = None
+        if not optimize:
+            if std is None:
+                std = dict(dc={t: hip.huff_standard(0, t) for t in (0, 1)}, ac={t: hip.huff_standard(1, t) for t in (0, 1)})
+            h = per[i] or {}
+            dc = {t: (h.get("dc") or {}).get(t, std["dc"][t]) for t in (0, 1)}
+            ac = {t: (h.get("ac") or {}).get(t, std["ac"][t]) for t in (0, 1)}
+        parts.append([jpeg_file.compose_parts(quants, vh, vv, cs, size, dc, ac,
+                                              0 if opts is None else _scan_interval(opts[i], vh, vv, size))
+                      for vh, vv in variants])
+    return parts
+
+
+def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=None, workspace: Workspace | None = None,
+                      restart_interval=None, restart_in_rows=None) -> dict:
+    """Complete baseline JPEG files in device memory, byte for byte what libjpeg 9 writes for jpeg_write_coefficients
+    (encode_batch's files), on the current stream and without host synchronisation: qs_hip_encode_device_batch_files.
+
+    images, result, huffman, restart_interval / restart_in_rows: as encode_batch (quants come from `result` when it is
+    given).  optimize (the default): libjpeg's optimize_coding, with histogram, tables (Annex K.2, one wave per table)
+    and DHT markers made on the device, so the tables follow the data also when a captured graph is replayed; it
+    excludes huffman.  optimize=False: the standard tables, or the caller's.  outs: preallocated contiguous uint8 buffers
+    (their size is the capacity).  workspace: as encode_scan_batch -- inside a graph capture it must come from an earlier
+    call with the same images' geometry, tables, quants and options; it owns the frames' device bytes and the scratch, so
+    keep it alive as long as a graph that was captured with it.
+    For an image with two geometries (a smoothing result with replacement chroma) both variants' markers are composed --
+    variant 1 with the original sampling factors and its own DRI value under restart_in_rows -- and the device takes the
+    one its stop selects, for the head, the mid and the scan alike.
+    Returns dict(files=[uint8 tensors], len=int64 tensor, status=int32 tensor, tables, workspace): file i is
+    files[i][:len[i]] when status[i] is 0.  status as encode_scan_batch, plus 5: a table with a code length above 32
+    (libjpeg's "Huffman code size table overflow").  tables: with optimize a uint8 tensor (len(images), 1096) of
+    qs_hip_huff_tables records (huffman_of_tables reads one), else None."""
+    return _encode_file_batch(images, result, optimize, huffman, outs, workspace, "encode_file_batch",
+                              _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"))
+
+
+def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, opts):
+    import torch
+    if optimize and huffman is not None:
+        raise ValueError(f"{who}: optimize and huffman exclude each other")
+    jobs, dev, stop = _encode_jobs(images, result, who, torch)
+    hip = _hip()
+    n = len(jobs)
+    tabs, tabkey = _huff_tables(hip, huffman, n, who)
+    per, workspace = _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts)
+    parts = _file_frames(images, result, opts, optimize, huffman, who)
+    fkey = (bool(optimize), tuple(tuple(v) for v in parts), str(dev))
+    if workspace.files is None or workspace.files["key"] != fkey:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call with the same "
+                               f"markers (workspace=...): uploading them copies from the host")
+        blob, at = bytearray(), []
+        for variants in parts:
+            at.append([])
+            for head, mid in variants:
+                at[-1].append((len(blob), len(head), len(blob) + len(head), len(mid)))
+                blob += head + mid
+        buf = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+        base = buf.data_ptr()
+        frames = []
+        for variants in at:
+            v = variants + [None] * (2 - len(variants))
+            frames.append(hip.encode_frame(head=[None if e is None else (base + e[0], e[1]) for e in v],
+                                           mid=[None if e is None else (base + e[2], e[3]) for e in v]))
+        nbytes = hip.encode_files_scratch_bytes(n)
+        workspace.files = dict(key=fkey, buf=buf, frames=frames, scratch=torch.empty(nbytes, dtype=torch.uint8, device=dev),
+                               fixed=[max(e[1] + e[3] for e in variants) for variants in at])
+    fs = workspace.files
+    if outs is None:
+        outs = [None] * n
+    if len(outs) != n:
+        raise ValueError(f"{who}: one output (or None) per image")
+    bufs = []
+    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
+        if o is None:
+            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
+            o = torch.empty(fs["fixed"][i] + 4 * 277 + 2 + min(inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks),
+                            dtype=torch.uint8, device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
+                or not o.is_contiguous() or o.numel() < 1:
+            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
+        bufs.append(o)
+    length = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    tables = torch.empty((n, TABLES_BYTES), dtype=torch.uint8, device=dev) if optimize else None
+    hip.encode_batch_files(jobs, fs["frames"], optimize, None if stop is None else stop.data_ptr(),
+                           [o.data_ptr() for o in bufs], [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(),
+                           None if tables is None else tables.data_ptr(), fs["scratch"].data_ptr(), int(fs["scratch"].numel()),
+                           workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    return dict(files=bufs, len=length, status=status, tables=tables, workspace=workspace)
+
+
+def encode_file(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, optimize=True,
+                huffman=None, out=None, workspace: Workspace | None = None, restart_interval=None, restart_in_rows=None) -> dict:
+    """encode_file_batch on one image -> dict(file, len, status, tables, workspace); len and status are device tensors of
+    one element"""
+    r = _encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
+                                 image_size=image_size)],
+                           None if result is None else dict(stop=result["stop"], images=[result]), optimize, huffman,
+                           None if out is None else [out], workspace, "encode_file",
+                           _restart_opts(restart_interval, restart_in_rows, 1, "encode_file"))
+    return dict(file=r["files"][0], len=r["len"], status=r["status"], tables=r["tables"], workspace=r["workspace"])
 
 
 # ---- reading a scan into coefficient tensors (qs_hip_read_device_batch) -----------------------------------------------------

@@ -22,6 +22,13 @@ coefficient arrays to the host (a lower bound of that route by itself) plus libj
 core (tests/libjpeg9_encode.c on a staged input file: its time includes reading the arrays and writing the file).
 Medians of --repeats windows; exits non-zero unless the device route gives libjpeg's bytes and beats the copy alone.
 
+--encode --optimize-files times the whole-file run with optimized tables instead (torch_qs.encode_file_batch: histogram,
+table kernel, coder and framing in one call) on the same three cases with all-ones quant tables, in device time
+(events around windows of calls, medians of --repeats): next to it the device work it replaces -- the histogram run plus
+the plain run -- and, separately, the wall time of the route it replaces as a whole, torch_qs.encode_batch(optimize=True)
+with its two host round trips; and the file sizes with the standard and with the optimized tables.  Exits non-zero
+unless the first file of each case is libjpeg's optimized file.
+
 --read times the device scan reader (torch_qs.read_batch) on the same three cases, on files the device coder wrote with
 --restart N / --restart-rows N: the upload of the file from pinned memory plus the read, and the read alone, next to the
 host route it replaces -- libjpeg 9's jpeg_read_coefficients on one core (tests/libjpeg9_decode.c read: its time
@@ -61,6 +68,8 @@ def main():
                     help="--encode: write a restart marker every N MCUs (libjpeg's restart_interval)")
     ap.add_argument("--restart-rows", type=int, default=None, metavar="N",
                     help="--encode: write a restart marker every N MCU rows (libjpeg's restart_in_rows)")
+    ap.add_argument("--optimize-files", action="store_true",
+                    help="--encode: time the whole-file run with optimized tables next to the histogram run plus the plain run")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
     a = ap.parse_args()
@@ -70,6 +79,8 @@ def main():
         return bench_read(a)
     if a.decode:
         return bench_decode(a)
+    if a.encode and a.optimize_files:
+        return bench_encode_files(a)
     if a.encode:
         return bench_encode(a)
 
@@ -328,6 +339,93 @@ def bench_encode(a):
     if bad:                                                         # the bound of DESIGN.md section 13
         raise SystemExit(f"bench_device_batch --encode: {bad}: the device route must give libjpeg's bytes and be faster "
                          f"than the copy of the coefficient arrays alone")
+
+
+def bench_encode_files(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import synth_image
+    torch_qs = jpegqs_pkg.load().torch_qs
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows) if a.restart or a.restart_rows else {}
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1, amp=30)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
+             (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
+    out = dict(tool="bench_device_batch", leg="encode --optimize-files", device=torch.cuda.get_device_name(dev), results=[])
+    if rst:
+        out["restart"] = rst
+    for name, ims in cases:
+        unit = [np.ones(64, np.uint16)] * len(ims[0]["coefs"])      # what the smoothing leaves: every quantiser 1
+        images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], quants=unit, hsamp=im["hsamp"],
+                       vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
+        wf, wp = torch_qs.Workspace(), torch_qs.Workspace()
+        r = torch_qs.encode_file_batch(images, workspace=wf, **rst)
+        files, lens = r["files"], [int(v) for v in r["len"].cpu().tolist()]
+        assert r["status"].cpu().tolist() == [0] * len(images), "the default capacity did not hold the file"
+        s = torch_qs.encode_file_batch(images, optimize=False, workspace=torch_qs.Workspace(), **rst)
+        std_lens = [int(v) for v in s["len"].cpu().tolist()]
+        assert s["status"].cpu().tolist() == [0] * len(images)
+        del s
+        p = torch_qs.encode_scan_batch(images, workspace=wp, **rst)
+        segs = p["segments"]
+
+        def file_run():
+            torch_qs.encode_file_batch(images, outs=files, workspace=wf, **rst)
+
+        def replaced():
+            torch_qs.encode_histogram_batch(images, workspace=wp, **rst)
+            torch_qs.encode_scan_batch(images, outs=segs, workspace=wp, **rst)
+
+        def histogram_only():
+            torch_qs.encode_histogram_batch(images, workspace=wp, **rst)
+
+        def med(fn, calls):
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(a.repeats):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1) / calls)
+            return round(float(np.median(ms)), 3), [round(m, 3) for m in ms]
+
+        f_ms, f_all = med(file_run, 10)
+        r_ms, r_all = med(replaced, 10)
+        h_ms, _ = med(histogram_only, 10)
+        ts = []
+        for _ in range(3):                                          # the route as a whole, with its host round trips
+            t0 = time.perf_counter()
+            host = torch_qs.encode_batch(images, optimize=True, **rst)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        first = files[0][:lens[0]].cpu().numpy().tobytes()
+        row = dict(case=name, images=len(images), file_run_ms=f_ms, file_run_windows=f_all, histogram_plus_plain_ms=r_ms,
+                   histogram_plus_plain_windows=r_all, histogram_ms=h_ms, over_replaced=round(f_ms / r_ms, 4),
+                   encode_batch_optimize_wall_ms=round(float(np.median(ts)), 1), standard_bytes=sum(std_lens),
+                   optimized_bytes=sum(lens), optimized_over_standard=round(sum(lens) / sum(std_lens), 4),
+                   identical_to_encode_batch=bool(host[0] == first))
+        if rst:
+            row["identical"] = row["identical_to_encode_batch"]      # (libjpeg's file with restarts: tests/test_gpu_encode_files.py)
+        else:
+            with tempfile.TemporaryDirectory() as td:
+                from encode_oracle import LibJpeg9Enc
+                enc = LibJpeg9Enc(Path(td))
+                row["identical"] = bool(enc.write(dict(ims[0], quants=unit), optimize=True) == first)
+        out["results"].append(row)
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    if bad:
+        raise SystemExit(f"bench_device_batch --encode --optimize-files: {bad}: the file is not libjpeg's optimized file")
 
 
 def bench_read(a):
