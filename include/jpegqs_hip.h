@@ -381,7 +381,10 @@ typedef struct {
  * length above 32; precedence 4, 1, 5, 2 (3 cannot occur with optimize).  With 1, 3, 4 or 5 d_len[i] is 0 and the buffer
  * unspecified; with 2 d_len[i] is exact and the buffer holds the file's first out_capacity[i] bytes.
  * d_tables (device, [njobs], may be NULL): with optimize, the tables of each job; has_* is 0 for a table no component
- * uses.  Untouched without optimize.
+ * uses.  After status 5 the table whose code lengths pass 32 has has_* 1 and bits and huffval all 0, as
+ * qs_hip_huff_optimal_device leaves it, and the job's other tables are the valid ones of their counts.  With
+ * status 1 the tables are those of the counts with each refused value clamped to 10 bits (a DC difference to 11) --
+ * all 0 again where they pass 32; with status 4 they are unspecified.  Untouched without optimize.
  * QS_HIP_EINVAL before anything is enqueued: a job whose frames[i] lacks a variant it can take (no SOS header bytes, or a
  * null pointer with a non-zero length; variant 1 counts for a job with two geometries when d_stop is given), and a
  * scratch that is null, misaligned or short. */

@@ -515,7 +515,9 @@ def encode_batch(images, *, result=None, optimize=False, huffman=None, restart_i
     restart_interval / restart_in_rows: as encode_scan_batch; the file gets the DRI marker of the geometry written, and
     optimize counts the symbols of the restart scan.
     Reads len / status, which synchronises; a buffer that proved too small is retried once with the exact size.  Raises
-    ValueError with libjpeg's message where libjpeg would stop."""
+    ValueError with libjpeg's message where libjpeg would stop over a coefficient or a missing code; with optimize, a
+    table whose code lengths pass 32 (libjpeg's "Huffman code size table overflow") raises what HipQS.huff_optimal
+    raises, QsHipError with QS_HIP_EINVAL -- encode_file_batch reports it as status 5."""
     import torch
     from . import jpeg_file
     who = "encode_batch"
