@@ -453,11 +453,17 @@ int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[2
 /* ---- device compress (interleaved uint8 pixels in device memory -> the quantised coefficient arrays of device-resident jobs) ----
  * The inverse of the device decode: the arrays libjpeg 9 holds after jpeg_write_scanlines() -- what jpeg_read_coefficients()
  * returns for the file it writes -- for the same pixels, quant tables, sampling factors and colour space, bit for bit, with
- *   dct_method = JDCT_ISLOW (8x8 jpeg_fdct_islow for every component), smoothing_factor = 0 and
- *   do_fancy_downsampling = FALSE (box-filter chroma downsampling, jcsample.c).
- * OUT OF SCOPE: libjpeg 9's default do_fancy_downsampling = TRUE, which compresses 2x-subsampled chroma through 16-point
- * scaled forward DCTs (jpeg_fdct_16x16, _16x8, _8x16) and gives other coefficients wherever chroma is subsampled.  The
- * `fancy` argument of info / prepare is there for it: anything but 0 is QS_HIP_ENOTSUP today.
+ *   dct_method = JDCT_ISLOW, smoothing_factor = 0 and either chroma downsampling of libjpeg 9, chosen per job:
+ *   QS_HIP_DOWNSAMPLE_BOX  do_fancy_downsampling = FALSE: box-filter chroma downsampling (jcsample.c), then the 8x8
+ *                          jpeg_fdct_islow for every component.  What info / prepare without opts do.
+ *   QS_HIP_DOWNSAMPLE_DCT  do_fancy_downsampling = TRUE, libjpeg 9's default (cjpeg, jpeg_set_defaults): 2x-subsampled
+ *                          chroma goes through 16-point scaled forward DCTs instead of a box -- jpeg_fdct_16x16 of the
+ *                          full-resolution samples for luma 2x2, jpeg_fdct_16x8 for 2x1, jpeg_fdct_8x16 for 1x2, the h2v1
+ *                          box and then jpeg_fdct_16x8 for 4x1 -- and gives other chroma coefficients wherever chroma is
+ *                          subsampled.  Luma, grayscale and 1x1 chroma are the same in both modes.  The inverse of the
+ *                          device decode's chroma upsampling.  Through the _opts calls below.
+ * OUT OF SCOPE: smoothing_factor != 0 and the other DCT methods (JDCT_IFAST, JDCT_FLOAT).
+ * The `fancy` argument of info / prepare keeps its meaning: anything but 0 is QS_HIP_ENOTSUP (use the _opts calls).
  * Jobs are qs_hip_job records as the decode takes them, with coef[ci] the DEVICE arrays to FILL (wblk as the row stride,
  * 16-byte aligned), quant tables required (1 .. 65535, natural order, one per component; a 0: QS_HIP_EINVAL) and
  * image_width x image_height required.  Layouts, derived from ncomp and colorspace as in qs_hip_decode_info:
@@ -468,7 +474,8 @@ int qs_hip_huff_standard(int is_ac, int tbl, uint8_t bits[17], uint8_t huffval[2
  * height_in_blocks (QS_HIP_EINVAL otherwise; info reports them); exactly these blocks are written -- the blocks of a
  * larger array outside libjpeg's geometry (the dummy blocks of edge MCUs among them) are left as they are.  Edges follow
  * libjpeg: the right edge is replicated before downsampling; at the bottom the image is padded to a multiple of
- * max_v_samp rows with its last row, downsampled, and then the last DOWNSAMPLED row of each component is repeated.
+ * max_v_samp rows with its last row, downsampled, and then the last DOWNSAMPLED row of each component is repeated (BOX);
+ * the components that DCT scales take plain clamps, source column min(x, width - 1) and source row min(y, height - 1).
  * The same three-call pattern:
  *   info     per_job[i] = input shape, layout and block geometry of jobs[i]; *workspace_bytes; no device touched;
  *   prepare  writes the per-job descriptors (geometry, tables, their reciprocals) into the workspace; may synchronise
@@ -490,6 +497,20 @@ int qs_hip_compress_device_batch_prepare(qs_hip_job *const *jobs, int njobs, int
 		void *stream);
 int qs_hip_compress_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_pixels, const size_t *pitch,
 		void *d_workspace, size_t bytes, void *stream);
+/* info / prepare with opts[i] for job i: opts NULL or opts[i] NULL is QS_HIP_DOWNSAMPLE_BOX, exactly info / prepare
+ * with fancy = 0.  Any other value of `downsampling`, or a non-zero `reserved`: QS_HIP_EINVAL.  A batch may mix modes;
+ * geometry (per_job, *workspace_bytes) does not depend on the mode.  The run call is unchanged: it works in the mode
+ * the last prepare wrote into the workspace's descriptors. */
+#define QS_HIP_DOWNSAMPLE_BOX 0   /* do_fancy_downsampling = FALSE */
+#define QS_HIP_DOWNSAMPLE_DCT 1   /* libjpeg 9's default: 2x chroma through 16-point scaled forward DCTs */
+typedef struct {
+	int32_t downsampling;   /* QS_HIP_DOWNSAMPLE_* */
+	int32_t reserved[3];    /* 0 */
+} qs_hip_compress_opts;
+int qs_hip_compress_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_compress_opts *const *opts,
+		qs_hip_compress_info *per_job, size_t *workspace_bytes);
+int qs_hip_compress_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_compress_opts *const *opts,
+		void *d_workspace, size_t bytes, void *stream);
 
 void qs_hip_free(void *p);
 /* the job layer keeps freed device buffers (up to 6 GiB per device), pinned staging buffers (up
@@ -510,7 +531,7 @@ const char *qs_hip_last_error(void);
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
  * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
- * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files).  A caller built against
+ * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

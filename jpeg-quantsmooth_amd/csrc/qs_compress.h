@@ -1,22 +1,31 @@
 // qs_compress.h -- the device compress of pixels to quantised coefficient arrays (qs_hip_compress_device_batch,
-// csrc/qs_kernels_compress.hip): libjpeg 9's RGB -> YCbCr conversion (jccolor.c), its edge replication and box-filter
-// chroma downsampling (jcprepct.c, jcsample.c with do_fancy_downsampling = FALSE), jpeg_fdct_islow (jfdctint.c) and the
-// quantiser of jcdctmgr.c, as functions the kernel and a host build (tests/compress_host.cpp) can both compile, and the
-// per-job descriptor the host driver writes into the caller's workspace.
+// csrc/qs_kernels_compress.hip): libjpeg 9's RGB -> YCbCr conversion (jccolor.c), its edge replication and both of its
+// chroma downsamplings -- the box filter of do_fancy_downsampling = FALSE (jcprepct.c, jcsample.c) with jpeg_fdct_islow,
+// and its default, 2x chroma through the scaled forward DCTs jpeg_fdct_16x16 / _16x8 / _8x16 (jfdctint.c) -- and the
+// quantiser of jcdctmgr.c, as functions the kernel and the host builds (tests/compress_host.cpp,
+// tests/compress_fancy_host.cpp) can both compile, and the per-job descriptor the host driver writes into the caller's
+// workspace.
 //
-// OUT OF SCOPE: libjpeg 9's default do_fancy_downsampling = TRUE compresses 2x-subsampled chroma through 16-point
-// scaled forward DCTs (jpeg_fdct_16x16, _16x8, _8x16) instead of a box filter and an 8x8 DCT.  That mode is not
-// implemented; the entry points refuse it (QS_HIP_ENOTSUP).  For 1x1 chroma and grayscale the two modes coincide.
+// Covered: JDCT_ISLOW with either downsampling, per job (QsCmpJob::mode).  OUT OF SCOPE: smoothing_factor != 0 and the
+// other DCT methods (JDCT_IFAST, JDCT_FLOAT).  For 1x1 chroma and grayscale the two modes coincide.
 //
 // Numerical contract: everything fits wrapping 32-bit arithmetic for 8-bit samples.
 //   colour:  |FIX(c) * s| <= 65536 * 255 per term, three terms plus (128 << 16) + 32767 < 2^26.
-//   pass 1:  a row's outputs are sum_k M[i][k] * x[k] with |M[i][k]| <= 2^13 * sqrt(2) * 1.0004 < 11590 (the composed
-//            FIX() constants); the AC rows of M sum to zero, so x may be taken as x - 128, |x - 128| <= 128:
-//            |sum| <= 8 * 11590 * 128 + 2^10 < 2^24, stored >> 11: |d| <= 5796.  DC: (sum - 1024) << 2, |d| <= 4096.
-//   pass 2:  |sum_k M[i][k] * d[k]| + 2^14 <= 8 * 11590 * 5796 + 2^14 < 2^29.01 < 2^31.
+// Each DCT pass is an integer matrix M (the composed FIX() constants) and one rounding shift.  The matrices are taken
+// with unit vectors from a host build (tests/compress_fancy_host.cpp norms; asserted in
+// tests/test_compress_fancy_host.py): row 0 is the plain sum (L1 norm 8 or 16); every other row sums to zero, so x may be
+// taken as x - 128, |x - 128| <= 128; the largest row L1 norm is 60 548 for the 8-point pass (row 4 of it is a
+// butterfly of norm 8, scaled << 2) and 121 088 for the 16-point pass -- not the crude 8 or 16 times 11 590.
+//   pass 1:  8-point  |sum| <=  60 548 * 128 + 2^10 < 2^23, stored >> 11: |d| <= 3 784; DC (sum - 1024) << 2: |d| <= 4 096.
+//            16-point |sum| <= 121 088 * 128 + 2^10 < 2^24, stored >> 11: |d| <= 7 568; DC (sum - 2048) << 2: |d| <= 8 192.
+//   pass 2:  a column of |d| <= dmax through either matrix, plus the rounding term:
+//            8x8    60 548 * 4 096 + 2^14 < 2^27.9        16x8  60 548 * 8 192 + 2^15 < 2^28.9
+//            8x16  121 088 * 4 096 + 2^15 < 2^28.9        16x16 121 088 * 8 192 + 2^16 = 992 018 432 < 2^29.9
+// The crude bound 16 * 11 590 * 11 590 passes 2^31 for the second pass of _16x16 (libjpeg's INT32 is a 64-bit long
+// there); the measured norms leave a factor 2.16 of room, so NO pass needs 64-bit arithmetic.
 // Every final sum fits int32, so sums and products taken modulo 2^32 (uint32_t here) agree with the true ones: a value
-// in [-2^31, 2^31) is its own residue, whatever the intermediates did.  After pass 2's >> 15 (>> 2 for the two
-// butterfly outputs) |w| <= 2^14.01 < 2^17, the domain over which the quantiser's reciprocal is proven below.
+// in [-2^31, 2^31) is its own residue, whatever the intermediates did.  After pass 2's shifts |w| <= 8 192 (the DC of an
+// all-0 block; 7 569 elsewhere) < 2^17, the domain over which the quantiser's reciprocal is proven below.
 #pragma once
 #include <stdint.h>
 
@@ -45,6 +54,7 @@ struct QsCmpJob {
   int32_t stride[3];             // the caller's row stride in blocks (its wblk >= wib)
   int32_t tiles_x;               // tiles per tile row
   int32_t tile0, tiles;          // first workgroup of this job in its chunk's launch, and how many it has
+  int32_t mode, pad;             // QS_CMP_DS_*: what chroma goes through (qc_chroma_shape)
   uint16_t q[3][64];             // the components' tables (natural order)
   uint32_t recip[3][64];         // qc_recip(q << 3)
 };
@@ -143,6 +153,64 @@ QS_CMP_HD void qc_fdct_col(const int32_t* d, int32_t* w) {
   for (int k = 0; k < 8; ++k) w[k] = (int32_t)o[k] >> ((k & 3) ? 15 : 2);
 }
 
+// ---- jfdctint.c: the 16-point pass of jpeg_fdct_16x16 / _16x8 / _8x16 (cK = sqrt(2) * cos(K * pi / 32)) --------------
+// 16 inputs -> the 8 low-frequency sums BEFORE rounding and shift: o[0] is the plain sum of the inputs, o[1..7] carry
+// 2^CONST_BITS.  T is uint32_t (wrapping; exact whenever the final sums fit int32, see the contract above) or int64_t.
+template <class T>
+QS_CMP_HD void qc_fdct16(const T* in, T* o) {
+#define QC_F(x) ((T)(int32_t)((x) * 8192 + 0.5))
+  T tmp0 = in[0] + in[15], tmp1 = in[1] + in[14], tmp2 = in[2] + in[13], tmp3 = in[3] + in[12];
+  T tmp4 = in[4] + in[11], tmp5 = in[5] + in[10], tmp6 = in[6] + in[9], tmp7 = in[7] + in[8];
+  T tmp10 = tmp0 + tmp7, tmp14 = tmp0 - tmp7, tmp11 = tmp1 + tmp6, tmp15 = tmp1 - tmp6;
+  T tmp12 = tmp2 + tmp5, tmp16 = tmp2 - tmp5, tmp13 = tmp3 + tmp4, tmp17 = tmp3 - tmp4;
+  tmp0 = in[0] - in[15]; tmp1 = in[1] - in[14]; tmp2 = in[2] - in[13]; tmp3 = in[3] - in[12];
+  tmp4 = in[4] - in[11]; tmp5 = in[5] - in[10]; tmp6 = in[6] - in[9]; tmp7 = in[7] - in[8];
+  o[0] = tmp10 + tmp11 + tmp12 + tmp13;
+  o[4] = (tmp10 - tmp13) * QC_F(1.306562965) + (tmp11 - tmp12) * QC_F(0.541196100);       // c4, c12
+  tmp10 = (tmp17 - tmp15) * QC_F(0.275899379) + (tmp14 - tmp16) * QC_F(1.387039845);      // c14, c2
+  o[2] = tmp10 + tmp15 * QC_F(1.451774982) + tmp16 * QC_F(2.172734804);                   // c6+c14, c2+c10
+  o[6] = tmp10 - tmp14 * QC_F(0.211164243) - tmp17 * QC_F(1.061594338);                   // c2-c6, c10+c14
+  tmp11 = (tmp0 + tmp1) * QC_F(1.353318001) + (tmp6 - tmp7) * QC_F(0.410524528);          // c3, c13
+  tmp12 = (tmp0 + tmp2) * QC_F(1.247225013) + (tmp5 + tmp7) * QC_F(0.666655658);          // c5, c11
+  tmp13 = (tmp0 + tmp3) * QC_F(1.093201867) + (tmp4 - tmp7) * QC_F(0.897167586);          // c7, c9
+  tmp14 = (tmp1 + tmp2) * QC_F(0.138617169) + (tmp6 - tmp5) * QC_F(1.407403738);          // c15, c1
+  tmp15 = (T)0 - (tmp1 + tmp3) * QC_F(0.666655658) - (tmp4 + tmp6) * QC_F(1.247225013);   // -c11, -c5
+  tmp16 = (T)0 - (tmp2 + tmp3) * QC_F(1.353318001) + (tmp5 - tmp4) * QC_F(0.410524528);   // -c3, c13
+  o[1] = tmp11 + tmp12 + tmp13 - tmp0 * QC_F(2.286341144) + tmp7 * QC_F(0.779653625);
+  o[3] = tmp11 + tmp14 + tmp15 + tmp1 * QC_F(0.071888074) - tmp6 * QC_F(1.663905119);
+  o[5] = tmp12 + tmp14 + tmp16 - tmp2 * QC_F(1.125726048) + tmp5 * QC_F(1.227391138);
+  o[7] = tmp13 + tmp15 + tmp16 + tmp3 * QC_F(1.065388962) + tmp4 * QC_F(2.167985692);
+#undef QC_F
+}
+
+// pass 1 of _16x16 and _16x8: one row of 16 samples -> 8 values scaled by 2^PASS1_BITS (16 * CENTERJSAMPLE leaves the
+// sum; the other rows of the matrix sum to zero).  Wrapping 32 bits: |sum| < 2^24 (contract above).
+QS_CMP_HD void qc_fdct16_row(const uint8_t* s, int32_t* d) {
+  uint32_t in[16], o[8];
+  for (int k = 0; k < 16; ++k) in[k] = s[k];
+  qc_fdct16<uint32_t>(in, o);
+  d[0] = (int32_t)((o[0] - 16u * 128u) << 2);
+  for (int k = 1; k < 8; ++k) d[k] = (int32_t)(o[k] + (1u << 10)) >> 11;
+}
+
+// pass 2 of _16x16 (extra = 2: the output scaled by (8/16)^2) and of _8x16 (extra = 1: by 8/16): one column of 16
+// pass-1 values -> 8 outputs, left scaled by 8
+QS_CMP_HD void qc_fdct16_col(const int32_t* d, int extra, int32_t* w) {
+  uint32_t in[16], o[8];
+  for (int k = 0; k < 16; ++k) in[k] = (uint32_t)d[k];
+  qc_fdct16<uint32_t>(in, o);
+  w[0] = (int32_t)(o[0] + (1u << (1 + extra))) >> (2 + extra);
+  for (int k = 1; k < 8; ++k) w[k] = (int32_t)(o[k] + (1u << (14 + extra))) >> (15 + extra);
+}
+
+// pass 2 of _16x8: the 8-point column pass with one more bit removed (the output scaled by 8/16)
+QS_CMP_HD void qc_fdct_col_half(const int32_t* d, int32_t* w) {
+  uint32_t in[8], o[8];
+  for (int k = 0; k < 8; ++k) in[k] = (uint32_t)d[k];
+  qc_fdct8(in, 1u << 2, 1u << 15, o);
+  for (int k = 0; k < 8; ++k) w[k] = (int32_t)o[k] >> ((k & 3) ? 16 : 3);
+}
+
 // ---- jcdctmgr.c: forward_DCT's quantiser for JDCT_ISLOW, divisor d = quantval << 3 ------------------------------------
 // coef = sign(w) * ((|w| + (d >> 1)) / d), exact integer division.  The division is a multiplication by
 // m = floor(2^32 / d) and one correction: for 0 <= a < 2^32 and 8 <= d < 2^19, with e = 2^32 / d - m in [0, 1),
@@ -155,6 +223,29 @@ QS_CMP_HD int16_t qc_quant(int32_t w, uint32_t q, uint32_t m) {
   uint32_t t = (uint32_t)(((uint64_t)a * m) >> 32);
   if (a - t * d >= d) ++t;
   return (int16_t)(w < 0 ? -(int32_t)t : (int32_t)t);
+}
+
+// ---- what chroma goes through (jcmaster.c, jcsample.c, jcdctmgr.c), per downsampling mode -----------------------------
+// With luma hs x vs and chroma 1x1, one chroma block covers 8 hs x 8 vs pixels.  QS_CMP_DS_BOX: a box of hs x vs, then the
+// 8x8 DCT.  QS_CMP_DS_DCT (do_fancy_downsampling = TRUE): libjpeg scales the component's DCT up to 2x each way
+// (DCT_h_scaled_size 16 where hs >= 2, DCT_v_scaled_size 16 where vs == 2) and downsamples only what is left: the
+// h2v1 box for 4x1, nothing otherwise.  Edges are plain clamps there: source column min(x, W - 1), source row
+// min(y, H - 1) (the expanded-edge rows of jcprepct.c; no downsampled row is repeated, since none is made).
+#define QS_CMP_DS_BOX 0
+#define QS_CMP_DS_DCT 1
+struct QsCmpShape {
+  int bh, bv;                    // the box in front of the DCT
+  int dw, dh;                    // samples one block's DCT takes: 8 or 16 each way
+};
+QS_CMP_HD QsCmpShape qc_chroma_shape(int mode, int hs, int vs) {
+  QsCmpShape s;
+  if (mode == QS_CMP_DS_DCT) {
+    s.bh = hs == 4 ? 2 : 1; s.bv = 1;
+    s.dw = hs >= 2 ? 16 : 8; s.dh = vs == 2 ? 16 : 8;
+  } else {
+    s.bh = hs; s.bv = vs; s.dw = 8; s.dh = 8;
+  }
+  return s;
 }
 
 // libjpeg's geometry of component ci: width_in_blocks / height_in_blocks for a sampling factor `samp` of `max`

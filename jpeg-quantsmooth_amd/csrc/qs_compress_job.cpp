@@ -1,10 +1,12 @@
 // qs_compress_job.cpp -- the device compress of the flat C ABI (include/jpegqs_hip.h):
-// qs_hip_compress_device_batch_info / _prepare / qs_hip_compress_device_batch.  The coefficient arrays libjpeg 9 holds
-// after jpeg_write_scanlines (JDCT_ISLOW, smoothing_factor 0, do_fancy_downsampling FALSE) for device-resident pixels,
-// written into the arrays of qs_hip_job records, every job of a batch in one launch (qs_kernels_compress.hip).
-// libjpeg 9's default, fancy downsampling, is out of scope: fancy != 0 is QS_HIP_ENOTSUP.
+// qs_hip_compress_device_batch_info / _prepare (and their _opts forms) / qs_hip_compress_device_batch.  The coefficient
+// arrays libjpeg 9 holds after jpeg_write_scanlines (JDCT_ISLOW, smoothing_factor 0) for device-resident pixels, written
+// into the arrays of qs_hip_job records, every job of a batch in one launch (qs_kernels_compress.hip).  The chroma
+// downsampling is per job (qs_hip_compress_opts): the box filter of do_fancy_downsampling FALSE, which is what the
+// calls without opts do, or libjpeg 9's default, 2x chroma through 16-point scaled forward DCTs.  The `fancy` argument
+// of the calls without opts keeps its meaning: anything but 0 is QS_HIP_ENOTSUP.
 //
-// Workspace: one QsCmpJob per job (geometry, tables and their reciprocals, the job's tiles in its chunk's launch),
+// Workspace: one QsCmpJob per job (geometry, mode, tables and their reciprocals, the job's tiles in its chunk's launch),
 // written by prepare; its layout and contents are a function of the jobs' geometry and tables alone.  The run passes
 // the pixels and the arrays in the kernel arguments, QS_CMP_CHUNK jobs per launch.
 #include "qs_common.h"
@@ -117,8 +119,8 @@ struct Who {
 
 // the descriptors of a batch and, with d_pix (the run), the kernel-argument records; the tile prefix restarts with
 // every chunk of QS_CMP_CHUNK jobs (one launch each)
-int describe_all(qs_hip_job* const* jobs, int njobs, const uint8_t* const* d_pix, const size_t* pitch,
-                 std::vector<QsCmpJob>& D, std::vector<QsCmpPtrs>* P, qs_hip_compress_info* info, const char* who) {
+int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts* const* opts,
+                 const uint8_t* const* d_pix, const size_t* pitch, std::vector<QsCmpJob>& D, std::vector<QsCmpPtrs>* P, qs_hip_compress_info* info, const char* who) {
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   if (d_pix && !pitch) return qs_fail(QS_HIP_EINVAL, "%s: null pitch", who);
   D.assign((size_t)njobs, QsCmpJob());
@@ -129,6 +131,14 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const uint8_t* const* d_pix
     if (d_pix && !pix) return qs_fail(QS_HIP_EINVAL, "%s: job %d has no pixels", who, i);
     if (int r = describe(jobs[i], pix, d_pix ? pitch[i] : 0, &D[i], P ? &(*P)[i] : nullptr, info ? &info[i] : nullptr,
                          Who(who, i).s)) return r;
+    if (const qs_hip_compress_opts* o = opts ? opts[i] : nullptr) {
+      if (o->downsampling != QS_HIP_DOWNSAMPLE_BOX && o->downsampling != QS_HIP_DOWNSAMPLE_DCT)
+        return qs_fail(QS_HIP_EINVAL, "%s: job %d: downsampling %d (QS_HIP_DOWNSAMPLE_BOX or QS_HIP_DOWNSAMPLE_DCT)", who, i,
+                       o->downsampling);
+      if (o->reserved[0] || o->reserved[1] || o->reserved[2])
+        return qs_fail(QS_HIP_EINVAL, "%s: job %d: the reserved fields of qs_hip_compress_opts must be 0", who, i);
+      D[i].mode = o->downsampling == QS_HIP_DOWNSAMPLE_DCT ? QS_CMP_DS_DCT : QS_CMP_DS_BOX;
+    }
     if (i % QS_CMP_CHUNK == 0) tiles = 0;
     D[i].tile0 = (int)tiles;
     tiles += D[i].tiles;
@@ -148,8 +158,9 @@ int check_ws(int njobs, const void* d_workspace, size_t bytes, const char* who) 
 
 int no_fancy(int fancy, const char* who) {
   if (fancy)
-    return qs_fail(QS_HIP_ENOTSUP, "%s: fancy downsampling (libjpeg 9's default: 2x chroma through 16-point scaled DCTs) "
-                   "is not implemented; pass 0 for the box filter of do_fancy_downsampling = FALSE", who);
+    return qs_fail(QS_HIP_ENOTSUP, "%s: fancy != 0 is refused: pass 0 for the box filter of do_fancy_downsampling = FALSE; "
+                   "libjpeg 9's default (2x chroma through 16-point scaled DCTs) is QS_HIP_DOWNSAMPLE_DCT of the _opts "
+                   "calls", who);
   return QS_HIP_OK;
 }
 
@@ -169,34 +180,60 @@ template <class F> int guarded(F f) {
   }
 }
 
+
+
+int info_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts* const* opts, int fancy,
+              qs_hip_compress_info* per_job, size_t* bytes, const char* who) {
+  if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
+  std::vector<QsCmpJob> D;
+  if (int r = describe_all(jobs, njobs, opts, nullptr, nullptr, D, nullptr, per_job, who)) return r;
+  if (int r = no_fancy(fancy, who)) return r;
+  *bytes = workspace_bytes(njobs);
+  return QS_HIP_OK;
+}
+
+int prepare_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts* const* opts, int fancy,
+                 void* d_workspace, size_t bytes, void* stream, const char* who) {
+  std::vector<QsCmpJob> D;
+  if (int r = describe_all(jobs, njobs, opts, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
+  if (int r = no_fancy(fancy, who)) return r;
+  if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
+  if (int r = device_ok()) return r;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsCmpJob), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));                        // (a pageable source: it must outlive the copy)
+  return QS_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" int qs_hip_compress_device_batch_info(qs_hip_job* const* jobs, int njobs, int fancy,
                                                  qs_hip_compress_info* per_job, size_t* bytes) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_compress_device_batch_info";
-    if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
-    std::vector<QsCmpJob> D;
-    if (int r = describe_all(jobs, njobs, nullptr, nullptr, D, nullptr, per_job, who)) return r;
-    if (int r = no_fancy(fancy, who)) return r;
-    *bytes = workspace_bytes(njobs);
-    return QS_HIP_OK;
+    return info_impl(jobs, njobs, nullptr, fancy, per_job, bytes, "qs_hip_compress_device_batch_info");
+  });
+}
+
+extern "C" int qs_hip_compress_device_batch_info_opts(qs_hip_job* const* jobs, int njobs,
+                                                      const qs_hip_compress_opts* const* opts,
+                                                      qs_hip_compress_info* per_job, size_t* bytes) {
+  return guarded([&]() -> int {
+    return info_impl(jobs, njobs, opts, 0, per_job, bytes, "qs_hip_compress_device_batch_info_opts");
   });
 }
 
 extern "C" int qs_hip_compress_device_batch_prepare(qs_hip_job* const* jobs, int njobs, int fancy, void* d_workspace,
                                                     size_t bytes, void* stream) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_compress_device_batch_prepare";
-    std::vector<QsCmpJob> D;
-    if (int r = describe_all(jobs, njobs, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
-    if (int r = no_fancy(fancy, who)) return r;
-    if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
-    if (int r = device_ok()) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsCmpJob), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
-    return QS_HIP_OK;
+    return prepare_impl(jobs, njobs, nullptr, fancy, d_workspace, bytes, stream, "qs_hip_compress_device_batch_prepare");
+  });
+}
+
+extern "C" int qs_hip_compress_device_batch_prepare_opts(qs_hip_job* const* jobs, int njobs,
+                                                         const qs_hip_compress_opts* const* opts, void* d_workspace,
+                                                         size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    return prepare_impl(jobs, njobs, opts, 0, d_workspace, bytes, stream, "qs_hip_compress_device_batch_prepare_opts");
   });
 }
 
@@ -207,7 +244,7 @@ extern "C" int qs_hip_compress_device_batch(qs_hip_job* const* jobs, int njobs, 
     std::vector<QsCmpJob> D;
     std::vector<QsCmpPtrs> P;
     if (!d_pixels) return qs_fail(QS_HIP_EINVAL, "%s: null d_pixels", who);
-    if (int r = describe_all(jobs, njobs, d_pixels, pitch, D, &P, nullptr, who)) return r;
+    if (int r = describe_all(jobs, njobs, nullptr, d_pixels, pitch, D, &P, nullptr, who)) return r;
     if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -97,6 +97,11 @@ class CompressInfo(C.Structure):
                 ("wblk", C.c_int32 * MAXC), ("hblk", C.c_int32 * MAXC)]
 
 
+class CompressOpts(C.Structure):
+    """qs_hip_compress_opts: the chroma downsampling of one job of the device compress (DOWNSAMPLE_BOX / DOWNSAMPLE_DCT)"""
+    _fields_ = [("downsampling", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class HuffTable(C.Structure):
     """qs_hip_huff_table: bits[l] = codes of length l, huffval = the symbols by increasing code length"""
     _fields_ = [("bits", C.c_uint8 * 17), ("huffval", C.c_uint8 * 256)]
@@ -139,6 +144,9 @@ class ReadInfo(C.Structure):
 
 MAX_PLANES = 56
 COMPRESS_CHUNK = 44              # QS_HIP_COMPRESS_CHUNK: jobs per launch of the device compress
+DOWNSAMPLE_BOX = 0               # QS_HIP_DOWNSAMPLE_BOX: do_fancy_downsampling = FALSE
+DOWNSAMPLE_DCT = 1               # QS_HIP_DOWNSAMPLE_DCT: libjpeg 9's default, 2x chroma through 16-point scaled DCTs
+DOWNSAMPLING = {"box": DOWNSAMPLE_BOX, "dct": DOWNSAMPLE_DCT}
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 # every symbol include/jpegqs_hip.h declares: (restype, argtypes)
@@ -204,6 +212,12 @@ ABI = {
                                                      C.POINTER(C.c_size_t)]),
     "qs_hip_compress_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                         C.c_void_p]),
+    "qs_hip_compress_device_batch_info_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                          C.POINTER(C.POINTER(CompressOpts)), C.POINTER(CompressInfo),
+                                                          C.POINTER(C.c_size_t)]),
+    "qs_hip_compress_device_batch_prepare_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                             C.POINTER(C.POINTER(CompressOpts)), C.c_void_p, C.c_size_t,
+                                                             C.c_void_p]),
     "qs_hip_compress_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_huff_optimal": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
@@ -533,14 +547,41 @@ class HipQS:
                                                         d_workspace, nbytes, stream))
 
     # -- device compress of pixels (a list of device_job() Jobs over the arrays to fill) ---
-    def compress_batch_info(self, jobs, fancy: bool = False):
-        """qs_hip_compress_device_batch_info (no device needed) -> (list of dict(width, height, channels, layout, wblk,
-        hblk: libjpeg's block geometry per component), the batch's workspace bytes).  fancy: libjpeg 9's default
-        do_fancy_downsampling, not implemented (QS_HIP_ENOTSUP)"""
+    @staticmethod
+    def _compress_opt_ptrs(opts, n):
+        """opts: one entry per job -- None (the box mode), "box" / "dct", a DOWNSAMPLE_* value or a CompressOpts -> (the
+        pointer array, what it points to: keep it alive over the call)"""
+        if len(opts) != n:
+            raise ValueError(f"compress opts: {len(opts)} entries for {n} jobs")
+        keep = []
+        for o in opts:
+            if o is None or isinstance(o, CompressOpts):
+                keep.append(o)
+                continue
+            if isinstance(o, str):
+                if o not in DOWNSAMPLING:
+                    raise ValueError(f"compress opts: downsampling {o!r} (one of {sorted(DOWNSAMPLING)})")
+                o = DOWNSAMPLING[o]
+            rec = CompressOpts()
+            rec.downsampling = int(o)
+            keep.append(rec)
+        arr = (C.POINTER(CompressOpts) * max(1, n))(*[C.pointer(o) if o is not None else None for o in keep])
+        return arr, keep
+
+    def compress_batch_info(self, jobs, fancy: bool = False, opts=None):
+        """qs_hip_compress_device_batch_info[_opts] (no device needed) -> (list of dict(width, height, channels, layout,
+        wblk, hblk: libjpeg's block geometry per component), the batch's workspace bytes).  opts: None (the call without
+        opts: every job in the box mode), or one entry per job: None, "box", "dct" (libjpeg 9's default DCT-scaled
+        chroma downsampling) or a CompressOpts.  fancy: the old argument, still refused (QS_HIP_ENOTSUP)"""
         per = (CompressInfo * max(1, len(jobs)))()
         total = C.c_size_t(0)
-        self._check(self.lib.qs_hip_compress_device_batch_info(self._job_ptrs(jobs), len(jobs), int(bool(fancy)), per,
-                                                               C.byref(total)))
+        if opts is None or fancy:
+            self._check(self.lib.qs_hip_compress_device_batch_info(self._job_ptrs(jobs), len(jobs), int(bool(fancy)), per,
+                                                                   C.byref(total)))
+        else:
+            arr, _keep = self._compress_opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_compress_device_batch_info_opts(self._job_ptrs(jobs), len(jobs), arr, per,
+                                                                        C.byref(total)))
         out = []
         for i, job in enumerate(jobs):
             n = int(job.ncomp)
@@ -548,11 +589,17 @@ class HipQS:
                             layout=int(per[i].layout), wblk=list(per[i].wblk[:n]), hblk=list(per[i].hblk[:n])))
         return out, int(total.value)
 
-    def compress_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, fancy: bool = False) -> None:
-        """qs_hip_compress_device_batch_prepare: geometry and tables into the workspace (synchronises `stream`; not
-        inside a capture)"""
-        self._check(self.lib.qs_hip_compress_device_batch_prepare(self._job_ptrs(jobs), len(jobs), int(bool(fancy)),
-                                                                  d_workspace, nbytes, stream))
+    def compress_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, fancy: bool = False,
+                               opts=None) -> None:
+        """qs_hip_compress_device_batch_prepare[_opts]: geometry, modes and tables into the workspace (synchronises
+        `stream`; not inside a capture); opts as compress_batch_info takes them"""
+        if opts is None or fancy:
+            self._check(self.lib.qs_hip_compress_device_batch_prepare(self._job_ptrs(jobs), len(jobs), int(bool(fancy)),
+                                                                      d_workspace, nbytes, stream))
+        else:
+            arr, _keep = self._compress_opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_compress_device_batch_prepare_opts(self._job_ptrs(jobs), len(jobs), arr,
+                                                                           d_workspace, nbytes, stream))
 
     def compress_batch(self, jobs, d_pixels, pitch, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_compress_device_batch: enqueue the compress of every job (one launch per 44 jobs); d_pixels[i] = device

@@ -38,7 +38,8 @@ dict the three calls above take.
     im = torch_qs.compress(pixels, quality=85, hsamp=[2, 1, 1], vsamp=[2, 1, 1])   # pixels: uint8 (H, W, 3) on the device
 
 compresses pixels into the same image dict (qs_hip_compress_device_batch): libjpeg 9's jpeg_write_scanlines with
-JDCT_ISLOW and do_fancy_downsampling = FALSE; its default fancy downsampling is not implemented.
+JDCT_ISLOW and either chroma downsampling -- downsampling="box" (do_fancy_downsampling = FALSE, the default here) or
+downsampling="dct" (libjpeg 9's own default: 2x chroma through 16-point scaled forward DCTs).
 
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
@@ -899,13 +900,15 @@ def _compress_tables(im, n, who):
     return [q.astype(np.uint16) for q in qs]
 
 
-def compress(pixels, *, quality=None, quants=None, hsamp=None, vsamp=None, colorspace=None, fancy=False, out=None,
-             workspace: Workspace | None = None) -> dict:
+def compress(pixels, *, quality=None, quants=None, hsamp=None, vsamp=None, colorspace=None, fancy=False,
+             downsampling="box", out=None, workspace: Workspace | None = None) -> dict:
     """Compress device pixels into quantised coefficient tensors on the current stream: exactly the arrays libjpeg 9
-    holds after jpeg_write_scanlines with JDCT_ISLOW, smoothing_factor 0 and do_fancy_downsampling = FALSE (8x8
-    jpeg_fdct_islow for every component, box-filter chroma downsampling), i.e. what jpeg_read_coefficients returns for
-    that file.  libjpeg 9's default, do_fancy_downsampling = TRUE (2x chroma through 16-point scaled DCTs), is out of
-    scope: fancy=True raises ValueError.  Where chroma is not subsampled the two modes agree.
+    holds after jpeg_write_scanlines with JDCT_ISLOW and smoothing_factor 0, i.e. what jpeg_read_coefficients returns
+    for that file.  downsampling="box": do_fancy_downsampling = FALSE (box-filter chroma downsampling, the 8x8
+    jpeg_fdct_islow for every component).  downsampling="dct": do_fancy_downsampling = TRUE, the default of libjpeg 9,
+    cjpeg and jpeg_set_defaults (2x-subsampled chroma through jpeg_fdct_16x16 / _16x8 / _8x16 of the full-resolution
+    samples; the h2v1 box first for 4x1) -- the inverse of decode's chroma upsampling.  Where chroma is not subsampled
+    the two modes agree.  fancy=True still raises ValueError, as does any other downsampling.
 
     pixels: a uint8 CUDA tensor (H, W, 1) or (H, W, 3) with contiguous rows (any row pitch, any base alignment): gray,
     or RGB.  quality: libjpeg's jpeg_set_quality(q, TRUE) tables (luminance for component 0, chrominance for the
@@ -918,30 +921,43 @@ def compress(pixels, *, quality=None, quants=None, hsamp=None, vsamp=None, color
     vsamp, colorspace, image_size -- so quantsmooth_(**im, ...), decode(**im) and encode(**im, restart_interval=...)
     take it as it is."""
     r = compress_batch([dict(pixels=pixels, quality=quality, quants=quants, hsamp=hsamp, vsamp=vsamp,
-                             colorspace=colorspace)], fancy=fancy, outs=None if out is None else [out],
+                             colorspace=colorspace)], fancy=fancy, downsampling=downsampling,
+                       outs=None if out is None else [out],
                        workspace=workspace, _who="compress")
     return r["images"][0]
 
 
-def compress_batch(images, *, fancy=False, outs=None, workspace: Workspace | None = None, _who="compress_batch") -> dict:
+def _downsampling(value, who):
+    from . import hipqs
+    if not isinstance(value, str) or value not in hipqs.DOWNSAMPLING:
+        raise ValueError(f"{who}: downsampling {value!r}: \"box\" (do_fancy_downsampling = FALSE) or \"dct\" (libjpeg 9's "
+                         f"default, DCT-scaled chroma downsampling)")
+    return value
+
+
+def compress_batch(images, *, fancy=False, downsampling="box", outs=None, workspace: Workspace | None = None,
+                   _who="compress_batch") -> dict:
     """compress on many images in one call (one kernel launch for up to 44 images).  images[i]: a dict with compress's
-    per-image arguments (pixels, quality or quants, hsamp, vsamp, colorspace).  outs[i]: optional preallocated arrays.
-    Returns dict(images=[image dicts], workspace=Workspace)."""
+    per-image arguments (pixels, quality or quants, hsamp, vsamp, colorspace, and optionally downsampling, which
+    overrides this call's downsampling= for that image: one batch may mix modes).  outs[i]: optional preallocated
+    arrays.  Returns dict(images=[image dicts], workspace=Workspace)."""
     import torch
     who = _who
     if not isinstance(images, (list, tuple)) or not images:
         raise ValueError(f"{who}: images must be a non-empty list of dicts")
     if fancy:
-        raise ValueError(f"{who}: fancy downsampling (libjpeg 9's default, 2x chroma through 16-point scaled DCTs) is not "
-                         f"implemented: the compress is libjpeg's with do_fancy_downsampling = FALSE")
+        raise ValueError(f"{who}: fancy=True is refused; libjpeg 9's default downsampling (2x chroma through 16-point "
+                         f"scaled DCTs) is downsampling=\"dct\"")
+    _downsampling(downsampling, who)
     if outs is not None and len(outs) != len(images):
         raise ValueError(f"{who}: one output list (or None) per image")
     hip = _hip()
-    dev, metas = None, []
+    dev, metas, modes = None, [], []
     for i, im in enumerate(images):
         w_i = f"{who}: image {i}"
         if not isinstance(im, dict) or "pixels" not in im:
             raise ValueError(f"{w_i} must be a dict with pixels")
+        modes.append(downsampling if im.get("downsampling") is None else _downsampling(im["downsampling"], w_i))
         px = im["pixels"]
         if not isinstance(px, torch.Tensor) or px.dtype != torch.uint8 or not px.is_cuda:
             raise TypeError(f"{w_i}: pixels must be a uint8 CUDA (HIP) tensor")
@@ -982,8 +998,9 @@ def compress_batch(images, *, fancy=False, outs=None, workspace: Workspace | Non
                                    vsamp=vs, colorspace=cs, image_size=(w, h)))
         results.append(dict(coefs=coefs, quants=[q.copy() for q in qs], hsamp=hs, vsamp=vs, colorspace=cs,
                             image_size=(w, h)))
-    _per, total = hip.compress_batch_info(jobs)
-    key = ("compress",) + tuple(_key(job, 0, 0) for job in jobs)
+    opts = modes if any(m != "box" for m in modes) else None      # (all box: the calls without opts)
+    _per, total = hip.compress_batch_info(jobs, opts=opts)
+    key = ("compress",) + tuple(_key(job, 0, 0) + (mode,) for job, mode in zip(jobs, modes))
     if workspace is None:
         workspace = Workspace()
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -993,7 +1010,7 @@ def compress_batch(images, *, fancy=False, outs=None, workspace: Workspace | Non
                                f"geometry and tables (workspace=...): preparing one synchronises")
         if workspace.nbytes < total or workspace.buf.device != dev:
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.compress_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, stream)
+        hip.compress_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, stream, opts=opts)
         workspace.key = key
     pitches = [int(m[0].stride(0)) if m[0].shape[0] > 1 else int(m[0].shape[1]) * m[1] for m in metas]
     hip.compress_batch(jobs, [m[0].data_ptr() for m in metas], pitches, workspace.buf.data_ptr(), workspace.nbytes, stream)

@@ -39,10 +39,14 @@ restart intervals: the lanes of each case are reported.  Exits non-zero unless t
 same three cases, as time per call and GB/s of pixels read plus coefficients written, next to the decode of the arrays
 it wrote (the same bytes the other way) and the host route it replaces: libjpeg 9's jpeg_write_scanlines on one core
 (tests/libjpeg9_compress.c on a staged input file: its time includes reading the pixels and writing the file) plus the
-pinned upload of the coefficient arrays.  Exits non-zero unless the arrays are libjpeg's.
+pinned upload of the coefficient arrays.  Exits non-zero unless the arrays are libjpeg's.  --downsampling dct runs
+the same three cases with libjpeg 9's default DCT-scaled chroma downsampling (do_fancy_downsampling = TRUE in the host
+route and the comparison, tests/libjpeg9_compress_fancy.c) and reports whether each case's arrays coincide with the box
+mode's: the gray case must.
 
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode | --read | --compress] [--restart N | --restart-rows N]"""
+                                       [--decode | --encode | --read | --compress] [--restart N | --restart-rows N]
+                                       [--downsampling box|dct]"""
 import argparse
 import json
 import sys
@@ -72,6 +76,8 @@ def main():
                     help="--encode: time the whole-file run with optimized tables next to the histogram run plus the plain run")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
+    ap.add_argument("--downsampling", choices=["box", "dct"], default="box",
+                    help="--compress: box (do_fancy_downsampling = FALSE) or dct (libjpeg 9's default)")
     a = ap.parse_args()
     if a.compress:
         return bench_compress(a)
@@ -532,6 +538,9 @@ def bench_compress(a):
     import jpegqs_pkg
     sys.path.insert(0, str(ROOT / "tests"))
     from compress_oracle import Compress9, pack, tables
+    mode = a.downsampling
+    if mode == "dct":
+        from compress_fancy_oracle import CompressFancy9 as Compress9   # libjpeg with do_fancy_downsampling = TRUE
     pkg = jpegqs_pkg.load()
     torch_qs, synth = pkg.torch_qs, pkg.synth
     if not torch.cuda.is_available():
@@ -547,7 +556,8 @@ def bench_compress(a):
     cases = [("8192x8192_gray", picture(8192, 8192, 1), dict(hsamp=[1], vsamp=[1]), 1),
              ("8192x8192_420", picture(8192, 8192, 3), s420, 1),
              (f"{a.images}x1920x1080_420", picture(1920, 1080, 3), s420, a.images)]
-    out = dict(tool="bench_device_batch", leg="compress", device=torch.cuda.get_device_name(dev), results=[])
+    out = dict(tool="bench_device_batch", leg="compress", downsampling=mode, device=torch.cuda.get_device_name(dev),
+               results=[])
 
     def windows(fn, calls=20):
         for _ in range(3):
@@ -569,15 +579,20 @@ def bench_compress(a):
         on_dev = [torch.from_numpy(px).to(dev) for _ in range(count)]
         images = [dict(pixels=t, quality=50, **samp) for t in on_dev]
         ws, dws = torch_qs.Workspace(), torch_qs.Workspace()
-        res = torch_qs.compress_batch(images, workspace=ws)["images"]
+        kw = dict(downsampling=mode) if mode != "box" else {}
+        res = torch_qs.compress_batch(images, workspace=ws, **kw)["images"]
         outs = [im["coefs"] for im in res]
         nbytes = sum(t.numel() for t in on_dev) + sum(c.numel() * 2 for o in outs for c in o)
-        med, ms = windows(lambda: torch_qs.compress_batch(images, outs=outs, workspace=ws))
+        med, ms = windows(lambda: torch_qs.compress_batch(images, outs=outs, workspace=ws, **kw))
         back = torch_qs.decode_batch(res, workspace=dws)["images"]
         dmed, dms = windows(lambda: torch_qs.decode_batch(res, outs=back, workspace=dws))
         row = dict(case=name, images=count, mbytes=round(nbytes / 1e6, 1), ms=ms, median_ms=round(med, 4),
                    gb_per_s=round(nbytes / (med * 1e-3) / 1e9, 1), decode_ms=dms, decode_median_ms=round(dmed, 4),
                    compress_over_decode=round(med / dmed, 2))
+        if mode != "box":                                  # the same pixels through the box mode: equal without subsampling
+            box = torch_qs.compress_batch(images[:1])["images"][0]["coefs"]
+            row["same_as_box"] = [bool(torch.equal(x, y)) for x, y in zip(box, outs[0])]
+            del box
         # the host route: libjpeg 9 on one core, then the arrays up from pinned memory
         host_pinned = [[c.cpu().pin_memory() for c in o] for o in outs]
         dst = [[torch.empty_like(c) for c in o] for o in outs]
@@ -618,6 +633,8 @@ def bench_compress(a):
     bad = [r["case"] for r in out["results"] if not r["identical"]]
     if bad:
         raise SystemExit(f"bench_device_batch --compress: {bad}: the arrays are not libjpeg's")
+    if mode != "box" and not all(out["results"][0]["same_as_box"]):
+        raise SystemExit("bench_device_batch --compress: the gray case does not coincide with the box mode")
 
 
 if __name__ == "__main__":
