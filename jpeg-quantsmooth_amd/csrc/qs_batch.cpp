@@ -7,6 +7,7 @@
 #include <system_error>
 
 #include "qs_jobint.h"
+#include "qs_stage.h"
 
 using namespace qsx;
 using namespace qsj;
@@ -433,11 +434,5 @@ static int do_quantsmooth_batch_impl(qs_hip_job* const* jobs, int njobs, int fla
 
 extern "C" int qs_hip_do_quantsmooth_batch(qs_hip_job* const* jobs, int njobs, int flags, int niter, int* results) {
   struct Kick { ~Kick() { kick_background(); } } kick;
-  try {
-    return do_quantsmooth_batch_impl(jobs, njobs, flags, niter, results);
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
+  return guarded([&] { return do_quantsmooth_batch_impl(jobs, njobs, flags, niter, results); });
 }

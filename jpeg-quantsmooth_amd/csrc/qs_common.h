@@ -1,4 +1,5 @@
-// qs_common.h -- what the host-side translation units share: error reporting.
+// qs_common.h -- what the host-side translation units share: error reporting.  What the host drivers of the device
+// stages share on top of it (the guard at the C ABI, workspace and job checks) is in qs_stage.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -10,23 +10,19 @@
 // written by prepare; its layout and contents are a function of the jobs' geometry and tables alone.  The run passes
 // the pixels and the arrays in the kernel arguments, QS_CMP_CHUNK jobs per launch.
 #include "qs_common.h"
+#include "qs_stage.h"
 #include "qs_compress.h"
 
 #include <algorithm>
-#include <new>
-#include <vector>
 
 void qs_launch_compress(const QsCmpArgs& a, int tiles, hipStream_t s);
 
 static_assert(QS_CMP_CHUNK == QS_HIP_COMPRESS_CHUNK, "the header documents the launch chunk");
 
+static_assert(QS_CMP_GRAY == QS_PIX_GRAY && QS_CMP_YCC == QS_PIX_YCC && QS_CMP_RGB == QS_PIX_RGB,
+              "pixel_job (qs_stage.h) returns the layouts of the kernel");
+
 namespace {
-
-int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-bool luma_ok(int h, int v) {
-  return (h == 1 && v == 1) || (h == 2 && v == 1) || (h == 1 && v == 2) || (h == 2 && v == 2) || (h == 4 && v == 1);
-}
 
 // one job's layout, input shape and descriptor (pointers left null when d_pix is null: the info and prepare calls).
 // The run call (d_pix set) needs the geometry, the tiles and the addresses only: the tables were checked and their
@@ -34,38 +30,12 @@ bool luma_ok(int h, int v) {
 int describe(const qs_hip_job* job, const uint8_t* d_pix, size_t pitch, QsCmpJob* D, QsCmpPtrs* P,
              qs_hip_compress_info* info, const char* who) {
   const bool tables = d_pix == nullptr;
-  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
-  if (job->image_width <= 0 || job->image_height <= 0)
-    return qs_fail(QS_HIP_EINVAL, "%s: the compress needs image_width x image_height (got %d x %d)", who,
-                   job->image_width, job->image_height);
-  if (job->image_width > 65500 || job->image_height > 65500)
-    return qs_fail(QS_HIP_EINVAL, "%s: image of %d x %d exceeds JPEG's 65500", who, job->image_width, job->image_height);
-  memset(D, 0, sizeof *D);
   int layout;
-  if (job->ncomp == 1 && job->colorspace == 1) layout = QS_CMP_GRAY;
-  else if (job->ncomp == 3 && job->colorspace == 3) layout = QS_CMP_YCC;
-  else if (job->ncomp == 3 && job->colorspace == 2) layout = QS_CMP_RGB;
-  else
-    return qs_fail(QS_HIP_ENOTSUP, "%s: %d components in colour space %d: the device compress covers grayscale, YCbCr "
-                   "and RGB (3 components)", who, job->ncomp, job->colorspace);
-  for (int ci = 0; ci < job->ncomp; ++ci) {
-    if (!job->has_quant[ci]) return qs_fail(QS_HIP_EINVAL, "%s: component %d has no quant table", who, ci);
-    for (int i = 0; tables && i < 64; ++i)
-      if (job->quant[ci][i] == 0) return qs_fail(QS_HIP_EINVAL, "%s: component %d has a quantiser of 0", who, ci);
-    if (job->hsamp[ci] < 1 || job->hsamp[ci] > 4 || job->vsamp[ci] < 1 || job->vsamp[ci] > 4)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has sampling factors %dx%d", who, ci, job->hsamp[ci], job->vsamp[ci]);
-  }
+  if (int r = pixel_job(job, "compress", tables, &layout, who)) return r;
+  memset(D, 0, sizeof *D);
   int hs = job->hsamp[0], vs = job->vsamp[0];
   if (layout == QS_CMP_GRAY) hs = vs = 1;                  // one component: its own grid is the pixel grid
-  else {
-    for (int ci = 1; ci < 3; ++ci)
-      if (job->hsamp[ci] != 1 || job->vsamp[ci] != 1)
-        return qs_fail(QS_HIP_ENOTSUP, "%s: chroma component %d is sampled %dx%d: the device compress needs 1x1 chroma",
-                       who, ci, job->hsamp[ci], job->vsamp[ci]);
-    if (!luma_ok(hs, vs))
-      return qs_fail(QS_HIP_ENOTSUP, "%s: luma sampling %dx%d: the device compress covers 1x1, 2x1, 1x2, 2x2 and 4x1",
-                     who, hs, vs);
-  }
+  else if (int r = pixel_sampling(job, "compress", who)) return r;
   const int W = job->image_width, Hh = job->image_height;
   D->width = W; D->height = Hh;
   D->layout = layout;
@@ -78,10 +48,9 @@ int describe(const qs_hip_job* job, const uint8_t* d_pix, size_t pitch, QsCmpJob
     if (job->wblk[ci] < D->wib[ci] || job->hblk[ci] < D->hib[ci])
       return qs_fail(QS_HIP_EINVAL, "%s: component %d has %d x %d blocks, a %d x %d image needs %d x %d", who, ci,
                      job->wblk[ci], job->hblk[ci], W, Hh, D->wib[ci], D->hib[ci]);
-    if ((long long)job->wblk[ci] * job->hblk[ci] > 0x7fffffffLL)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has more than 2^31 blocks", who, ci);
-    if (d_pix && (!job->coef[ci] || (reinterpret_cast<uintptr_t>(job->coef[ci]) & 15)))
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has no data or is not 16-byte aligned", who, ci);
+    if (int r = check_block_count(job, ci, who)) return r;
+    if (d_pix)
+      if (int r = check_array(job->coef[ci], ci, false, who)) return r;
     for (int i = 0; tables && i < 64; ++i) {
       D->q[ci][i] = job->quant[ci][i];
       D->recip[ci][i] = qc_recip((uint32_t)job->quant[ci][i] << 3);
@@ -94,8 +63,7 @@ int describe(const qs_hip_job* job, const uint8_t* d_pix, size_t pitch, QsCmpJob
   D->tiles_x = ceil_div(W, QS_CMP_TW);
   D->tiles = D->tiles_x * ceil_div(Hh, QS_CMP_TH);
   if (d_pix) {
-    if (pitch < (size_t)W * D->nin || pitch > ((size_t)1 << 40))
-      return qs_fail(QS_HIP_EINVAL, "%s: pixel pitch %zu for rows of %d x %d samples", who, pitch, W, D->nin);
+    if (int r = check_pitch(pitch, W, D->nin, "pixel", who)) return r;
     if (P) {
       P->pix = d_pix;
       P->pitch = (int64_t)pitch;
@@ -112,15 +80,11 @@ int describe(const qs_hip_job* job, const uint8_t* d_pix, size_t pitch, QsCmpJob
   return QS_HIP_OK;
 }
 
-struct Who {
-  char s[96];
-  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
-};
-
 // the descriptors of a batch and, with d_pix (the run), the kernel-argument records; the tile prefix restarts with
 // every chunk of QS_CMP_CHUNK jobs (one launch each)
 int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts* const* opts,
-                 const uint8_t* const* d_pix, const size_t* pitch, std::vector<QsCmpJob>& D, std::vector<QsCmpPtrs>* P, qs_hip_compress_info* info, const char* who) {
+                 const uint8_t* const* d_pix, const size_t* pitch, std::vector<QsCmpJob>& D, std::vector<QsCmpPtrs>* P,
+                 qs_hip_compress_info* info, const char* who) {
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   if (d_pix && !pitch) return qs_fail(QS_HIP_EINVAL, "%s: null pitch", who);
   D.assign((size_t)njobs, QsCmpJob());
@@ -149,13 +113,6 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts*
 
 size_t workspace_bytes(int njobs) { return (size_t)njobs * sizeof(QsCmpJob); }
 
-int check_ws(int njobs, const void* d_workspace, size_t bytes, const char* who) {
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < workspace_bytes(njobs))
-    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %zu", who, bytes,
-                   workspace_bytes(njobs));
-  return QS_HIP_OK;
-}
-
 int no_fancy(int fancy, const char* who) {
   if (fancy)
     return qs_fail(QS_HIP_ENOTSUP, "%s: fancy != 0 is refused: pass 0 for the box filter of do_fancy_downsampling = FALSE; "
@@ -163,24 +120,6 @@ int no_fancy(int fancy, const char* who) {
                    "calls", who);
   return QS_HIP_OK;
 }
-
-int device_ok() {
-  if (qs_hip_device_count() <= 0)
-    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-  return QS_HIP_OK;
-}
-
-template <class F> int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
-}
-
-
 
 int info_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts* const* opts, int fancy,
               qs_hip_compress_info* per_job, size_t* bytes, const char* who) {
@@ -197,12 +136,9 @@ int prepare_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_compress_opts*
   std::vector<QsCmpJob> D;
   if (int r = describe_all(jobs, njobs, opts, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
   if (int r = no_fancy(fancy, who)) return r;
-  if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
+  if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
   if (int r = device_ok()) return r;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsCmpJob), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));                        // (a pageable source: it must outlive the copy)
-  return QS_HIP_OK;
+  return upload(d_workspace, D, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -245,7 +181,7 @@ extern "C" int qs_hip_compress_device_batch(qs_hip_job* const* jobs, int njobs, 
     std::vector<QsCmpPtrs> P;
     if (!d_pixels) return qs_fail(QS_HIP_EINVAL, "%s: null d_pixels", who);
     if (int r = describe_all(jobs, njobs, nullptr, d_pixels, pitch, D, &P, nullptr, who)) return r;
-    if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
+    if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int j0 = 0; j0 < njobs; j0 += QS_CMP_CHUNK) {

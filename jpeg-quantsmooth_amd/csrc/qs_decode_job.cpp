@@ -8,45 +8,24 @@
 // layout and contents are a function of the jobs' geometry and tables alone.  The run passes the arrays and outputs in
 // the kernel arguments, QS_DEC_CHUNK jobs per launch.
 #include "qs_common.h"
+#include "qs_stage.h"
 #include "qs_decode.h"
 
 #include <algorithm>
-#include <new>
-#include <vector>
 
 void qs_launch_decode(const QsDecArgs& a, int tiles, hipStream_t s);
 
+static_assert(QS_DEC_GRAY == QS_PIX_GRAY && QS_DEC_YCC == QS_PIX_YCC && QS_DEC_RGB == QS_PIX_RGB,
+              "pixel_job (qs_stage.h) returns the layouts of the kernel");
+
 namespace {
-
-int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-// the luma sampling factors libjpeg 9 decodes with DCT-scaled chroma and no other upsampler here
-bool luma_ok(int h, int v) {
-  return (h == 1 && v == 1) || (h == 2 && v == 1) || (h == 1 && v == 2) || (h == 2 && v == 2) || (h == 4 && v == 1);
-}
 
 // one job's layout, output shape and descriptor (pointers left null when d_out is null: the info call)
 int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, QsDecPtrs* P,
              qs_hip_decode_info* info, const char* who) {
-  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
-  if (job->image_width <= 0 || job->image_height <= 0)
-    return qs_fail(QS_HIP_EINVAL, "%s: the decode needs image_width x image_height (got %d x %d)", who,
-                   job->image_width, job->image_height);
-  if (job->image_width > 65500 || job->image_height > 65500)
-    return qs_fail(QS_HIP_EINVAL, "%s: image of %d x %d exceeds JPEG's 65500", who, job->image_width, job->image_height);
-  memset(D, 0, sizeof *D);
   int layout;
-  if (job->ncomp == 1 && job->colorspace == 1) layout = QS_DEC_GRAY;
-  else if (job->ncomp == 3 && job->colorspace == 3) layout = QS_DEC_YCC;
-  else if (job->ncomp == 3 && job->colorspace == 2) layout = QS_DEC_RGB;
-  else
-    return qs_fail(QS_HIP_ENOTSUP, "%s: %d components in colour space %d: the device decode covers grayscale, YCbCr "
-                   "and RGB (3 components)", who, job->ncomp, job->colorspace);
-  for (int ci = 0; ci < job->ncomp; ++ci) {
-    if (!job->has_quant[ci]) return qs_fail(QS_HIP_EINVAL, "%s: component %d has no quant table", who, ci);
-    if (job->hsamp[ci] < 1 || job->hsamp[ci] > 4 || job->vsamp[ci] < 1 || job->vsamp[ci] > 4)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has sampling factors %dx%d", who, ci, job->hsamp[ci], job->vsamp[ci]);
-  }
+  if (int r = pixel_job(job, "decode", false, &layout, who)) return r;
+  memset(D, 0, sizeof *D);
   const int W = job->image_width, Hh = job->image_height;
   // the two geometries: variant 0 = replacement chroma when the job has it, variant 1 = the original arrays
   const bool up = job->up_wblk > 0 && layout != QS_DEC_GRAY;
@@ -56,15 +35,7 @@ int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, Q
     int hs = job->hsamp[0], vs = job->vsamp[0];
     if (layout == QS_DEC_GRAY) hs = vs = 1;                // one component: its own grid is the pixel grid
     else if (repl) hs = vs = 1;
-    else {
-      for (int ci = 1; ci < 3; ++ci)
-        if (job->hsamp[ci] != 1 || job->vsamp[ci] != 1)
-          return qs_fail(QS_HIP_ENOTSUP, "%s: chroma component %d is sampled %dx%d: the device decode needs 1x1 chroma",
-                         who, ci, job->hsamp[ci], job->vsamp[ci]);
-      if (!luma_ok(hs, vs))
-        return qs_fail(QS_HIP_ENOTSUP, "%s: luma sampling %dx%d: the device decode covers 1x1, 2x1, 1x2, 2x2 and 4x1",
-                       who, hs, vs);
-    }
+    else if (int rc = pixel_sampling(job, "decode", who)) return rc;   // (the only upsampler here: DCT-scaled chroma)
     g.hs = hs; g.vs = vs;
     for (int ci = 0; ci < job->ncomp; ++ci) {
       const bool r = repl && ci > 0;
@@ -77,9 +48,8 @@ int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, Q
       if (g.wblk[ci] < nw || g.hblk[ci] < nh)
         return qs_fail(QS_HIP_EINVAL, "%s: component %d%s has %d x %d blocks, a %d x %d image needs %d x %d", who, ci,
                        r ? " (replacement chroma)" : "", g.wblk[ci], g.hblk[ci], W, Hh, nw, nh);
-      if (d_out && (!arr || (reinterpret_cast<uintptr_t>(arr) & 15)))
-        return qs_fail(QS_HIP_EINVAL, "%s: component %d%s has no data or is not 16-byte aligned", who, ci,
-                       r ? " (replacement chroma)" : "");
+      if (d_out)
+        if (int rc = check_array(arr, ci, r, who)) return rc;
       if (P) {
         P->coef[slot] = arr;
         P->nblk[slot] = g.wblk[ci] * g.hblk[ci];
@@ -95,8 +65,7 @@ int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, Q
   for (int ci = 0; ci < job->ncomp; ++ci)
     for (int i = 0; i < 64; ++i) D->q[ci][i] = job->quant[ci][i];
   if (d_out) {
-    if (pitch < (size_t)W * D->nout || pitch > ((size_t)1 << 40))
-      return qs_fail(QS_HIP_EINVAL, "%s: output pitch %zu for rows of %d x %d samples", who, pitch, W, D->nout);
+    if (int rc = check_pitch(pitch, W, D->nout, "output", who)) return rc;
     if (P) {
       P->out = d_out;
       P->pitch = (int64_t)pitch;
@@ -108,11 +77,6 @@ int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, Q
   }
   return QS_HIP_OK;
 }
-
-struct Who {
-  char s[96];
-  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
-};
 
 // the descriptors of a batch and, with d_out (the run), the kernel-argument records; the tile prefix restarts with
 // every chunk of QS_DEC_CHUNK jobs (one launch each)
@@ -138,29 +102,6 @@ int describe_all(qs_hip_job* const* jobs, int njobs, uint8_t* const* d_out, cons
 
 size_t workspace_bytes(int njobs) { return (size_t)njobs * sizeof(QsDecJob); }
 
-int check_ws(int njobs, const void* d_workspace, size_t bytes, const char* who) {
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < workspace_bytes(njobs))
-    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %zu", who, bytes,
-                   workspace_bytes(njobs));
-  return QS_HIP_OK;
-}
-
-int device_ok() {
-  if (qs_hip_device_count() <= 0)
-    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-  return QS_HIP_OK;
-}
-
-template <class F> int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
-}
-
 }  // namespace
 
 extern "C" int qs_hip_decode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_decode_info* per_job,
@@ -181,12 +122,9 @@ extern "C" int qs_hip_decode_device_batch_prepare(qs_hip_job* const* jobs, int n
     const char* who = "qs_hip_decode_device_batch_prepare";
     std::vector<QsDecJob> D;
     if (int r = describe_all(jobs, njobs, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
-    if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
+    if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsDecJob), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
-    return QS_HIP_OK;
+    return upload(d_workspace, D, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -199,7 +137,7 @@ extern "C" int qs_hip_decode_device_batch(qs_hip_job* const* jobs, int njobs, co
     std::vector<QsDecPtrs> P;
     if (!d_out) return qs_fail(QS_HIP_EINVAL, "%s: null d_out", who);
     if (int r = describe_all(jobs, njobs, d_out, out_pitch, D, &P, nullptr, who)) return r;
-    if (int r = check_ws(njobs, d_workspace, bytes, who)) return r;
+    if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int j0 = 0; j0 < njobs; j0 += QS_DEC_CHUNK) {

@@ -31,15 +31,12 @@
 // fix-up tables (QsDevBRec).  A single job's workspace is its region alone: make_plan reserves its word and room for
 // its own tables in it.
 #include "qs_common.h"
+#include "qs_stage.h"
 #include "qs_device_job.h"
 
 #include <algorithm>
-#include <new>
-#include <vector>
 
 namespace {
-
-size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct DevComp {
   bool modified = false;      // the plan writes this component's coefficients
@@ -74,12 +71,11 @@ int needs_lowres(const qs_hip_job* job, int flags) {
 }
 
 int check_geometry(const qs_hip_job* job, const char* who) {
-  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
+  if (int r = check_job(job, who)) return r;
   for (int ci = 0; ci < job->ncomp; ++ci) {
     if (job->wblk[ci] <= 0 || job->hblk[ci] <= 0)
       return qs_fail(QS_HIP_EINVAL, "%s: component %d has no blocks", who, ci);
-    if (job->hsamp[ci] < 1 || job->hsamp[ci] > 4 || job->vsamp[ci] < 1 || job->vsamp[ci] > 4)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has sampling factors %dx%d", who, ci, job->hsamp[ci], job->vsamp[ci]);
+    if (int r = check_sampling(job, ci, who)) return r;
     if ((long long)job->wblk[ci] * job->hblk[ci] > (1ll << 27))
       return qs_fail(QS_HIP_EINVAL, "%s: component %d is too large", who, ci);
   }
@@ -92,12 +88,11 @@ int make_plan(const qs_hip_job* job, int flags, int niter, DevPlan& P, const cha
   niter = niter < 0 ? 0 : niter > 100 ? 100 : niter;       // reference :2455-2456
   P.niter = niter;
   P.need_lowres = needs_lowres(job, flags);
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += align_up(n); return o; };
-  P.off_word = take(sizeof(uint32_t));
-  P.off_pre = take(job->ncomp * sizeof(QsDevBRec));        // (at most one precheck and one fix-up record per component)
-  P.off_fix = take(job->ncomp * sizeof(QsDevBRec));
-  if (niter <= 0 && !((flags & QS_UPSAMPLE_UV) && P.need_lowres)) { P.total = off; return QS_HIP_OK; }   // reference :2458
+  Layout L;
+  P.off_word = L.take(sizeof(uint32_t));
+  P.off_pre = L.take(job->ncomp * sizeof(QsDevBRec));        // (at most one precheck and one fix-up record per component)
+  P.off_fix = L.take(job->ncomp * sizeof(QsDevBRec));
+  if (niter <= 0 && !((flags & QS_UPSAMPLE_UV) && P.need_lowres)) { P.total = L.total; return QS_HIP_OK; }   // reference :2458
   P.todo = 1;
 
   // independent components and ordinary tables (qs_job.cpp: job_fusable): one plane-set launch per pass
@@ -119,19 +114,19 @@ int make_plan(const qs_hip_job* job, int flags, int niter, DevPlan& P, const cha
     if (acc >= 0x800) stop = 1;                            // :2504
     if (C.iters + C.extra == 0) continue;                  // :2542
     C.modified = true;
-    C.off_cst = take(sizeof(QsConsts));
+    C.off_cst = L.take(sizeof(QsConsts));
     if (stop) continue;                                    // dequantise only, :2551-2566
     C.passes = true;
-    C.off_status = take(sizeof(int32_t));
-    C.off_plane = take(qs_hip_plane_bytes(job->wblk[ci], job->hblk[ci]));
+    C.off_status = L.take(sizeof(int32_t));
+    C.off_plane = L.take(qs_hip_plane_bytes(job->wblk[ci], job->hblk[ci]));
     C.fuse = !(flags & QS_LOW_QUALITY) && C.iters + C.extra > 1;
-    if (C.fuse) C.off_plane2 = take(qs_hip_plane_bytes(job->wblk[ci], job->hblk[ci]));
+    if (C.fuse) C.off_plane2 = L.take(qs_hip_plane_bytes(job->wblk[ci], job->hblk[ci]));
     if (have_yfull) C.upsample = true;                     // :2691-2752
     else if (!ci && P.need_lowres) {                       // :2753-2815
       P.have_llow = 1;
       if (!(job->hsamp[0] == 1 && job->vsamp[0] == 1)) {
         P.llow_own = 1;
-        P.off_llow = take(qs_hip_plane_bytes(job->wblk[1], job->hblk[1]));
+        P.off_llow = L.take(qs_hip_plane_bytes(job->wblk[1], job->hblk[1]));
         if (flags & QS_UPSAMPLE_UV) have_yfull = P.have_yfull = 1;
       }
     }
@@ -140,7 +135,7 @@ int make_plan(const qs_hip_job* job, int flags, int niter, DevPlan& P, const cha
   // replacement chroma only when both chroma components were re-encoded and nothing stopped (qs_job.cpp, :2833-2849);
   // otherwise the job layer discards them, and so are they not computed here
   P.up = P.have_yfull && job->ncomp == 3 && P.c[1].upsample && P.c[2].upsample && !stop;
-  if (P.up) P.off_px = take(qs_hip_upsample_bytes(job->image_width, job->image_height, job->hsamp[0], job->vsamp[0]));
+  if (P.up) P.off_px = L.take(qs_hip_upsample_bytes(job->image_width, job->image_height, job->hsamp[0], job->vsamp[0]));
   else P.c[1].upsample = P.c[2].upsample = false;
 
   // the snapshot: every component the passes write that a stop at an earlier-or-equal checked component must rebuild
@@ -150,9 +145,9 @@ int make_plan(const qs_hip_job* job, int flags, int niter, DevPlan& P, const cha
     for (int ci = first_checked; ci < job->ncomp; ++ci)
       if (P.c[ci].modified) {
         P.c[ci].snap = true;
-        P.c[ci].off_snap = take((size_t)job->wblk[ci] * job->hblk[ci] * 64 * sizeof(int16_t));
+        P.c[ci].off_snap = L.take((size_t)job->wblk[ci] * job->hblk[ci] * 64 * sizeof(int16_t));
       }
-  P.total = off;
+  P.total = L.total;
   return QS_HIP_OK;
 }
 
@@ -201,14 +196,6 @@ struct BatchPlan {
   size_t off_words = 0, off_pre = 0, off_fix = 0, total = 0;
 };
 
-struct Who {                                // "<call>: job <i>", the prefix of a job's error messages in a batch
-  char s[96];
-  Who(const char* who, int i, bool standalone) {
-    if (standalone) snprintf(s, sizeof s, "%s", who);
-    else snprintf(s, sizeof s, "%s: job %d", who, i);
-  }
-};
-
 uint64_t comp_nvec(const qs_hip_job* job, int ci) { return (uint64_t)job->wblk[ci] * job->hblk[ci] * 8; }
 
 // blk0: a prefix over the workgroups of each chunk's launch (qs_kernels_device.hip: qs_devb_grid)
@@ -229,13 +216,12 @@ int make_batch_plan(qs_hip_job* const* jobs, int njobs, int flags, int niter, bo
   B.P.resize((size_t)njobs);
   B.route.resize((size_t)njobs);
   B.region.resize((size_t)njobs);
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += align_up(n); return o; };
-  if (!standalone) B.off_words = take((size_t)njobs * sizeof(uint32_t));
+  Layout L;
+  if (!standalone) B.off_words = L.take((size_t)njobs * sizeof(uint32_t));
   for (int i = 0; i < njobs; ++i) {
     if (int r = make_plan(jobs[i], flags, niter, B.P[i], Who(who, i, standalone).s)) return r;
     B.route[i] = route_of(flags, B.P[i]);
-    B.region[i] = take(B.P[i].total);
+    B.region[i] = L.take(B.P[i].total);
   }
   for (int i = 0; i < njobs; ++i) {
     const qs_hip_job* job = jobs[i];
@@ -269,31 +255,17 @@ int make_batch_plan(qs_hip_job* const* jobs, int njobs, int flags, int niter, bo
   if (standalone) {
     B.off_words = B.P[0].off_word; B.off_pre = B.P[0].off_pre; B.off_fix = B.P[0].off_fix;
   } else {
-    B.off_pre = take(B.pre.size() * sizeof(QsDevBRec));
-    B.off_fix = take(B.fix.size() * sizeof(QsDevBRec));
+    B.off_pre = L.take(B.pre.size() * sizeof(QsDevBRec));
+    B.off_fix = L.take(B.fix.size() * sizeof(QsDevBRec));
   }
-  B.total = off;
-  return QS_HIP_OK;
-}
-
-int device_ok() {
-  if (qs_hip_device_count() <= 0)
-    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-  return QS_HIP_OK;
-}
-
-int check_workspace(const BatchPlan& B, const void* d_workspace, size_t bytes, bool standalone, const char* who) {
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < B.total)
-    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the %s needs %zu", who, bytes,
-                   standalone ? "job" : "batch", B.total);
+  B.total = L.total;
   return QS_HIP_OK;
 }
 
 // job->coef / coef_up present and aligned; `who` names the call (and the job of a batch)
 int check_job_arrays(const qs_hip_job* job, const DevPlan& P, const char* who) {
   for (int ci = 0; ci < job->ncomp; ++ci)                  // (the kernels move 16 bytes per lane)
-    if (!job->coef[ci] || (reinterpret_cast<uintptr_t>(job->coef[ci]) & 15))
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has no data or is not 16-byte aligned", who, ci);
+    if (int r = check_array(job->coef[ci], ci, false, who)) return r;
   if (P.up && (!job->coef_up[0] || !job->coef_up[1] || ((reinterpret_cast<uintptr_t>(job->coef_up[0]) |
                                                            reinterpret_cast<uintptr_t>(job->coef_up[1])) & 15)))
     return qs_fail(QS_HIP_EINVAL, "%s: UPSAMPLE_UV replaces the chroma: coef_up[0] and coef_up[1] must be device arrays "
@@ -557,16 +529,6 @@ void report_quant(qs_hip_job* job, const DevPlan& P) {    // reference :2851-285
 
 // ---- the three calls on njobs jobs; standalone: a single-job call (its own layout, no "job <i>" in messages) ----
 
-template <class F> int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
-}
-
 int info(qs_hip_job* const* jobs, int njobs, int flags, int niter, qs_hip_device_info* per_job, size_t* workspace_bytes,
          bool standalone, const char* who) {
   if (!per_job || !workspace_bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
@@ -581,7 +543,7 @@ int prepare(qs_hip_job* const* jobs, int njobs, int flags, int niter, void* d_wo
             bool standalone, const char* who) {
   BatchPlan B;
   if (int r = make_batch_plan(jobs, njobs, flags, niter, standalone, B, who)) return r;
-  if (int r = check_workspace(B, d_workspace, bytes, standalone, who)) return r;
+  if (int r = check_workspace(B.total, d_workspace, bytes, who, standalone ? "job" : "batch")) return r;
   if (int r = device_ok()) return r;
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(d_workspace);
@@ -603,7 +565,7 @@ int run(qs_hip_job* const* jobs, int njobs, int flags, int niter, void* d_worksp
   for (int i = 0; i < njobs; ++i)
     if (int r = check_job_arrays(jobs[i], B.P[i], Who(who, i, standalone).s)) return r;
   if (int r = check_disjoint(jobs, njobs, B, who)) return r;
-  if (int r = check_workspace(B, d_workspace, bytes, standalone, who)) return r;
+  if (int r = check_workspace(B.total, d_workspace, bytes, who, standalone ? "job" : "batch")) return r;
   if (int r = device_ok()) return r;
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(d_workspace);

@@ -33,6 +33,69 @@ struct QsEncGeom {
   int32_t nblocks;                 // mcus * bpm
 };
 
+// why qs_enc_geometry refuses a scan
+#define QS_GEOM_OK 0
+#define QS_GEOM_ARGS 1             // components not 1..4, or an image outside 1..65500
+#define QS_GEOM_SHORT 2            // *detail = the first component whose array is short of nw x nh blocks (both filled in)
+#define QS_GEOM_MCU 3              // *detail = the blocks of an MCU, more than libjpeg's 10
+#define QS_GEOM_SCAN 4             // more than 0x7fff0000 blocks in the scan
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define QS_ENC_HD __host__ __device__ static inline   // (static: the library exports nothing from here)
+#else
+#define QS_ENC_HD static inline
+#endif
+
+// The scan that carries all components of a frame (jcmaster.c / jdinput.c per_scan_setup), for the coder and the scan
+// reader alike (csrc/qs_read.h: qr_geometry).  hs / vs: the sampling factors, which the caller has checked; stride /
+// rows: the arrays in blocks; slot: null means slot[c] = c.  -> QS_GEOM_*
+QS_ENC_HD int qs_enc_geometry(int ncomp, int W, int H, const int32_t* hs, const int32_t* vs, const int32_t* stride,
+                              const int32_t* rows, const int32_t* slot, QsEncGeom* g, int* detail) {
+  *g = QsEncGeom();
+  if (ncomp < 1 || ncomp > 4 || W < 1 || H < 1 || W > 65500 || H > 65500) return QS_GEOM_ARGS;
+  int mh = 1, mv = 1;
+  for (int c = 0; c < ncomp; ++c) {
+    if (hs[c] > mh) mh = hs[c];
+    if (vs[c] > mv) mv = vs[c];
+  }
+  g->ncomp = ncomp;
+  for (int c = 0; c < ncomp; ++c) {
+    g->nw[c] = (int32_t)(((long long)W * hs[c] + 8LL * mh - 1) / (8LL * mh));   // width_in_blocks / height_in_blocks
+    g->nh[c] = (int32_t)(((long long)H * vs[c] + 8LL * mv - 1) / (8LL * mv));
+    g->stride[c] = stride[c];
+    g->slot[c] = slot ? slot[c] : c;
+    if (stride[c] < g->nw[c] || rows[c] < g->nh[c]) {
+      *detail = c;
+      return QS_GEOM_SHORT;
+    }
+  }
+  if (ncomp == 1) {                                                 // non-interleaved: an MCU is one block
+    g->hs[0] = g->vs[0] = 1;
+    g->bpm = 1;
+    g->mcus_x = g->nw[0];
+    g->mcus = g->nw[0] * g->nh[0];
+  } else {
+    int first = 0;
+    for (int c = 0; c < ncomp; ++c) {
+      g->hs[c] = hs[c];
+      g->vs[c] = vs[c];
+      g->first[c] = first;
+      first += hs[c] * vs[c];
+    }
+    if (first > 10) {
+      *detail = first;
+      return QS_GEOM_MCU;
+    }
+    g->bpm = first;
+    g->mcus_x = (int32_t)((W + 8LL * mh - 1) / (8LL * mh));
+    const long long mcus = (long long)g->mcus_x * ((H + 8LL * mv - 1) / (8LL * mv));
+    if (mcus * first > 0x7fff0000LL) return QS_GEOM_SCAN;
+    g->mcus = (int32_t)mcus;
+  }
+  g->nblocks = g->mcus * g->bpm;
+  return QS_GEOM_OK;
+}
+
 // One job as the kernels see it (workspace, written by prepare): geometry, code tables and where its scratch arrays
 // lie in the workspace.  No addresses of caller memory.
 struct QsEncJob {

@@ -15,14 +15,13 @@
 // workspace it does not find there runs as one without restart jobs, as every workspace did before there were options;
 // should its descriptors hold an interval after all, the kernels end those jobs with status 4.
 #include "qs_common.h"
+#include "qs_stage.h"
 #include "qs_encode.h"
 #include "qs_huff.h"
 
 #include <algorithm>
 #include <mutex>
-#include <new>
 #include <unordered_map>
-#include <vector>
 
 void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, bool restart, hipStream_t s);
 void qs_launch_huff_optimal(const uint32_t* d_counts, int ntables, uint8_t* d_tables, int32_t* d_status, hipStream_t s);
@@ -87,56 +86,24 @@ int derive(const qs_hip_huff_table& t, bool is_dc, uint32_t* out, int nout, cons
   return QS_HIP_OK;
 }
 
-int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
 // one geometry: the sampling factors hs / vs, array strides and slots of its components
 int geometry(const qs_hip_job* job, const int* hs, const int* vs, const int* stride, const int* rows, const int* slot,
              QsEncGeom* g, const char* who) {
-  const int n = job->ncomp, W = job->image_width, H = job->image_height;
-  int mh = 1, mv = 1;
-  for (int c = 0; c < n; ++c) {
-    mh = std::max(mh, hs[c]);
-    mv = std::max(mv, vs[c]);
+  const int W = job->image_width, H = job->image_height;
+  int d = 0;
+  switch (qs_enc_geometry(job->ncomp, W, H, hs, vs, stride, rows, slot, g, &d)) {
+    case QS_GEOM_OK: return QS_HIP_OK;
+    case QS_GEOM_SHORT:
+      return qs_fail(QS_HIP_EINVAL, "%s: component %d has %d x %d blocks, a %d x %d image sampled %dx%d needs %d x %d", who, d,
+                     stride[d], rows[d], W, H, hs[d], vs[d], g->nw[d], g->nh[d]);
+    case QS_GEOM_MCU: return qs_fail(QS_HIP_ENOTSUP, "%s: %d blocks in an MCU; libjpeg takes at most 10", who, d);
+    case QS_GEOM_SCAN: return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 blocks in the scan", who);
+    default: return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);      // (describe has looked at ncomp and the image)
   }
-  memset(g, 0, sizeof *g);
-  g->ncomp = n;
-  for (int c = 0; c < n; ++c) {
-    g->nw[c] = ceil_div((long long)W * hs[c], 8LL * mh);          // jcmaster.c: width_in_blocks / height_in_blocks
-    g->nh[c] = ceil_div((long long)H * vs[c], 8LL * mv);
-    g->stride[c] = stride[c];
-    g->slot[c] = slot[c];
-    if (stride[c] < g->nw[c] || rows[c] < g->nh[c])
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has %d x %d blocks, a %d x %d image sampled %dx%d needs %d x %d", who, c,
-                     stride[c], rows[c], W, H, hs[c], vs[c], g->nw[c], g->nh[c]);
-  }
-  if (n == 1) {                                                   // non-interleaved: an MCU is one block
-    g->hs[0] = g->vs[0] = 1;
-    g->bpm = 1;
-    g->mcus_x = g->nw[0];
-    g->mcus = g->nw[0] * g->nh[0];
-  } else {
-    int first = 0;
-    for (int c = 0; c < n; ++c) {
-      g->hs[c] = hs[c];
-      g->vs[c] = vs[c];
-      g->first[c] = first;
-      first += hs[c] * vs[c];
-    }
-    if (first > 10)
-      return qs_fail(QS_HIP_ENOTSUP, "%s: %d blocks in an MCU; libjpeg takes at most 10", who, first);
-    g->bpm = first;
-    g->mcus_x = ceil_div(W, 8LL * mh);
-    const long long mcus = (long long)g->mcus_x * ceil_div(H, 8LL * mv);
-    if (mcus * first > 0x7fff0000LL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 blocks in the scan", who);
-    g->mcus = (int)mcus;
-  }
-  g->nblocks = g->mcus * g->bpm;
-  return QS_HIP_OK;
 }
 
 int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, qs_hip_encode_info* info, const char* who) {
-  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
+  if (int r = check_job(job, who)) return r;
   const int n = job->ncomp;
   if (job->image_width <= 0 || job->image_height <= 0 || job->image_width > 65500 || job->image_height > 65500)
     return qs_fail(QS_HIP_EINVAL, "%s: the encoder needs image_width x image_height within 65500 (got %d x %d)", who,
@@ -151,8 +118,7 @@ int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays,
                    "CMYK and YCCK (4)", who, n, cs);
   for (int c = 0; c < n; ++c) {
     D->tbl[c] = ((cs == 3 || cs == 5) && (c == 1 || c == 2)) ? 1 : 0;
-    if (job->hsamp[c] < 1 || job->hsamp[c] > 4 || job->vsamp[c] < 1 || job->vsamp[c] > 4)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has sampling factors %dx%d", who, c, job->hsamp[c], job->vsamp[c]);
+    if (int r = check_sampling(job, c, who)) return r;
     if (job->wblk[c] < 1 || job->hblk[c] < 1) return qs_fail(QS_HIP_EINVAL, "%s: component %d has no blocks", who, c);
   }
   const bool up = job->up_wblk > 0 && n == 3;
@@ -171,9 +137,8 @@ int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays,
       rows[c] = r ? job->up_hblk : job->hblk[c];
       slot[c] = (up && !repl && c) ? 3 + c : c;
       const int16_t* arr = r ? job->coef_up[c - 1] : job->coef[c];
-      if (need_arrays && (!arr || (reinterpret_cast<uintptr_t>(arr) & 15)))
-        return qs_fail(QS_HIP_EINVAL, "%s: component %d%s has no data or is not 16-byte aligned", who, c,
-                       r ? " (replacement chroma)" : "");
+      if (need_arrays)
+        if (int rc = check_array(arr, c, r, who)) return rc;
       if (P) {
         P->coef[slot[c]] = arr;
         P->nblk[slot[c]] = stride[c] * rows[c];
@@ -190,13 +155,6 @@ int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays,
   }
   return QS_HIP_OK;
 }
-
-struct Who {
-  char s[96];
-  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
-};
-
-uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QsEncJob), 256); }
 
 // jcmaster.c (per_scan_setup): restart_in_rows wins and is counted in the geometry's MCU rows, limited to 16 bits.
 // -> the interval the kernels work with: 0 where no marker is written (none asked for, or one interval covers the scan)
@@ -244,7 +202,8 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* c
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   D.assign((size_t)njobs, QsEncJob());
   if (P) P->assign((size_t)njobs, QsEncPtrs());
-  uint64_t off = descriptors_bytes(njobs);
+  Layout L;
+  L.take((uint64_t)njobs * sizeof(QsEncJob));                       // the descriptors
   long long wgs = 0, swgs = 0;
   for (int i = 0; i < njobs; ++i) {
     if (int r = describe(jobs[i], &D[i], P ? &(*P)[i] : nullptr, need_arrays, info ? &info[i] : nullptr, Who(who, i).s))
@@ -273,45 +232,21 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* c
     J.swg0 = (int)swgs;
     swgs += J.nswg;
     if (wgs > 0x7fffffffLL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
-    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += align_up(bytes, 256); return at; };
-    J.off_state = take(sizeof(QsEncState));
-    J.off_bits = take(slots * 2);
-    J.off_wgsum = take((uint64_t)J.nwg * 4);
-    J.off_wgoff = take((uint64_t)J.nwg * 8);
-    J.off_raw = take(J.raw_cap);
-    J.off_ffcnt = take(chunks * 4);
-    J.off_ffoff = take(chunks * 8);
-    J.off_rrel = take(nint * 4);
-    J.off_rd = take((nint + 1) * 8);
-    J.off_rp = take((nint + 1) * 8);
+    J.off_state = L.take(sizeof(QsEncState));
+    J.off_bits = L.take(slots * 2);
+    J.off_wgsum = L.take((uint64_t)J.nwg * 4);
+    J.off_wgoff = L.take((uint64_t)J.nwg * 8);
+    J.off_raw = L.take(J.raw_cap);
+    J.off_ffcnt = L.take(chunks * 4);
+    J.off_ffoff = L.take(chunks * 8);
+    J.off_rrel = L.take(nint * 4);
+    J.off_rd = L.take((nint + 1) * 8);
+    J.off_rp = L.take((nint + 1) * 8);
     // every byte stuffed; per interval end a pad byte that may be stuffed, and the two bytes of the marker
     if (info) info[i].max_segment_bytes = 2 * (((uint64_t)nblocks * QS_ENC_MAXBITS + 7) / 8) + 4 * (nint - 1);
   }
-  *total = off;
+  *total = L.total;
   return QS_HIP_OK;
-}
-
-int check_ws(uint64_t need, const void* d_workspace, size_t bytes, const char* who) {
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < need)
-    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %llu", who, bytes,
-                   (unsigned long long)need);
-  return QS_HIP_OK;
-}
-
-int device_ok() {
-  if (qs_hip_device_count() <= 0)
-    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-  return QS_HIP_OK;
-}
-
-template <class F> int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
 }
 
 // the whole-file run's scratch (qs_hip_encode_files_scratch_bytes): byte offsets of its arrays
@@ -319,14 +254,13 @@ struct FilesScratch {
   uint64_t counts, codes, tables, prefix, tstatus, total;
   explicit FilesScratch(int njobs) {
     const uint64_t n = (uint64_t)std::max(njobs, 0);
-    uint64_t off = 0;
-    auto take = [&](uint64_t b) { const uint64_t at = off; off += align_up(b, 256); return at; };
-    counts = take(n * 4 * 257 * 4);
-    codes = take(n * QS_ENC_CODES * 4);
-    tables = take(n * QS_ENC_TABLES_BYTES);
-    prefix = take(n * 8);
-    tstatus = take(n * 4);
-    total = off;
+    Layout L;
+    counts = L.take(n * 4 * 257 * 4);
+    codes = L.take(n * QS_ENC_CODES * 4);
+    tables = L.take(n * QS_ENC_TABLES_BYTES);
+    prefix = L.take(n * 8);
+    tstatus = L.take(n * 4);
+    total = L.total;
   }
 };
 
@@ -369,11 +303,11 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
                            who, i, v);
         }
       }
-    if (!F->d_scratch || (reinterpret_cast<uintptr_t>(F->d_scratch) & 255) || F->scratch_bytes < FS.total)
+    if (!workspace_ok(F->d_scratch, F->scratch_bytes, FS.total))
       return qs_fail(QS_HIP_EINVAL, "%s: scratch of %zu bytes (256-byte aligned), %d jobs need %llu", who, F->scratch_bytes,
                      njobs, (unsigned long long)FS.total);
   }
-  if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+  if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
   // the kernels to launch follow what prepare wrote at this address.  An address not known here (a copy of a prepared
   // workspace, or one of more than QS_ENC_PREPARED_MAX) runs without restarts, as it always did; the kernels give
   // status 4 to a job whose descriptor has an interval nevertheless, so a lost marker is never silent
@@ -389,7 +323,7 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
       chunk_restart = it->second.chunk_restart;
     }
   }
-  if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+  if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
   if (int r = device_ok()) return r;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int j0 = 0; j0 < njobs; j0 += QS_ENC_CHUNK) {
@@ -497,11 +431,9 @@ int prepare_opts(qs_hip_job* const* jobs, int njobs, const qs_hip_huff_tables* c
         if (int r = derive(ac, false, D[(size_t)i].ac[t], 256, who, what)) return r;
       }
     }
-    if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+    if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QsEncJob), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
+    if (int r = upload(d_workspace, D, static_cast<hipStream_t>(stream))) return r;
     Prepared p{njobs, total, 0, std::vector<uint8_t>((size_t)ceil_div(njobs, QS_ENC_CHUNK), 0)};
     for (int i = 0; i < njobs; ++i)
       if (D[(size_t)i].ri[0] || D[(size_t)i].ri[1]) p.chunk_restart[(size_t)(i / QS_ENC_CHUNK)] = 1;

@@ -8,6 +8,7 @@
 #include <system_error>
 
 #include "qs_jobint.h"
+#include "qs_stage.h"
 
 // ---------------------------------------------------------------------------
 // job layer
@@ -667,22 +668,16 @@ int qsj::do_quantsmooth_impl(qs_hip_job* job, int flags, int niter, int progprec
   return r;
 }
 
-// The C ABI never lets a C++ exception (std::bad_alloc from the host-side containers) escape.
+// The C ABI never lets a C++ exception (std::bad_alloc from the host-side containers) escape: guarded, qs_stage.h.
 extern "C" int qs_hip_do_quantsmooth(qs_hip_job* job, int flags, int niter, int progprec,
                                      qs_hip_progress_fn progress, void* userdata) {
   struct Kick { ~Kick() { kick_background(); } } kick;   // staging blocks this call missed are pinned afterwards
-  try {
-    return do_quantsmooth_impl(job, flags, niter, progprec, progress, userdata);
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
+  return guarded([&] { return do_quantsmooth_impl(job, flags, niter, progprec, progress, userdata); });
 }
 
 extern "C" int qs_hip_do_quantsmooth_rows(qs_hip_job* job, int16_t* const* const* rows, int flags, int niter, int progprec,
                                           qs_hip_progress_fn progress, void* userdata) {
-  try {
+  return guarded([&]() -> int {
     if (!job || !rows || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC)
       return qs_fail(QS_HIP_EINVAL, "qs_hip_do_quantsmooth_rows: bad job");
     for (int ci = 0; ci < job->ncomp; ++ci) {
@@ -693,15 +688,11 @@ extern "C" int qs_hip_do_quantsmooth_rows(qs_hip_job* job, int16_t* const* const
     struct Kick { ~Kick() { kick_background(); } } kick;
     RowScope scope(rows);
     return do_quantsmooth_impl(job, flags, niter, progprec, progress, userdata);
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
+  });
 }
 
 extern "C" int qs_hip_do_quantsmooth_sharded(qs_hip_job* job, int flags, int niter, const int* devices, int ndev) {
-  try {
+  return guarded([&]() -> int {
     if (!devices || ndev < 1) return qs_fail(QS_HIP_EINVAL, "qs_hip_do_quantsmooth_sharded: empty device list");
     struct Kick { ~Kick() { kick_background(); } } kick;
     const int todo = prepare_job(job, flags, &niter);
@@ -713,9 +704,5 @@ extern "C" int qs_hip_do_quantsmooth_sharded(qs_hip_job* job, int flags, int nit
     if (r == JOB_RERUN_CAREFUL)
       r = run_job(job, flags, niter, 0, nullptr, nullptr, /*eager=*/false);
     return r;
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
+  });
 }

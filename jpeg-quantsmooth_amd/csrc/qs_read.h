@@ -234,49 +234,19 @@ QS_RD_HD int qr_build_table(const uint8_t* bits, const uint8_t* huffval, int is_
 
 // ---- geometry ------------------------------------------------------------------------------------------------------------
 
-// The scan of a frame whose one scan carries all its components (jdinput.c per_scan_setup): QsEncGeom as the coder
-// fills it, slot[c] = c.  stride / rows: the caller's arrays.  0 ok; 1 an array holds fewer blocks than libjpeg's
-// width_in_blocks x height_in_blocks, or bad factors; 2 more than 10 blocks in an MCU
+// The scan of a frame whose one scan carries all its components (jdinput.c per_scan_setup): the coder's QsEncGeom from
+// the coder's own function (qs_encode.h: qs_enc_geometry), slot[c] = c.  stride / rows: the caller's arrays.  0 ok; 1 an
+// array holds fewer blocks than libjpeg's width_in_blocks x height_in_blocks, or bad factors; 2 more than 10 blocks in
+// an MCU
 QS_RD_HD int qr_geometry(int ncomp, int W, int H, const int32_t* hsamp, const int32_t* vsamp, const int32_t* stride,
                          const int32_t* rows, QsEncGeom* g) {
   memset(g, 0, sizeof *g);
-  if (ncomp < 1 || ncomp > 4 || W < 1 || H < 1 || W > 65500 || H > 65500) return 1;
-  int mh = 1, mv = 1;
-  for (int c = 0; c < ncomp; ++c) {
+  if (ncomp < 1 || ncomp > 4) return 1;
+  for (int c = 0; c < ncomp; ++c)
     if (hsamp[c] < 1 || hsamp[c] > 4 || vsamp[c] < 1 || vsamp[c] > 4 || stride[c] < 1 || rows[c] < 1) return 1;
-    if (hsamp[c] > mh) mh = hsamp[c];
-    if (vsamp[c] > mv) mv = vsamp[c];
-  }
-  g->ncomp = ncomp;
-  for (int c = 0; c < ncomp; ++c) {
-    g->nw[c] = (int32_t)(((long long)W * hsamp[c] + 8LL * mh - 1) / (8LL * mh));
-    g->nh[c] = (int32_t)(((long long)H * vsamp[c] + 8LL * mv - 1) / (8LL * mv));
-    g->stride[c] = stride[c];
-    g->slot[c] = c;
-    if (stride[c] < g->nw[c] || rows[c] < g->nh[c]) return 1;
-  }
-  if (ncomp == 1) {                              // non-interleaved: an MCU is one block
-    g->hs[0] = g->vs[0] = 1;
-    g->bpm = 1;
-    g->mcus_x = g->nw[0];
-    g->mcus = g->nw[0] * g->nh[0];
-  } else {
-    int first = 0;
-    for (int c = 0; c < ncomp; ++c) {
-      g->hs[c] = hsamp[c];
-      g->vs[c] = vsamp[c];
-      g->first[c] = first;
-      first += hsamp[c] * vsamp[c];
-    }
-    if (first > 10) return 2;
-    g->bpm = first;
-    g->mcus_x = (W + 8 * mh - 1) / (8 * mh);
-    const long long mcus = (long long)g->mcus_x * ((H + 8 * mv - 1) / (8 * mv));
-    if (mcus * first > 0x7fff0000LL) return 1;
-    g->mcus = (int32_t)mcus;
-  }
-  g->nblocks = g->mcus * g->bpm;
-  return 0;
+  int detail;
+  const int why = qs_enc_geometry(ncomp, W, H, hsamp, vsamp, stride, rows, nullptr, g, &detail);
+  return why == QS_GEOM_OK ? 0 : why == QS_GEOM_MCU ? 2 : 1;
 }
 
 // the intervals of a scan with DRI value `dri` (0: none): MCUs per interval and their number

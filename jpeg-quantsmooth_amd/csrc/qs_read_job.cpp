@@ -8,11 +8,10 @@
 // alone.  The segment's length is not known before the run: the arrays that depend on it are sized for the longest
 // segment the geometry can have, and the kernels look no further.
 #include "qs_common.h"
+#include "qs_stage.h"
 #include "qs_read.h"
 
 #include <algorithm>
-#include <new>
-#include <vector>
 
 void qs_launch_read(const QrArgs& a, int zwgs, int mwgs, int dwgs, hipStream_t s);
 
@@ -21,19 +20,12 @@ static_assert(QS_RD_CHUNK == QS_HIP_READ_CHUNK && QS_RD_MAX_INTERVAL_BLOCKS == Q
 
 namespace {
 
-int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QrJob), 256); }
-
-struct Who {
-  char s[96];
-  Who(const char* who, int i) { snprintf(s, sizeof s, "%s: job %d", who, i); }
-};
+uint64_t descriptors_bytes(int njobs) { return align_up((uint64_t)njobs * sizeof(QrJob)); }
 
 // geometry, tables and intervals of one job; the code tables themselves only when `tables`
 int describe(const qs_hip_job* job, const qs_hip_read_opts* o, bool tables, QrJob* D, qs_hip_read_info* info,
              const char* who) {
-  if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);
+  if (int rc = check_job(job, who)) return rc;
   if (!o) return qs_fail(QS_HIP_EINVAL, "%s: no options (the tables of each component and the restart interval)", who);
   const int n = job->ncomp;
   memset(D, 0, sizeof *D);
@@ -58,8 +50,7 @@ int describe(const qs_hip_job* job, const qs_hip_read_opts* o, bool tables, QrJo
                      "standard table)", who, c);
     D->dc_tbl[c] = td;
     D->ac_tbl[c] = ta;
-    if ((long long)job->wblk[c] * job->hblk[c] > 0x7fffffffLL)
-      return qs_fail(QS_HIP_EINVAL, "%s: component %d has more than 2^31 blocks", who, c);
+    if (int rc = check_block_count(job, c, who)) return rc;
   }
   if (tables) {
     for (int t = 0; t < 8; ++t) {
@@ -90,7 +81,8 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_read_opts* con
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   if (!opts) return qs_fail(QS_HIP_EINVAL, "%s: null opts", who);
   D.assign((size_t)njobs, QrJob());
-  uint64_t off = descriptors_bytes(njobs);
+  Layout L;
+  L.take(descriptors_bytes(njobs));
   for (int i = 0; i < njobs; ++i) {
     if (int r = describe(jobs[i], opts[i], tables, &D[(size_t)i], info ? &info[i] : nullptr, Who(who, i).s)) return r;
     QrJob& J = D[(size_t)i];
@@ -98,37 +90,13 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_read_opts* con
     for (int c = 0; c < J.g.ncomp; ++c) blocks += (long long)jobs[i]->wblk[c] * jobs[i]->hblk[c];
     J.nzwg = qr_zero_wgs(blocks);
     const uint64_t chunks = (J.max_scan + 32) / QS_RD_MCHUNK + 2;
-    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += align_up(bytes, 256); return at; };
-    J.off_state = take(sizeof(QrState));
-    J.off_cnt = take(chunks * 4);
-    J.off_off = take(chunks * 4);
-    J.off_p = take(((uint64_t)J.intervals + 1) * 8);
+    J.off_state = L.take(sizeof(QrState));
+    J.off_cnt = L.take(chunks * 4);
+    J.off_off = L.take(chunks * 4);
+    J.off_p = L.take(((uint64_t)J.intervals + 1) * 8);
   }
-  *total = off;
+  *total = L.total;
   return QS_HIP_OK;
-}
-
-int check_ws(uint64_t need, const void* d_workspace, size_t bytes, const char* who) {
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < need)
-    return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned), the batch needs %llu", who, bytes,
-                   (unsigned long long)need);
-  return QS_HIP_OK;
-}
-
-int device_ok() {
-  if (qs_hip_device_count() <= 0)
-    return qs_fail(QS_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-  return QS_HIP_OK;
-}
-
-template <class F> int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return qs_fail(QS_HIP_ENOMEM, "out of host memory");
-  } catch (...) {
-    return qs_fail(QS_HIP_ENODEV, "unexpected internal error");
-  }
 }
 
 }  // namespace
@@ -153,12 +121,9 @@ extern "C" int qs_hip_read_device_batch_prepare(qs_hip_job* const* jobs, int njo
     std::vector<QrJob> D;
     uint64_t total = 0;
     if (int r = describe_all(jobs, njobs, opts, true, D, nullptr, &total, who)) return r;
-    if (int r = check_ws(total, d_workspace, bytes, who)) return r;
+    if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(d_workspace, D.data(), D.size() * sizeof(QrJob), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));                      // (a pageable source: it must outlive the copy)
-    return QS_HIP_OK;
+    return upload(d_workspace, D, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -172,7 +137,7 @@ extern "C" int qs_hip_read_device_batch(qs_hip_job* const* jobs, int njobs, cons
     const char* who = "qs_hip_read_device_batch";
     if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
     if (!d_scan || !scan_bytes || !d_status) return qs_fail(QS_HIP_EINVAL, "%s: null argument", who);
-    if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) || bytes < descriptors_bytes(njobs))
+    if (!workspace_ok(d_workspace, bytes, descriptors_bytes(njobs)))
       return qs_fail(QS_HIP_EINVAL, "%s: workspace of %zu bytes (256-byte aligned): not what prepare was given", who, bytes);
     if (int r = device_ok()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -188,7 +153,7 @@ extern "C" int qs_hip_read_device_batch(qs_hip_job* const* jobs, int njobs, cons
       for (int k = 0; k < a.n; ++k) {
         const qs_hip_job* job = jobs[j0 + k];
         const Who w(who, j0 + k);
-        if (!job || job->ncomp < 1 || job->ncomp > QS_HIP_MAXC) return qs_fail(QS_HIP_EINVAL, "%s: bad job", w.s);
+        if (int rc = check_job(job, w.s)) return rc;
         if (!d_scan[j0 + k]) return qs_fail(QS_HIP_EINVAL, "%s: no scan bytes", w.s);
         QsEncGeom g;
         if (int rc = qr_geometry(job->ncomp, job->image_width, job->image_height, job->hsamp, job->vsamp, job->wblk,
@@ -198,10 +163,8 @@ extern "C" int qs_hip_read_device_batch(qs_hip_job* const* jobs, int njobs, cons
         QrPtrs& P = a.p[k];
         for (int c = 0; c < job->ncomp; ++c) {
           int16_t* arr = job->coef[c];
-          if (!arr || (reinterpret_cast<uintptr_t>(arr) & 15))
-            return qs_fail(QS_HIP_EINVAL, "%s: component %d has no data or is not 16-byte aligned", w.s, c);
-          if ((long long)job->wblk[c] * job->hblk[c] > 0x7fffffffLL)
-            return qs_fail(QS_HIP_EINVAL, "%s: component %d has more than 2^31 blocks", w.s, c);
+          if (int rc = check_array(arr, c, false, w.s)) return rc;
+          if (int rc = check_block_count(job, c, w.s)) return rc;
           P.coef[c] = arr;
           P.nblk[c] = job->wblk[c] * job->hblk[c];
           blocks += P.nblk[c];
