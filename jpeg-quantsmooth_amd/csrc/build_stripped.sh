@@ -7,7 +7,8 @@
 #   * the LLVM tools are the ones hipcc itself would run (`hipcc --print-prog-name=clang`), not a hard-coded prefix;
 #   * every intermediate lives in a private mktemp directory that is removed on every exit path;
 #   * a failed GUARD (v_ashr_pk_u8_i32 selected, a scalar load read before its wait, fewer removable no-ops than
-#     <min-removed>) fails the build;
+#     <min-removed>, and with QS_BUDGET_CHECK=1 a recovery kernel over its register / scratch / LDS budget,
+#     check_kernel_budget.py) fails the build;
 #   * missing LLVM tools or a bundle the toolchain refuses do NOT: the object is then built by the plain one-step
 #     `hipcc -c` (correct, 2-6 % slower kernels) with a warning -- unless QS_REQUIRE_STRIP=1.
 set -u
@@ -33,6 +34,11 @@ grep -v "argument unused during compilation" "$B.err" >&2
 if grep -q v_ashr_pk_u8_i32 "$B.isa.s"; then echo "ERROR: v_ashr_pk_u8_i32 selected" >&2; exit 1; fi
 if ! python3 "$HERE/check_inflight.py" "$B.isa.s"; then
   echo "ERROR: a hand-placed scalar load is read or moved before its wait" >&2; exit 1; fi
+# register / scratch / LDS budget of the four recovery kernels, from the code-object metadata alone.  Asked for by
+# csrc/Makefile for the shipped translation unit (QS_BUDGET_CHECK=1); the measurement variants of
+# tools/build_variants.sh, some of which are over budget on purpose, build without it.
+if [ "${QS_BUDGET_CHECK:-0}" = 1 ] && ! python3 "$HERE/check_kernel_budget.py" "$B.isa.s"; then
+  echo "ERROR: a recovery kernel misses its budget of 168 VGPRs, no scratch and 54,613 B of LDS" >&2; exit 1; fi
 python3 "$HERE/strip_asm_nops.py" "$B.isa.s" "$B.dev.s" --min-removed "$FLOOR" || exit 1
 if ! python3 "$HERE/check_inflight.py" "$B.dev.s" > "$B.chk" 2>&1; then
   cat "$B.chk" >&2; echo "ERROR: the stripped assembly fails the in-flight check" >&2; exit 1; fi

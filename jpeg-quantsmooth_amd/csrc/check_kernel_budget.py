@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Build guard for qs_kernels.hip (csrc/build_stripped.sh): the four recovery kernels -- qs_smooth_plane_kernel and
+qs_smooth_set_kernel, each with and without DIAGONALS -- must keep three waves per SIMD and three workgroups per CU with
+nothing in scratch.  The luma instantiations hold 144 pixel differences in registers and sit a few registers under the
+limit: a toolchain or a source change that tips them over would still build, and run 10-40 % slower on spills or at
+two waves per SIMD (LABNOTES.md 4.2).
+
+Reads the code-object metadata the compiler prints into the device assembly (the `amdhsa.kernels` list between
+.amdgpu_metadata and .end_amdgpu_metadata) and nothing else -- no instruction is looked at:
+    .private_segment_fixed_size == 0      no spills, no scratch
+    .vgpr_count <= 168                    512 / 3 registers per lane, in the allocation granule of 8
+    .group_segment_fixed_size <= 54613    160 KiB of LDS / 3 workgroups
+
+usage: check_kernel_budget.py <device.s>      exit status 1 (with the offending kernels named) when a budget is missed
+"""
+import re
+import sys
+
+KERNELS = ("qs_smooth_plane_kernel", "qs_smooth_set_kernel")
+MAX_VGPRS = 168
+MAX_LDS = 160 * 1024 // 3
+FIELDS = ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count")
+
+
+def kernel_records(text):
+    """{symbol: {field: int}} of the metadata block"""
+    m = re.search(r"^\s*\.amdgpu_metadata\s*$(.*?)^\s*\.end_amdgpu_metadata\s*$", text, re.S | re.M)
+    if not m:
+        return {}
+    # The list is YAML as LLVM prints it: a kernel record opens with "  - .<field>:" (its argument list, whose items sit
+    # deeper) and its scalar fields follow at four columns.
+    recs, cur = [], None
+    for line in m.group(1).split("\n"):
+        if re.match(r"  - \.", line):
+            cur = {}
+            recs.append(cur)
+            line = "    " + line[4:]
+        f = re.match(r"    \.(\w+):\s*(\S+)\s*$", line)
+        if f and cur is not None:
+            cur[f.group(1)] = f.group(2)
+    return {r["name"]: {k: int(r[k]) for k in FIELDS if k in r} for r in recs if "name" in r}
+
+
+def main(path):
+    recs = {n: r for n, r in kernel_records(open(path).read()).items() if any(k in n for k in KERNELS)}
+    if len(recs) != 4 or any(len(r) != len(FIELDS) for r in recs.values()):
+        print(f"check_kernel_budget: ERROR: expected the metadata of 4 recovery kernels in {path}, found {sorted(recs)}", file=sys.stderr)
+        return 1
+    bad = 0
+    for n, r in sorted(recs.items()):
+        why = []
+        if r["private_segment_fixed_size"] != 0:
+            why.append(f"{r['private_segment_fixed_size']} B of scratch per lane (spills)")
+        if r["vgpr_count"] > MAX_VGPRS:
+            why.append(f"{r['vgpr_count']} VGPRs > {MAX_VGPRS} (three waves per SIMD)")
+        if r["group_segment_fixed_size"] > MAX_LDS:
+            why.append(f"{r['group_segment_fixed_size']} B of LDS > {MAX_LDS} (three workgroups per CU)")
+        print(f"check_kernel_budget: {n}: {r['vgpr_count']} VGPRs, {r['private_segment_fixed_size']} B scratch, "
+              f"{r['group_segment_fixed_size']} B LDS" + (" -- ERROR: " + "; ".join(why) if why else ""),
+              file=sys.stderr if why else sys.stdout)
+        bad += bool(why)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1]))

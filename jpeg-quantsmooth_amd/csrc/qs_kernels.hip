@@ -14,12 +14,18 @@
 // quantiser data and control flow are wave-uniform (scalar loads + uniform
 // branches) and nothing diverges.
 //
-// Per-lane state: the block's 64 pixels (scaled by 2^-12, see QS_TERM_D) and the
-// 32 edge differences live in VGPRs as exact small floats, so an interior pixel
-// difference is one v_sub_f32; the 32 neighbour-edge pixels stay packed four to
-// a VGPR; the 64 int16 coefficients live in LDS, one dword column per lane
-// (stride 65 dwords => conflict-free both for the per-lane column accesses and
-// for the coalesced-load transpose).  147 VGPRs => 3 waves per SIMD.
+// Per-lane state: pixel DIFFERENCES (scaled by 2^-12, see QS_TERM_D) as exact small
+// floats in VGPRs.  The luma walk holds all of them -- 56 horizontal, 56 vertical,
+// 32 edge differences, re-formed at each refresh -- and no pixels; its 32
+// neighbour-edge pixels (packed four to a dword), its rebalance sums and one stash
+// slot sit in LDS behind the coefficient columns (QS_X_*).  The DIAGONALS walk
+// (210 differences: they cannot fit) holds the block's 64 pixels, the 32 edge
+// differences and the first 32 horizontal ones, so that most interior differences
+// are one v_sub_f32 per term, and keeps the neighbour pixels in 8 VGPRs.  The 64
+// int16 coefficients live in LDS, one dword column per lane (stride 65 dwords =>
+// conflict-free both for the per-lane column accesses and for the coalesced-load
+// transpose).  161-168 of the 168 VGPRs that 3 waves per SIMD allow
+// (csrc/check_kernel_budget.py fails the build beyond that).
 //
 // This translation unit holds the SHIPPED kernels only.  The variants that were built and
 // measured on the way (and lost) are kept, compilable, under tools/experiments/ and are
@@ -312,15 +318,15 @@ __device__ __forceinline__ void lds_set_coef(uint32_t* col, int i, int v) {
 // rules: loads and their s_waitcnt in ONE statement, early-clobber outputs -- nothing is in flight at a statement's end).
 // Row r of the column (coefficients 2r, 2r + 1) sits r * QS_LDS_PITCH dwords = r * 260 bytes in.
 static_assert(QS_LDS_PITCH * 4 == 260, "the literal offsets below assume a 260-byte row pitch");
-#define QS_LDS16_GROUP(BASE, W, N0) \
-  asm volatile("ds_read_i16 %0, %16\n\tds_read_i16 %1, %16 offset:2\n\t" \
-               "ds_read_i16 %2, %16 offset:260\n\tds_read_i16 %3, %16 offset:262\n\t" \
-               "ds_read_i16 %4, %16 offset:520\n\tds_read_i16 %5, %16 offset:522\n\t" \
-               "ds_read_i16 %6, %16 offset:780\n\tds_read_i16 %7, %16 offset:782\n\t" \
-               "ds_read_i16 %8, %16 offset:1040\n\tds_read_i16 %9, %16 offset:1042\n\t" \
-               "ds_read_i16 %10, %16 offset:1300\n\tds_read_i16 %11, %16 offset:1302\n\t" \
-               "ds_read_i16 %12, %16 offset:1560\n\tds_read_i16 %13, %16 offset:1562\n\t" \
-               "ds_read_i16 %14, %16 offset:1820\n\tds_read_i16 %15, %16 offset:1822\n\t" \
+#define QS_LDS16_GROUP(BASE, W, N0, O) \
+  asm volatile("ds_read_i16 %0, %16 offset:" #O "\n\tds_read_i16 %1, %16 offset:" #O "+2\n\t" \
+               "ds_read_i16 %2, %16 offset:" #O "+260\n\tds_read_i16 %3, %16 offset:" #O "+262\n\t" \
+               "ds_read_i16 %4, %16 offset:" #O "+520\n\tds_read_i16 %5, %16 offset:" #O "+522\n\t" \
+               "ds_read_i16 %6, %16 offset:" #O "+780\n\tds_read_i16 %7, %16 offset:" #O "+782\n\t" \
+               "ds_read_i16 %8, %16 offset:" #O "+1040\n\tds_read_i16 %9, %16 offset:" #O "+1042\n\t" \
+               "ds_read_i16 %10, %16 offset:" #O "+1300\n\tds_read_i16 %11, %16 offset:" #O "+1302\n\t" \
+               "ds_read_i16 %12, %16 offset:" #O "+1560\n\tds_read_i16 %13, %16 offset:" #O "+1562\n\t" \
+               "ds_read_i16 %14, %16 offset:" #O "+1820\n\tds_read_i16 %15, %16 offset:" #O "+1822\n\t" \
                "s_waitcnt lgkmcnt(0)" \
                : "=&v"(W[(N0) + 0]), "=&v"(W[(N0) + 1]), "=&v"(W[(N0) + 2]), "=&v"(W[(N0) + 3]), \
                  "=&v"(W[(N0) + 4]), "=&v"(W[(N0) + 5]), "=&v"(W[(N0) + 6]), "=&v"(W[(N0) + 7]), \
@@ -331,10 +337,20 @@ __device__ __forceinline__ void lds_read_block_i16(const uint32_t* col, uint32_t
   typedef const __attribute__((address_space(3))) uint32_t* lds_ptr;    // generic -> LDS address space: the DS byte address
   const uint32_t a0 = (uint32_t)(uintptr_t)(lds_ptr)col;
   const uint32_t a1 = a0 + 8 * 260, a2 = a0 + 16 * 260, a3 = a0 + 24 * 260;
-  QS_LDS16_GROUP(a0, ws, 0);
-  QS_LDS16_GROUP(a1, ws, 16);
-  QS_LDS16_GROUP(a2, ws, 32);
-  QS_LDS16_GROUP(a3, ws, 48);
+  QS_LDS16_GROUP(a0, ws, 0, 0);
+  QS_LDS16_GROUP(a1, ws, 16, 0);
+  QS_LDS16_GROUP(a2, ws, 32, 0);
+  QS_LDS16_GROUP(a3, ws, 48, 0);
+}
+// the same from the column pointer alone, the row groups as immediate offsets (luma walk: the three derived
+// addresses above otherwise stay live from the prologue to the epilogue)
+__device__ __forceinline__ void lds_read_block_i16_1(const uint32_t* col, uint32_t (&ws)[64]) {
+  typedef const __attribute__((address_space(3))) uint32_t* lds_ptr;
+  const uint32_t a0 = (uint32_t)(uintptr_t)(lds_ptr)col;
+  QS_LDS16_GROUP(a0, ws, 0, 0);
+  QS_LDS16_GROUP(a0, ws, 16, 2080);
+  QS_LDS16_GROUP(a0, ws, 32, 4160);
+  QS_LDS16_GROUP(a0, ws, 48, 6240);
 }
 
 // One term of the weighted least-squares sums, reference quantsmooth.h:1519-1520:
@@ -372,7 +388,7 @@ typedef int qs_i4 __attribute__((ext_vector_type(4)));         // one per-coeffi
 // waves per workgroup: the waves of a workgroup share nothing (each has its own
 // LDS slice), so the size only sets the dispatch granularity
 #define QS_WAVES_PER_WG 4
-// register budget: 3 waves per SIMD (168 VGPRs; the kernel uses 147).  Measured: 2 waves per SIMD -11 %, a
+// register budget: 3 waves per SIMD (168 VGPRs; the four instantiations use 161, 162, 164 and 168).  Measured: 2 waves per SIMD -11 %, a
 // 4-wave budget (128 VGPRs, edge differences recomputed per term) -7.5 % (LABNOTES.md 4.2).
 #define QS_SMOOTH_MIN_WAVES 3
 // workgroups the chip holds at once = 256 CUs x 3 (a workgroup puts one wave on each of a CU's four SIMDs):
@@ -431,11 +447,10 @@ typedef int qs_i4 __attribute__((ext_vector_type(4)));         // one per-coeffi
           "v_add_f32 %[e], %[e], %[d]" \
           : [n] "+v"(num), [e] "+v"(den), [d] "=&v"(d_), [t] "=&v"(t_) \
           : [a] "v"(D), [w] "s"(W), [r] "s"(Rs)); }
-// The first QS_HOIST horizontal differences (rows 0, 1 and most of row 2) are kept in registers between refreshes
-// instead of being re-formed for every coefficient: the kernel has ~20 VGPRs to spare under its 3-waves-per-SIMD
-// budget (168).  Measured A/B, identical results (profiles/r04d_hoist): 14, 20 and 26 hoisted differences are all
-// 2.3 % faster per plane launch at 8192^2 (1.597 -> 1.560 ms), 3 % at 128-512 block rows, +0.7 % in the 12-plane bench.
-#define QS_HOIST 20
+// DIAGONALS walk: the first QS_HOIST_DIAG horizontal differences (rows 0..3 and most of row 4) are kept in registers
+// between refreshes instead of being re-formed for every coefficient -- as many as its 3-waves-per-SIMD budget (168)
+// leaves.  The luma walk started the same way with 20 of them (profiles/r04d_hoist: +2.3 % per plane launch) and now
+// holds all 112 interior differences (qs_smooth_kernel.inc, profiles/r07a_resident: another +3.2 % on the bench line).
 #ifndef QS_HOIST_DIAG
 #define QS_HOIST_DIAG 32   /* the DIAGONALS kernel: 152 VGPRs at 20 */
 #endif
@@ -446,6 +461,31 @@ typedef int qs_i4 __attribute__((ext_vector_type(4)));         // one per-coeffi
 #ifndef QS_STASH
 #define QS_STASH 1
 #endif
+// The luma (non-DIAGONALS) walk keeps all 112 interior pixel differences and the 32 edge differences in VGPRs and no
+// pixels at all; what else used to live in registers across the walk sits in LDS, QS_X_DWORDS dwords per lane behind the
+// wave's coefficient columns (dword index n of lane l: 32 * QS_LDS_PITCH + n * 64 + l, an immediate offset from the
+// lane's column pointer).  3 workgroups per CU leave 160 KiB / 3 = 54,613 B each: 33,280 B of columns + 20 KiB.
+#define QS_X_STASH 0     /* 8: the one stash slot (pass-1 output of block column 0, later 7) */
+#define QS_X_EDGE 8      /* 8: neighbour edge pixels, packed four to a dword */
+#define QS_X_REB 16      /* 4: the two 64-bit rebalance sums, as [2][64] uint64 */
+#define QS_X_DWORDS 20
+static_assert(QS_WAVES_PER_WG * (32 * QS_LDS_PITCH + QS_X_DWORDS * 64) * 4 <= 160 * 1024 / 3, "LDS budget of three workgroups per CU");
+// a 64-bit sum kept in the lane's own LDS slot: one ds_add_u64 without return -- no register holds the sum and no
+// wait follows (the LDS pipe of this kernel idles; each slot has a single writer, its lane)
+typedef unsigned long long __attribute__((address_space(3))) qs_lds_u64;
+__device__ __forceinline__ void qs_lds_add64(qs_lds_u64* p, long long v) {
+  __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// The lane's slot of sum n (0 / 1), derived where it is used from the one per-lane pointer that is live anyway: the
+// column address is the wave's base + 4 * lane, the slot's is the base + constant + 8 * lane.  The opaque copy keeps the
+// result from being hoisted into a register of its own for the whole walk (one v_mov + one v_lshl_add per use).
+__device__ __forceinline__ qs_lds_u64* qs_xreb(const uint32_t* col, const uint32_t* lds, int n) {
+  typedef const __attribute__((address_space(3))) uint32_t* lds_ptr;
+  uint32_t a = (uint32_t)(uintptr_t)(lds_ptr)col;
+  asm volatile("" : "+v"(a));
+  const uint32_t b = (uint32_t)(uintptr_t)(lds_ptr)lds;
+  return (qs_lds_u64*)(a * 2u - b + (uint32_t)((32 * QS_LDS_PITCH + (QS_X_REB + 2 * n) * 64) * 4));
+}
 
 // The recovery kernel (qs_smooth_kernel.inc): one plane, and a set of planes (job / batch layer: parameters come
 // from the plane set in the kernarg segment instead of from scalar arguments)

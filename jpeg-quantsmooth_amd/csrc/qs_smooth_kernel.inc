@@ -11,11 +11,14 @@ template <bool DIAG>
 __global__ void __launch_bounds__(64 * QS_WAVES_PER_WG, QS_SMOOTH_MIN_WAVES)
 #ifdef QS_SMOOTH_SET
 QS_SMOOTH_KERNEL_NAME(const QsPlaneSet set, int final_clamp) {
-  __shared__ uint32_t lds_all[QS_WAVES_PER_WG][32 * QS_LDS_PITCH];
+  // the luma walk (!DIAG) keeps 20 more dwords per lane behind its coefficient columns (QS_X_*, qs_kernels.hip): one
+  // stash slot, the packed neighbour pixels and the two rebalance sums -- everything at an immediate offset from `col`
+  __shared__ __attribute__((aligned(16))) uint32_t lds_all[QS_WAVES_PER_WG][32 * QS_LDS_PITCH + (DIAG ? 0 : QS_X_DWORDS * 64)];
 #if QS_STASH
-  __shared__ uint32_t stash_all[QS_WAVES_PER_WG][2 * 8 * 64];   // pass-1 outputs of two block columns per lane, see the refresh
+  __shared__ uint32_t stash_all[QS_WAVES_PER_WG][2 * 8 * 64];   // (DIAG only) pass-1 outputs of two block columns per lane, see the refresh
 #endif
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // (luma walk: the wave index is made scalar, so that the wave's LDS base is no per-lane value that stays live across the walk)
+  const int lane = threadIdx.x & 63, wave = DIAG ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t* lds = lds_all[wave];
   uint32_t* col = lds + lane;
   const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * QS_WAVES_PER_WG + wave));
@@ -38,11 +41,14 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
   // blocks [blk_begin, blk_end) of the plane (linear, row-major): the whole
   // plane, or the interior / the edge block rows of a band when the halo
   // exchange is overlapped with the interior (bands.py)
-  __shared__ uint32_t lds_all[QS_WAVES_PER_WG][32 * QS_LDS_PITCH];
+  // the luma walk (!DIAG) keeps 20 more dwords per lane behind its coefficient columns (QS_X_*, qs_kernels.hip): one
+  // stash slot, the packed neighbour pixels and the two rebalance sums -- everything at an immediate offset from `col`
+  __shared__ __attribute__((aligned(16))) uint32_t lds_all[QS_WAVES_PER_WG][32 * QS_LDS_PITCH + (DIAG ? 0 : QS_X_DWORDS * 64)];
 #if QS_STASH
-  __shared__ uint32_t stash_all[QS_WAVES_PER_WG][2 * 8 * 64];   // pass-1 outputs of two block columns per lane, see the refresh
+  __shared__ uint32_t stash_all[QS_WAVES_PER_WG][2 * 8 * 64];   // (DIAG only) pass-1 outputs of two block columns per lane, see the refresh
 #endif
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // (luma walk: the wave index is made scalar, so that the wave's LDS base is no per-lane value that stays live across the walk)
+  const int lane = threadIdx.x & 63, wave = DIAG ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t* lds = lds_all[wave];
   uint32_t* col = lds + lane;
   const int nblk = blk_end;
@@ -64,6 +70,11 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
   // ---- stage the wave's 64 blocks (8 KiB contiguous): 16 B per lane per
   // load, fully coalesced, transposed through LDS into per-lane columns.
   uint4* gsrc = reinterpret_cast<uint4*>(coef) + (size_t)base * 8;
+  // (luma walk) Does the wave hold a coefficient outside [-0x2000, 0x2000) -- bits 15..13 of an int16 not all equal?  No
+  // job does (its dequantised coefficients pass the +-2048 range check and move by less than a quantiser < 0x800), and
+  // two shortcuts of the walk rest on it, see the coefficient update.  Collected on the packed pairs as they are staged.
+  uint32_t bigacc = 0;
+#define QS_BIG_ACC(V) if constexpr (!DIAG) bigacc |= ((V).x ^ ((V).x << 1)) | ((V).y ^ ((V).y << 1)) | ((V).z ^ ((V).z << 1)) | ((V).w ^ ((V).w << 1))
 #ifdef QS_SMOOTH_SET
   // A plane whose dequantisation pass A deferred (QS_PLANE_QUANT, wave-uniform): the coefficients in HBM are still the
   // file's quantised ones, and the products pass A formed and range-checked -- coef * qraw, wrapped to int16 -- are
@@ -80,6 +91,7 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       uint4 v = make_uint4(0, 0, 0, 0);
       if (idx < nvec) v = gsrc[idx];
       v = qs_dequant8<false>(v, q, unused);
+      QS_BIG_ACC(v);
       uint32_t* dst = lds + m0 * QS_LDS_PITCH + (j * 8 + (lane >> 3));
       dst[0] = v.x; dst[QS_LDS_PITCH] = v.y; dst[2 * QS_LDS_PITCH] = v.z; dst[3 * QS_LDS_PITCH] = v.w;
     }
@@ -92,6 +104,7 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       const int idx = j * 64 + lane;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (idx < nvec) v = gsrc[idx];
+      QS_BIG_ACC(v);
       uint32_t* dst = lds + m0 * QS_LDS_PITCH + (j * 8 + (lane >> 3));
       dst[0] = v.x; dst[QS_LDS_PITCH] = v.y; dst[2 * QS_LDS_PITCH] = v.z; dst[3 * QS_LDS_PITCH] = v.w;
     }
@@ -119,22 +132,39 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
     edge[6] = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
     edge[7] = r[4] | (r[5] << 8) | (r[6] << 16) | (r[7] << 24);
   }
+  // the lane's own dwords behind the columns (luma walk): written once here, the neighbour pixels read at each refresh
+  uint32_t* const xcol = col + 32 * QS_LDS_PITCH;
+  if constexpr (!DIAG) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xcol[(QS_X_EDGE + e) * 64] = edge[e];
+    *qs_xreb(col, lds, 0) = 0; *qs_xreb(col, lds, 1) = 0;
+  }
   wave_lds_sync();
 
   constexpr int TS = DIAG ? 272 : 160;
-  float px[64];   // own pixels * 2^-12
+  // Terms read pixel DIFFERENCES only, and pixels change only at a refresh.  The luma walk (!DIAG) therefore holds no
+  // pixels at all: its 56 horizontal differences dh[y * 7 + x] = px[y][x] - px[y][x + 1], its 56 vertical ones
+  // dv[y * 8 + x] = px[y][x] - px[y + 1][x] and the 32 edge differences bd[] are formed once per refresh, row by row
+  // behind pass 2, and every term is the eight-instruction QS_TERM_D_ASM.  Each difference is the same single f32
+  // subtraction of the same two operands as before (exact: integers scaled by 2^-12), formed once instead of once
+  // per coefficient.  The DIAGONALS walk has 210 differences, which cannot fit: it keeps its pixels and hoists the
+  // first NH horizontal differences, as many as its 3-waves-per-SIMD register budget leaves.
+  float px[DIAG ? 64 : 1];   // (DIAG) own pixels * 2^-12
   float bd[32];   // own edge pixel minus neighbour pixel, * 2^-12 (top, bottom, left, right)
-  // the first NH horizontal differences (rows 0.., x = 0..6), held between refreshes: as many as the 3-waves-per-SIMD
-  // register budget leaves -- the DIAGONALS instantiation allocates 14 registers fewer for the rest and hoists that many more
-  constexpr int NH = DIAG ? QS_HOIST_DIAG : QS_HOIST;
-  float hd[NH];
+  constexpr int NH = DIAG ? QS_HOIST_DIAG : 1;
+  float hd[NH];              // (DIAG) the first NH horizontal differences (rows 0.., x = 0..6), held between refreshes
+  float dh[DIAG ? 1 : 56], dv[DIAG ? 1 : 56];   // (luma) all interior differences
 
   int kfirst = 63;
 #if QS_STASH
   int stash_hi = 0;   // bit 0 / 1: column 6 / 7's final pass-1 output is in its stash slot (wave-uniform)
 #endif
-  uint32_t chg = 0;   // any coefficient of this lane's block changed since the last refresh
-  long long reb_m0 = 0, reb_m1 = 0;   // sum c*orig, sum orig*orig over the 63 AC coefficients (rebalance step)
+  uint32_t chg = 0;   // (DIAG) any coefficient of this lane's block changed since the last refresh
+  uint64_t chg_any = 0;   // (luma) the same as a mask of the wave's lanes: SGPRs, the refresh ballot is its only reader
+#undef QS_BIG_ACC
+  const bool big_wave = !DIAG && __builtin_amdgcn_ballot_w64((bigacc & 0xC000C000u) != 0) != 0;   // (wave-uniform)
+  // sum c*orig, sum orig*orig over the 63 AC coefficients (rebalance step); the luma walk keeps them in LDS (xreb)
+  long long reb_m0 = 0, reb_m1 = 0;
   // Scalar operands.  Everything about coefficient k comes from its 16-byte record (QsConsts::rec); the weights
   // stream through two 16-SGPR buffers (WA / WB), one 16-float chunk per pipeline step (QS_ISSUE / QS_LAND below).
   const float* tabp = cst->tab;
@@ -161,12 +191,13 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
     // A wave skips the IDCT when NONE of its 64 blocks changed a coefficient in the last
     // anti-diagonal -- the pixels and edge differences in registers are then still exact.  Free on
     // smooth image regions; never taken on noisy content (LABNOTES.md 4.2c).
-    if (g == 0 || __builtin_amdgcn_ballot_w64(chg != 0) != 0) {
+    if (g == 0 || (DIAG ? __builtin_amdgcn_ballot_w64(chg != 0) != 0 : chg_any != 0)) {
       chg = 0;
+      chg_any = 0;
       uint32_t ws[64];
       // 64 sign-extending 16-bit LDS reads (ds_read_i16) instead of 16 ds_read2_b32 + 48 VALU sign extensions: the kernel
       // is bound by VALU issue slots, the LDS pipe idles (refresh 940 -> 885 VALU instructions; profiles/r05g_lds16)
-      lds_read_block_i16(col, ws);
+      if constexpr (DIAG) lds_read_block_i16(col, ws); else lds_read_block_i16_1(col, ws);
 #if QS_STASH
       // Column-restricted pass 1.  Pass 1 transforms block COLUMNS, and column x only holds coefficients of the
       // anti-diagonals 7 - x .. 14 - x: column 0 is untouched until anti-diagonal 7, column 1 until 6; column 7 is final
@@ -177,11 +208,13 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       // Columns 0 / 1 are stored by refresh 0, which always runs; columns 7 / 6 by the first refresh that RUNS at
       // g >= 8 / g >= 9 (the wave-uniform refresh skip may sit some out): stash_hi remembers that it happened.
       {
-        uint32_t* stash = stash_all[wave] + lane;
+        // The luma walk has LDS for slot 0 alone (columns 0 and 7: 12 of the 22 saved transforms) -- the other eight
+        // dwords per lane hold what its resident differences pushed out of the register file (QS_X_*).
+        uint32_t* stash = DIAG ? stash_all[wave] + lane : xcol + QS_X_STASH * 64;
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
           uint32_t c[8];
-          const bool low = x <= 1, high = x >= 6;
+          const bool low = x <= (DIAG ? 1 : 0), high = x >= (DIAG ? 6 : 7);
           const int slot = (x == 0 || x == 7) ? 0 : 1;
           bool reuse = false, store = false;
           if (low) { reuse = g >= 1 && g <= 7 - x; store = g == 0; }
@@ -212,6 +245,40 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
 #else
       idct_pass1(ws);
 #endif
+      if constexpr (!DIAG) {
+        // Pass 2 row by row; behind row y its 7 horizontal differences, the 8 vertical ones against row y - 1 (eight
+        // floats kept for one row) and the row's edge differences.  Operand order is the reference's: px[p] - px[p + 1],
+        // px[p] - px[p + 8], own pixel minus neighbour.  The neighbour pixels come from LDS where they are needed.
+        float prev[8];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+          uint32_t row[8]; float o[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) row[j] = ws[y * 8 + j];
+          idct_pass2_row_f(row, o);
+#pragma unroll
+          for (int x = 0; x < 7; ++x) dh[y * 7 + x] = o[x] - o[x + 1];
+          if (y > 0) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) dv[(y - 1) * 8 + x] = prev[x] - o[x];
+          }
+          if (y == 0 || y == 7) {
+            const uint32_t e0 = xcol[(QS_X_EDGE + (y ? 2 : 0)) * 64], e1 = xcol[(QS_X_EDGE + (y ? 3 : 1)) * 64];
+#pragma unroll
+            for (int x = 0; x < 8; ++x) bd[(y ? 8 : 0) + x] = o[x] - pix_from_byte(x < 4 ? e0 : e1, x & 3);
+          }
+          {
+            const uint32_t el = xcol[(QS_X_EDGE + 4 + (y >> 2)) * 64], er = xcol[(QS_X_EDGE + 6 + (y >> 2)) * 64];
+            bd[16 + y] = o[0] - pix_from_byte(el, y & 3);
+            bd[24 + y] = o[7] - pix_from_byte(er, y & 3);
+          }
+#pragma unroll
+          for (int x = 0; x < 8; ++x) prev[x] = o[x];
+          // rows stay in order: interleaved by the scheduler, their butterflies' temporaries pile up on top of the
+          // 144 resident values and spill
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
 #pragma unroll
       for (int y = 0; y < 8; ++y) {
         uint32_t row[8]; float o[8];
@@ -235,6 +302,7 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       }
 #pragma unroll
       for (int t = 0; t < NH; ++t) hd[t] = px[(t / 7) * 8 + t % 7] - px[(t / 7) * 8 + t % 7 + 1];
+      }   // (DIAG)
     }
     // anti-diagonal g (walking down from k = 63) holds min(g + 1, 15 - g) coefficients
     const int len = min(g + 1, 15 - g);
@@ -243,9 +311,11 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
     for (int k = kfirst; k >= klast; --k) {
       // Keep the interior pixel differences inside the coefficient loop: otherwise the compiler hoists all
       // 112/210 of them out of the k-loop (they only change per anti-diagonal) and pays for it in VGPRs /
-      // scratch spills.
+      // scratch spills.  (The luma walk has no pixels: its differences are resident by design.)
+      if constexpr (DIAG) {
 #pragma unroll
-      for (int p = 0; p < 64; ++p) asm volatile("" : "+v"(px[p]));
+        for (int p = 0; p < 64; ++p) asm volatile("" : "+v"(px[p]));
+      }
       // Everything about coefficient k that is a function of k alone comes ready-made in the record's fourth dword
       // (QsConsts::rec, qs_tables.cpp): which sections run and in which zero-skipping form, where the coefficient lives
       // in this lane's LDS column, whether the next coefficient's first chunk is its border chunk.  Round 4 computed
@@ -279,8 +349,14 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       if (__builtin_expect(md & QS_REC_Q1, 0)) {
         {   // (unconditional: without the rebalance step nobody reads the sums)
           const int c0 = *reinterpret_cast<lds_i16*>(reinterpret_cast<char*>(col) + lds_off);
-          reb_m0 += (long long)(c0 * c0);
-          reb_m1 += (long long)(c0 * c0);
+          if constexpr (DIAG) {
+            reb_m0 += (long long)(c0 * c0);
+            reb_m1 += (long long)(c0 * c0);
+          } else {
+            qs_lds_u64* const xreb = qs_xreb(col, lds, 0);
+            qs_lds_add64(xreb, (long long)(c0 * c0));
+            qs_lds_add64(xreb + 64, (long long)(c0 * c0));
+          }
         }
         asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx4 %1, %4, %5\n\ts_waitcnt lgkmcnt(0)"
                      : "=&s"(WA), "=&s"(RECN)
@@ -307,7 +383,9 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
           QS_TERM(px[(Y) * 8 + x], px[(Y) * 8 + x + 9], W[x]) \
           QS_TERM(px[(Y) * 8 + x + 1], px[(Y) * 8 + x + 8], W[8 + x]) } }
 #define QS_EDGE16(W, J0) { \
-        _Pragma("unroll") for (int j = 0; j < 16; ++j) QS_TERM_D(bd[(J0) + j], W[j]) }
+        _Pragma("unroll") for (int j = 0; j < 16; ++j) { \
+          if constexpr (DIAG) QS_TERM_D(bd[(J0) + j], W[j]) \
+          else QS_TERM_D_ASM(bd[(J0) + j], W[j]) } }   /* (luma: opaque, two temporaries -- scheduled freely the 16 terms' products pile up) */
       // (every term of a specialised section is an opaque 9-instruction asm block: the three copies must not share
       //  subexpressions, or hipcc hoists ~100 pixel differences above the branch and spills them)
 #define QS_HOISTED_TERM(T, WT) else if ((T) < NH) QS_TERM_D_ASM(hd[(T) % NH], WT)
@@ -315,12 +393,14 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
         _Pragma("unroll") for (int yy = 0; yy < 2; ++yy) \
         _Pragma("unroll") for (int x = 0; x < 7; ++x) { \
           if (((MODE) == 2 && (x & 1)) || ((MODE) == 1 && x == 3)) {} \
+          else if constexpr (!DIAG) QS_TERM_D_ASM(dh[((Y0) + yy) * 7 + x], W[yy * 8 + x]) \
           QS_HOISTED_TERM(((Y0) + yy) * 7 + x, W[yy * 8 + x]) \
           else QS_TERM_ASM(px[((Y0) + yy) * 8 + x], px[((Y0) + yy) * 8 + x + 1], W[yy * 8 + x]) } }
 #define QS_ROWS_V_M(W, Y0, NY, MODE) { \
         _Pragma("unroll") for (int yy = 0; yy < (NY); ++yy) \
         _Pragma("unroll") for (int x = 0; x < 8; ++x) { \
           if (((MODE) == 2 && (((Y0) + yy) & 1)) || ((MODE) == 1 && (Y0) + yy == 3)) {} \
+          else if constexpr (!DIAG) QS_TERM_D_ASM(dv[((Y0) + yy) * 8 + x], W[yy * 8 + x]) \
           else QS_TERM_ASM(px[((Y0) + yy) * 8 + x], px[((Y0) + yy) * 8 + x + 8], W[yy * 8 + x]) } }
 
       // "Landed" pipeline: every chunk step is  ISSUE(next chunk) ; 14-16 terms on the current one ;
@@ -428,11 +508,30 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
         interval(c0, qk, x1k, x2k, orig, lo, hi);
         int v = (int)((uint32_t)c0 - (uint32_t)r);  // wraps like the x86 build
         v = min(max(v, lo), hi);
-        *cptr = (lds_i16)v;
-        chg |= (uint32_t)(v ^ c0);
-        if (rebalance) {                            // wave-uniform
-          reb_m0 += (long long)(v * orig);
-          reb_m1 += (long long)(orig * orig);
+        if constexpr (DIAG) {
+          *cptr = (lds_i16)v;
+          chg |= (uint32_t)(v ^ c0);
+          if (rebalance) {                            // wave-uniform
+            reb_m0 += (long long)(v * orig);
+            reb_m1 += (long long)(orig * orig);
+          }
+        } else {
+          // The reference updates only `if (range)` (:1551).  Storing the clamped c0 back for r == 0 is the same thing
+          // as long as c0 lies inside its own interval -- true for every coefficient a job can hold, but the reciprocal
+          // tables divide exactly for |c| < 0x4000 only (:2527): beyond that the interval may miss c0 by one.  Such
+          // coefficients also break what lets the rebalance sums be collected here -- that the stored value has the
+          // `orig` of the value it replaced (inexact reciprocal, int16 wrap of the store).  A wave that was staged
+          // with a coefficient outside [-0x2000, 0x2000) (big_wave; nothing below that can reach 0x4000) therefore
+          // follows the reference to the letter, here and in the rebalance epilogue.
+          // (a real, wave-uniform branch: the empty asm keeps hipcc from turning it into two selects on every wave's path)
+          if (__builtin_expect(big_wave, 0)) { asm volatile("" : "+v"(v)); v = r ? v : c0; }
+          *cptr = (lds_i16)v;
+          chg_any |= __builtin_amdgcn_ballot_w64(v != c0);   // v_cmp + s_or_b64: no register per lane
+          if (rebalance) {                            // wave-uniform; integer sums, exact in any order, added in LDS
+            qs_lds_u64* const xreb = qs_xreb(col, lds, 0);
+            qs_lds_add64(xreb, (long long)(v * orig));
+            qs_lds_add64(xreb + 64, (long long)(orig * orig));
+          }
         }
       }
       REC = RECN;   // landed by the coefficient's last step
@@ -445,7 +544,22 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
   // ---- rebalance (reference :1823-1848): scale AC energy back towards the
   // quantised original, inside each coefficient's interval.
   if (rebalance) {
-    const long long m0 = reb_m0, m1 = reb_m1;
+    long long m0 = DIAG ? reb_m0 : (long long)*qs_xreb(col, lds, 0), m1 = DIAG ? reb_m1 : (long long)*qs_xreb(col, lds, 1);
+    // A wave staged with a coefficient outside [-0x2000, 0x2000) (big_wave: never in a job) follows the reference to
+    // the letter: the sums from the FINAL coefficients (:1826-1831), and below each `orig` as the JCOEF the reference
+    // keeps it in (:1829: int16 wrap).  Everywhere else both are what the walk collected.
+    const bool big = big_wave;
+    if (big) {
+      m0 = 0; m1 = 0;
+#pragma unroll 1
+      for (int n = 1; n < 64; ++n) {
+        const int c = lds_coef(col, n);
+        int orig, lo, hi;
+        interval(c, cst->qn[n], cst->x1n[n], cst->x2n[n], orig, lo, hi);
+        m0 += (long long)(c * orig);
+        m1 += (long long)(orig * orig);
+      }
+    }
     if (m1 > m0) {
       const int mul = (int)(((m1 << 13) + (m0 >> 1)) / m0);
 #pragma unroll 9
@@ -453,6 +567,11 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
         const int c = lds_coef(col, n);
         int orig, lo, hi;
         interval(c, cst->qn[n], cst->x1n[n], cst->x2n[n], orig, lo, hi);
+        if (big) {
+          const int div = cst->qn[n], a = (int16_t)orig;
+          hi = a + (a < 0 ? div >> 1 : (div - 1) >> 1);
+          lo = a - (a > 0 ? div >> 1 : (div - 1) >> 1);
+        }
         int v = (c * mul + 0x1000) >> 13;
         v = min(max(v, lo), hi);
         lds_set_coef(col, n, v);
@@ -466,7 +585,8 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
     // recompute the per-lane store addresses from an opaque copy of the lane
     // id, so that the 8 load addresses of the prologue do not stay live (and
     // get spilled) across the whole kernel
-    int lane2 = lane;
+    // (luma walk: the lane id comes from mbcnt, so that not even the id itself stays live)
+    int lane2 = DIAG ? lane : (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(lane2));
     const int lane = lane2;
     const int m0 = (lane & 7) * 4;
@@ -504,9 +624,11 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
 #endif
   if (plane_next) {                                         // wave-uniform
     uint32_t ws[64];
-    lds_read_block_i16(col, ws);
-    if (base + lane < nblk)
-      idct_ws_to_plane(ws, plane_next, wblk2, hblk2, pitch2, rep & QS_PLANE_REP_TOP, rep & QS_PLANE_REP_BOT, base + lane);
+    if constexpr (DIAG) lds_read_block_i16(col, ws); else lds_read_block_i16_1(col, ws);
+    int lane3 = DIAG ? lane : (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // (as in the write-back)
+    if constexpr (!DIAG) asm volatile("" : "+v"(lane3));
+    if (base + lane3 < nblk)
+      idct_ws_to_plane(ws, plane_next, wblk2, hblk2, pitch2, rep & QS_PLANE_REP_TOP, rep & QS_PLANE_REP_BOT, base + lane3);
   }
 }
 
