@@ -442,6 +442,36 @@ int qs_hip_read_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const q
 		void *d_workspace, size_t bytes, void *stream);
 int qs_hip_read_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_scan, const uint64_t *scan_bytes,
 		int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
+/* The split route of the scan reader: the same jobs, options, arguments and output as the three calls above, parallel
+ * inside an interval as well, so a file without DRI is read by many lanes and there is no interval cap (the other
+ * refusals are the same).  Every restart interval -- the whole scan when the file has none -- is cut into segments of
+ * QS_HIP_READ_SPLIT_BYTES stuffed bytes and one lane decodes one segment.  The first segment of an interval starts in
+ * the known state; every other one starts from a guess and takes, in each of QS_HIP_READ_SPLIT_ROUNDS further launches,
+ * the state its left neighbour reached in the launch before (Huffman streams synchronise themselves).  Then every link
+ * is checked: only when each segment was decoded from exactly the state its neighbour ended in are the values
+ * written, and the DC predictions rebuilt from the differences by a prefix sum (mod 2^16: libjpeg's int prediction
+ * stored as JCOEF).  For every input the calls above read with status 0 the arrays and the status are the same.
+ * d_status[i]: 0..3 as above (0 and 1 for exactly the inputs that get them there; which of 2 and 3 a damaged interval
+ * gets may differ), and 4: the segments did not synchronise in QS_HIP_READ_SPLIT_ROUNDS rounds -- the arrays are
+ * unspecified, every store lies inside them, other jobs are unaffected; the three calls above read such a file.  No
+ * valid file of the corpus the constant was measured on comes near it.
+ * per_job[i].max_segments: the segments the workspace is sized for, those of the longest scan the geometry can have.
+ * The run ENQUEUES 4 + 7 + QS_HIP_READ_SPLIT_ROUNDS + 1 kernel launches per QS_HIP_READ_CHUNK jobs on `stream`, a fixed
+ * number: no allocation, no synchronisation, no copy (graph-capturable, a linear graph).  The workspace is not the one
+ * of the calls above. */
+#define QS_HIP_READ_SPLIT_BYTES 256
+#define QS_HIP_READ_SPLIT_ROUNDS 17
+typedef struct {
+	int32_t blocks_in_mcu, mcus, intervals;
+	int64_t blocks_per_interval;
+	int64_t max_segments;
+} qs_hip_read_split_info;
+int qs_hip_read_split_device_batch_info(qs_hip_job *const *jobs, int njobs, const qs_hip_read_opts *const *opts,
+		qs_hip_read_split_info *per_job, size_t *workspace_bytes);
+int qs_hip_read_split_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const qs_hip_read_opts *const *opts,
+		void *d_workspace, size_t bytes, void *stream);
+int qs_hip_read_split_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_scan,
+		const uint64_t *scan_bytes, int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
 /* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
  * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT.  Counts
  * that are all zero: bits all 0, no symbols, success.  A code length above 32: QS_HIP_EINVAL.  (csrc/qs_huff.h: the
@@ -531,7 +561,8 @@ const char *qs_hip_last_error(void);
  * qs_hip_plane_ref back to its 48-byte form, second planes through qs_hip_smooth_planes_next; 6: round 6 --
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
  * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
- * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress).  A caller built against
+ * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress,
+ * the split route of the scan reader qs_hip_read_split_device_batch and its two calls).  A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

@@ -62,5 +62,32 @@ def main(path):
     return 1 if bad else 0
 
 
+# the kernels of the scan reader's split route (qs_kernels_read_split.hip): nothing in scratch -- a lane's bit reader,
+# its state and the block it writes to live in registers, the code tables in LDS
+SPLIT_READ_KERNELS = ("qrs_map", "qrs_decode", "qrs_count", "qrs_tile_scan", "qrs_write", "qrs_dc_tiles", "qrs_dc_write")
+
+
+def main_no_scratch(prefix, path):
+    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS that starts with the prefix is there and
+    has no scratch"""
+    want = [k for k in SPLIT_READ_KERNELS if k.startswith(prefix)]
+    recs = kernel_records(open(path).read())
+    bad = 0
+    for k in want:
+        hits = {n: r for n, r in recs.items() if re.search(rf"\d+{k}E", n)}
+        if len(hits) != 1 or "private_segment_fixed_size" not in next(iter(hits.values())):
+            print(f"check_kernel_budget: ERROR: expected the metadata of one kernel {k} in {path}, found {sorted(hits)}", file=sys.stderr)
+            bad += 1
+            continue
+        (n, r), = hits.items()
+        scratch = r["private_segment_fixed_size"]
+        print(f"check_kernel_budget: {n}: {r.get('vgpr_count')} VGPRs, {scratch} B scratch, {r.get('group_segment_fixed_size')} B LDS"
+              + (" -- ERROR: scratch" if scratch else ""), file=sys.stderr if scratch else sys.stdout)
+        bad += bool(scratch)
+    return 1 if bad or not want else 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--no-scratch":
+        sys.exit(main_no_scratch(sys.argv[2], sys.argv[3]))
     sys.exit(main(sys.argv[1]))

@@ -264,11 +264,17 @@ __global__ void __launch_bounds__(QS_RD_DWG) qr_decode(QrArgs a) {
 
 }  // namespace
 
-// what one run enqueues for a chunk of jobs: zwgs / mwgs / dwgs = workgroups of the init, marker and decode launches
-void qs_launch_read(const QrArgs& a, int zwgs, int mwgs, int dwgs, hipStream_t s) {
+// the init and marker launches of a chunk of jobs: what both routes decode behind (the split route:
+// qs_kernels_read_split.hip).  zwgs / mwgs = workgroups of the init and marker launches
+void qs_launch_read_markers(const QrArgs& a, int zwgs, int mwgs, hipStream_t s) {
   hipLaunchKernelGGL(qr_init, dim3(zwgs), dim3(QS_RD_WG), 0, s, a);
   if (mwgs > 0) hipLaunchKernelGGL(qr_mark_count, dim3(mwgs), dim3(QS_RD_WG), 0, s, a);
   hipLaunchKernelGGL(qr_mark_scan, dim3(a.n), dim3(QS_RD_WG), 0, s, a);
   if (mwgs > 0) hipLaunchKernelGGL(qr_mark_place, dim3(mwgs), dim3(QS_RD_WG), 0, s, a);
+}
+
+// what one run enqueues for a chunk of jobs: dwgs = workgroups of the decode launch
+void qs_launch_read(const QrArgs& a, int zwgs, int mwgs, int dwgs, hipStream_t s) {
+  qs_launch_read_markers(a, zwgs, mwgs, s);
   hipLaunchKernelGGL(qr_decode, dim3(dwgs), dim3(QS_RD_DWG), 0, s, a);
 }

@@ -142,6 +142,14 @@ class ReadInfo(C.Structure):
                 ("blocks_per_interval", C.c_int64)]
 
 
+class ReadSplitInfo(C.Structure):
+    """qs_hip_read_split_info: one job of the scan reader's split route (qs_hip_read_split_device_batch_info)"""
+    _fields_ = ReadInfo._fields_ + [("max_segments", C.c_int64)]
+
+
+READ_SPLIT_BYTES = 256           # QS_HIP_READ_SPLIT_BYTES: stuffed bytes of a restart interval one lane decodes
+READ_SPLIT_ROUNDS = 17           # QS_HIP_READ_SPLIT_ROUNDS: synchronisation launches of the split route
+
 MAX_PLANES = 56
 COMPRESS_CHUNK = 44              # QS_HIP_COMPRESS_CHUNK: jobs per launch of the device compress
 DOWNSAMPLE_BOX = 0               # QS_HIP_DOWNSAMPLE_BOX: do_fancy_downsampling = FALSE
@@ -208,6 +216,12 @@ ABI = {
                                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_read_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_read_split_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
+                                                       C.POINTER(ReadSplitInfo), C.POINTER(C.c_size_t)]),
+    "qs_hip_read_split_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
+                                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_read_split_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_compress_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.POINTER(CompressInfo),
                                                      C.POINTER(C.c_size_t)]),
     "qs_hip_compress_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
@@ -739,28 +753,32 @@ class HipQS:
             raise ValueError("one ReadOpts per job")
         return (C.POINTER(ReadOpts) * max(1, n))(*[None if o is None else C.pointer(o) for o in opts])
 
-    def read_batch_info(self, jobs, opts):
+    def read_batch_info(self, jobs, opts, split=False):
         """qs_hip_read_device_batch_info (no device needed) -> (list of dict(blocks_in_mcu, mcus, intervals,
-        blocks_per_interval), the batch's workspace bytes)"""
-        per = (ReadInfo * max(1, len(jobs)))()
+        blocks_per_interval), the batch's workspace bytes).  split: qs_hip_read_split_device_batch_info, the split
+        route (no interval cap; the dicts also hold max_segments); its workspace is another one"""
+        info = ReadSplitInfo if split else ReadInfo
+        call = self.lib.qs_hip_read_split_device_batch_info if split else self.lib.qs_hip_read_device_batch_info
+        per = (info * max(1, len(jobs)))()
         total = C.c_size_t(0)
-        self._check(self.lib.qs_hip_read_device_batch_info(self._job_ptrs(jobs), len(jobs), self._read_opt_ptrs(opts, len(jobs)),
-                                                           per, C.byref(total)))
-        return [{f: int(getattr(per[i], f)) for f, _ in ReadInfo._fields_} for i in range(len(jobs))], int(total.value)
+        self._check(call(self._job_ptrs(jobs), len(jobs), self._read_opt_ptrs(opts, len(jobs)), per, C.byref(total)))
+        return [{f: int(getattr(per[i], f)) for f, _ in info._fields_} for i in range(len(jobs))], int(total.value)
 
-    def read_batch_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None) -> None:
-        """qs_hip_read_device_batch_prepare: geometry and derived code tables into the workspace (synchronises `stream`;
-        not inside a capture)"""
-        self._check(self.lib.qs_hip_read_device_batch_prepare(self._job_ptrs(jobs), len(jobs),
-                                                              self._read_opt_ptrs(opts, len(jobs)), d_workspace, nbytes, stream))
+    def read_batch_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None, split=False) -> None:
+        """qs_hip_read_device_batch_prepare (split: qs_hip_read_split_device_batch_prepare): geometry and derived code
+        tables into the workspace (synchronises `stream`; not inside a capture)"""
+        call = self.lib.qs_hip_read_split_device_batch_prepare if split else self.lib.qs_hip_read_device_batch_prepare
+        self._check(call(self._job_ptrs(jobs), len(jobs), self._read_opt_ptrs(opts, len(jobs)), d_workspace, nbytes, stream))
 
-    def read_batch(self, jobs, d_scan, scan_bytes, d_status: int, d_workspace: int, nbytes: int, stream=None) -> None:
-        """qs_hip_read_device_batch: enqueue the scan reader of every job; d_scan[i] = device address of job i's bytes
-        behind the SOS header, scan_bytes[i] = how many may be read, d_status = device int32[njobs]"""
+    def read_batch(self, jobs, d_scan, scan_bytes, d_status: int, d_workspace: int, nbytes: int, stream=None,
+                   split=False) -> None:
+        """qs_hip_read_device_batch (split: qs_hip_read_split_device_batch): enqueue the scan reader of every job;
+        d_scan[i] = device address of job i's bytes behind the SOS header, scan_bytes[i] = how many may be read,
+        d_status = device int32[njobs]"""
         scans = (C.c_void_p * max(1, len(d_scan)))(*d_scan)
         lens = (C.c_uint64 * max(1, len(scan_bytes)))(*[int(v) for v in scan_bytes])
-        self._check(self.lib.qs_hip_read_device_batch(self._job_ptrs(jobs), len(jobs), scans, lens, d_status, d_workspace,
-                                                      nbytes, stream))
+        call = self.lib.qs_hip_read_split_device_batch if split else self.lib.qs_hip_read_device_batch
+        self._check(call(self._job_ptrs(jobs), len(jobs), scans, lens, d_status, d_workspace, nbytes, stream))
 
     def huff_optimal(self, freq):
         """qs_hip_huff_optimal (host only): symbol counts (256 or 257) -> (bits[17], huffval) as libjpeg's

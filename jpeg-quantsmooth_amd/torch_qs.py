@@ -780,7 +780,7 @@ def _huffman_of(p):
     return dict(dc={t: p["dc"][t] for t in used}, ac={t: p["ac"][t] for t in used})
 
 
-def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=None) -> dict:
+def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=None, split=False) -> dict:
     """Read the scans of JPEG files into device coefficient tensors on the current stream: what libjpeg 9's
     jpeg_read_coefficients leaves in its arrays.  One lane reads one restart interval, so files with a small restart
     interval (this package's encode(restart_interval=...), jpegtran -restart) are the workload; a file without DRI is
@@ -798,11 +798,19 @@ def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=N
     -- coefs, quants, hsamp, vsamp, colorspace, image_size -- with huffman (the file's tables in the form
     encode(huffman=...) takes, or None when a component's Td != Ta or a table id above 1 is used), restart_interval and
     status (a view of one element of `status`, the int32 tensor of the batch: 0 ok, 1 RSTn markers that do not match the
-    interval, 2 an interval with too few or too many bytes, 3 bits without a code; the arrays are then unspecified)."""
-    return _read_batch(datas, outs, workspace, device, "read_batch")
+    interval, 2 an interval with too few or too many bytes, 3 bits without a code; the arrays are then unspecified).
+
+    split=True takes the split route (qs_hip_read_split_device_batch): every restart interval -- the whole scan of a file
+    without DRI -- is cut into segments of hipqs.READ_SPLIT_BYTES bytes, one lane decodes one segment, the segments find
+    their entry states by self-synchronisation in hipqs.READ_SPLIT_ROUNDS launches and the DC predictions are rebuilt
+    by a prefix sum.  There is no interval cap; the images and the capture rules are the same, the workspace is one of
+    its own (a workspace prepared for one route is prepared again for the other), and status may also be 4: the
+    segments did not synchronise, read the file with split=False.  The default stays False until the crossover
+    between the routes is measured."""
+    return _read_batch(datas, outs, workspace, device, "read_batch", split)
 
 
-def _read_batch(datas, outs, workspace, device, who):
+def _read_batch(datas, outs, workspace, device, who, split=False):
     import torch
     if not isinstance(datas, (list, tuple)) or not datas:
         raise ValueError(f"{who}: datas must be a non-empty list of files")
@@ -851,8 +859,9 @@ def _read_batch(datas, outs, workspace, device, who):
         images.append(dict(coefs=coefs, quants=[q.copy() for q in p["quants"]], hsamp=list(p["hsamp"]),
                            vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), huffman=_huffman_of(p),
                            restart_interval=p["restart_interval"]))
-    _per, total = hip.read_batch_info(jobs, opts)
-    key = ("read",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o) for o in opts)
+    split = bool(split)
+    _per, total = hip.read_batch_info(jobs, opts, split=split)
+    key = ("read-split" if split else "read",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o) for o in opts)
     if workspace is None:
         workspace = Workspace()
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -862,22 +871,22 @@ def _read_batch(datas, outs, workspace, device, who):
                                f"geometry and tables (workspace=...): preparing one synchronises")
         if workspace.nbytes < total or workspace.buf.device != dev:
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.read_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream)
+        hip.read_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream, split=split)
         workspace.key = key
     workspace.headers = headers
     status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
     hip.read_batch(jobs, [b.data_ptr() + p["scan_offset"] for b, p in zip(bufs, headers)],
                    [b.numel() - p["scan_offset"] for b, p in zip(bufs, headers)], status.data_ptr(), workspace.buf.data_ptr(),
-                   workspace.nbytes, stream)
+                   workspace.nbytes, stream, split=split)
     for i, im in enumerate(images):
         im["status"] = status[i:i + 1]
     return dict(images=images, status=status, workspace=workspace)
 
 
-def read(data, *, out=None, workspace: Workspace | None = None, device=None) -> dict:
+def read(data, *, out=None, workspace: Workspace | None = None, device=None, split=False) -> dict:
     """read_batch on one file -> its image dict (coefs, quants, hsamp, vsamp, colorspace, image_size, huffman,
-    restart_interval, status) with the workspace used under `workspace`"""
-    r = _read_batch([data], None if out is None else [out], workspace, device, "read")
+    restart_interval, status) with the workspace used under `workspace`; split as read_batch takes it"""
+    r = _read_batch([data], None if out is None else [out], workspace, device, "read", split)
     return dict(r["images"][0], workspace=r["workspace"])
 
 

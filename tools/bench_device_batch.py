@@ -34,6 +34,10 @@ unless the first file of each case is libjpeg's optimized file.
 host route it replaces -- libjpeg 9's jpeg_read_coefficients on one core (tests/libjpeg9_decode.c read: its time
 includes writing the arrays to a file) plus the pinned upload of the coefficient arrays.  Parallelism is the number of
 restart intervals: the lanes of each case are reported.  Exits non-zero unless the arrays are the ones encoded.
+--read --split times the split route (read_batch(split=True): one lane per 256 bytes of an interval) and needs no
+restart option; where the interval route accepts the same file its time on it is reported beside it
+(interval_route_read_ms, null where it refuses the file), and both must give the arrays encoded.  --no-host leaves
+libjpeg's read out.
 
 --compress times the device compress of pixels (torch_qs.compress_batch, one launch per batch, quality 50 tables) on the
 same three cases, as time per call and GB/s of pixels read plus coefficients written, next to the decode of the arrays
@@ -45,7 +49,8 @@ route and the comparison, tests/libjpeg9_compress_fancy.c) and reports whether e
 mode's: the gray case must.
 
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode | --read | --compress] [--restart N | --restart-rows N]
+                                       [--decode | --encode | --read [--split] [--no-host] | --compress]
+                                       [--restart N | --restart-rows N]
                                        [--downsampling box|dct]"""
 import argparse
 import json
@@ -75,6 +80,9 @@ def main():
     ap.add_argument("--optimize-files", action="store_true",
                     help="--encode: time the whole-file run with optimized tables next to the histogram run plus the plain run")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
+    ap.add_argument("--split", action="store_true",
+                    help="--read: the split route (segments of an interval in parallel); works without a restart option")
+    ap.add_argument("--no-host", action="store_true", help="--read: do not time libjpeg's read of the file")
     ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
     ap.add_argument("--downsampling", choices=["box", "dct"], default="box",
                     help="--compress: box (do_fancy_downsampling = FALSE) or dct (libjpeg 9's default)")
@@ -441,9 +449,10 @@ def bench_read(a):
     import jpegqs_pkg
     sys.path.insert(0, str(ROOT / "tests"))
     from decode_oracle import LibJpeg9, synth_image
-    if not (a.restart or a.restart_rows):
-        raise SystemExit("bench_device_batch --read: give --restart N or --restart-rows N (one lane reads one interval)")
-    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows)
+    if not (a.restart or a.restart_rows or a.split):
+        raise SystemExit("bench_device_batch --read: give --restart N or --restart-rows N (one lane reads one interval), "
+                         "or --split")
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows) if a.restart or a.restart_rows else {}
     pkg = jpegqs_pkg.load()
     torch_qs = pkg.torch_qs
     if not torch.cuda.is_available():
@@ -455,6 +464,8 @@ def bench_read(a):
              ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
              (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
     out = dict(tool="bench_device_batch", leg="read", device=torch.cuda.get_device_name(dev), restart=rst, results=[])
+    if a.split:
+        out.update(split=True, split_bytes=pkg.hipqs.READ_SPLIT_BYTES, split_rounds=pkg.hipqs.READ_SPLIT_ROUNDS)
     for name, ims in cases:
         im = ims[0]
         coefs = [torch.from_numpy(c).to(dev) for c in im["coefs"]]
@@ -463,23 +474,24 @@ def bench_read(a):
         pinned = [torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory() for _ in ims]
         on_dev = [p.to(dev) for p in pinned]
         ws = torch_qs.Workspace()
-        r = torch_qs.read_batch(on_dev, workspace=ws)
+        r = torch_qs.read_batch(on_dev, workspace=ws, split=a.split)
         outs = [x["coefs"] for x in r["images"]]
         status = r["status"].cpu().tolist()
         identical = status == [0] * len(ims) and all(torch.equal(g, c) for o in outs for g, c in zip(o, coefs))
         header = pkg.jpeg_file.parse(data, header_only=True)
-        per, _ = pkg.HipQS().read_batch_info(
-            [pkg.HipQS.device_job([1] * len(coefs), [tuple(c.shape[:2]) for c in coefs], [None] * len(coefs), hsamp=im["hsamp"],
-                                  vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"])],
-            [pkg.HipQS.read_opts(header["dc"], header["ac"], header["dc_tbl"], header["ac_tbl"], header["restart_interval"])])
+        info_job = [pkg.HipQS.device_job([1] * len(coefs), [tuple(c.shape[:2]) for c in coefs], [None] * len(coefs),
+                                         hsamp=im["hsamp"], vsamp=im["vsamp"], colorspace=im["colorspace"],
+                                         image_size=im["image_size"])]
+        info_opts = [pkg.HipQS.read_opts(header["dc"], header["ac"], header["dc_tbl"], header["ac_tbl"], header["restart_interval"])]
+        per, _ = pkg.HipQS().read_batch_info(info_job, info_opts, split=a.split)
 
         def device_route():
             up = [p.to(dev, non_blocking=True) for p in pinned]
-            torch_qs.read_batch(up, outs=outs, workspace=ws)
+            torch_qs.read_batch(up, outs=outs, workspace=ws, split=a.split)
             torch.cuda.synchronize()
 
         def kernels_only():
-            torch_qs.read_batch(on_dev, outs=outs, workspace=ws)
+            torch_qs.read_batch(on_dev, outs=outs, workspace=ws, split=a.split)
             torch.cuda.synchronize()
 
         host_pinned = [[torch.from_numpy(c).pin_memory() for c in im["coefs"]] for _ in ims]
@@ -509,6 +521,28 @@ def bench_read(a):
                    restart_interval=header["restart_interval"], lanes=per[0]["intervals"] * len(ims),
                    blocks_per_lane=per[0]["blocks_per_interval"], device_upload_plus_read_ms=dev_ms, device_windows=dev_all,
                    device_read_ms=k_ms, device_read_windows=k_all, host_coef_upload_ms=up_ms, identical=bool(identical))
+        if a.split:                                                     # the interval route on the same file, where it takes it
+            row.update(segments_at_most=per[0]["max_segments"] * len(ims), interval_route_read_ms=None)
+            try:
+                pkg.HipQS().read_batch_info(info_job, info_opts)
+            except pkg.hipqs.QsHipError:
+                pass                                                    # (over the interval cap)
+            else:
+                ws_old = torch_qs.Workspace()
+                outs_old = [[torch.empty_like(c) for c in coefs] for _ in ims]
+
+                def interval_route():
+                    r = torch_qs.read_batch(on_dev, outs=outs_old, workspace=ws_old)
+                    torch.cuda.synchronize()
+                    return r
+                ro = interval_route()
+                same = ro["status"].cpu().tolist() == [0] * len(ims) and all(torch.equal(g, c) for o in outs_old for g, c in zip(o, coefs))
+                row["identical"] = bool(identical and same)
+                row["interval_route_read_ms"], row["interval_route_windows"] = med(interval_route, 1 if k_ms > 50 else 3)
+                del ws_old, outs_old
+        if a.no_host:
+            out["results"].append(row)
+            continue
         with tempfile.TemporaryDirectory() as td:
             lj9 = LibJpeg9(Path(td))
             f = Path(td) / "in.jpg"
