@@ -270,6 +270,42 @@ int qs_hip_decode_device_batch_prepare(qs_hip_job *const *jobs, int njobs, void 
 		void *stream);
 int qs_hip_decode_device_batch(qs_hip_job *const *jobs, int njobs, const int32_t *d_stop, uint8_t *const *d_out,
 		const size_t *out_pitch, void *d_workspace, size_t bytes, void *stream);
+/* The chroma upsampling, chosen per job through info / prepare with opts[i] for job i:
+ *   QS_HIP_UPSAMPLE_DCT       libjpeg 7..9: 2x-subsampled chroma is upsampled by DCT scaling (jpeg_idct_16x16, _16x8,
+ *                             _8x16), as described above.  What info / prepare without opts do.
+ *   QS_HIP_UPSAMPLE_TRIANGLE  libjpeg-turbo and libjpeg 6b (what Pillow, OpenCV and browsers decode with): the 8x8
+ *                             jpeg_idct_islow at chroma resolution, then jdsample.c's "fancy" triangle filters.  With c a
+ *                             chroma plane of Wc x Hc = ceil(width / hs) x ceil(height / vs) samples, indices clamped to
+ *                             0 .. Wc - 1 and 0 .. Hc - 1 (never to the block grid):
+ *       luma 2x1   out[y][x] = (3 c[y][x>>1] + c[y][x even ? (x>>1) - 1 : (x>>1) + 1] + (x even ? 1 : 2)) >> 2
+ *       luma 1x2   out[y][x] = (3 c[y>>1][x] + c[y even ? (y>>1) - 1 : (y>>1) + 1][x] + (y even ? 1 : 2)) >> 2
+ *       luma 2x2   s[y][i]   = 3 c[y>>1][i] + c[y even ? (y>>1) - 1 : (y>>1) + 1][i]
+ *                  out[y][x] = (3 s[y][x>>1] + s[y][x even ? (x>>1) - 1 : (x>>1) + 1] + (x even ? 8 : 7)) >> 4
+ *       luma 4x1   each sample four times (turbo has no filter for it)
+ *                             When Wc <= 2 the 2x1 and 2x2 filters are not used: each sample is replicated 2x1 / 2x2.
+ *                             Luma, grayscale and 1x1 chroma samples are the same in both modes (one jpeg_idct_islow), so
+ *                             for a job with replacement chroma (up_wblk > 0) the filters bear on the stop-1 geometry
+ *                             alone.  YCbCr -> RGB takes turbo's jdcolor.c tables in this mode, in every layout and both
+ *                             geometries: built from five-digit constants, they differ from libjpeg 9's in one entry
+ *                             (FIX(0.34414) = 22554 against FIX(0.344136286) = 22553), which makes G one lower on a
+ *                             few (Cb, Cr) pairs.
+ *                             Bit for bit libjpeg-turbo's pixels wherever its C and SIMD code agree (its 16-bit SIMD
+ *                             IDCT departs from jidctint.c on extreme coef * quantiser products; JSIMD_FORCENONE=1
+ *                             selects the C code); outside that domain the mode is DEFINED as "the 8x8 islow of this
+ *                             library (exact over the whole int16 x uint16 domain), then these filters".
+ * opts NULL or opts[i] NULL is QS_HIP_UPSAMPLE_DCT, exactly info / prepare; any other value of `upsampling`:
+ * QS_HIP_EINVAL before anything is enqueued.  A batch may mix modes; per_job and *workspace_bytes do not depend on the
+ * mode.  The run call is unchanged, with all its promises: it works in the mode the last prepare wrote into the
+ * workspace's descriptors. */
+#define QS_HIP_UPSAMPLE_DCT      0   /* libjpeg 7..9: DCT-scaled chroma */
+#define QS_HIP_UPSAMPLE_TRIANGLE 1   /* libjpeg-turbo / 6b: 8x8 islow + jdsample.c's fancy upsampling */
+typedef struct {
+	int32_t upsampling;   /* QS_HIP_UPSAMPLE_* */
+} qs_hip_decode_opts;
+int qs_hip_decode_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_decode_opts *const *opts,
+		qs_hip_decode_info *per_job, size_t *workspace_bytes);
+int qs_hip_decode_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_decode_opts *const *opts,
+		void *d_workspace, size_t bytes, void *stream);
 
 /* ---- device entropy coder (the coefficient arrays of device-resident jobs -> the bytes of a baseline JPEG scan) ----
  * What libjpeg 9 writes between the SOS header and EOI when jpeg_write_coefficients gets the same arrays (jchuff.c:
@@ -562,7 +598,8 @@ const char *qs_hip_last_error(void);
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
  * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
  * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress,
- * the split route of the scan reader qs_hip_read_split_device_batch and its two calls).  A caller built against
+ * the split route of the scan reader qs_hip_read_split_device_batch and its two calls, the _opts calls of the decode).
+ * A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7
 int qs_hip_abi_version(void);

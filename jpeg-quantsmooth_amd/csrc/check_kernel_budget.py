@@ -65,16 +65,19 @@ def main(path):
 # the kernels of the scan reader's split route (qs_kernels_read_split.hip): nothing in scratch -- a lane's bit reader,
 # its state and the block it writes to live in registers, the code tables in LDS
 SPLIT_READ_KERNELS = ("qrs_map", "qrs_decode", "qrs_count", "qrs_tile_scan", "qrs_write", "qrs_dc_tiles", "qrs_dc_write")
+# the decode to pixels (qs_kernels_decode.hip): a lane's block, its IDCT workspace and the rows of the triangle filter
+# are arrays indexed by unrolled loops -- they stay in registers only as long as every index is a constant
+DECODE_KERNELS = ("qs_decode_kernel",)
 
 
 def main_no_scratch(prefix, path):
-    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS that starts with the prefix is there and
-    has no scratch"""
-    want = [k for k in SPLIT_READ_KERNELS if k.startswith(prefix)]
+    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS and DECODE_KERNELS that starts with the
+    prefix is there and has no scratch"""
+    want = [k for k in SPLIT_READ_KERNELS + DECODE_KERNELS if k.startswith(prefix)]
     recs = kernel_records(open(path).read())
     bad = 0
     for k in want:
-        hits = {n: r for n, r in recs.items() if re.search(rf"\d+{k}E", n)}
+        hits = {n: r for n, r in recs.items() if re.search(rf"\d+{k}[E\d]", n)}
         if len(hits) != 1 or "private_segment_fixed_size" not in next(iter(hits.values())):
             print(f"check_kernel_budget: ERROR: expected the metadata of one kernel {k} in {path}, found {sorted(hits)}", file=sys.stderr)
             bad += 1

@@ -28,6 +28,11 @@ enum {                           // the supported layouts (qs_hip_decode_device_
   QS_DEC_RGB = 2                 // RGB without a colour transform, same sampling set, no conversion
 };
 
+enum {                           // chroma upsampling (qs_hip_decode_opts: QS_HIP_UPSAMPLE_*)
+  QS_DEC_UP_DCT = 0,             // libjpeg 7..9: the scaled IDCTs below
+  QS_DEC_UP_TRIANGLE = 1         // libjpeg-turbo / 6b: 8x8 islow at chroma resolution, then jdsample.c's triangle filters
+};
+
 // One job as the kernel sees it (workspace, written by the prepare call): geometry and tables, no addresses.  Two
 // geometries when the job carries UPSAMPLE_UV's replacement chroma: variant 0 = the replacement chroma at luma
 // resolution (taken when d_stop[job] reads 0), variant 1 = the original chroma and sampling (reference :2835).
@@ -40,7 +45,8 @@ struct QsDecJob {
   QsDecGeom g[2];
   int32_t width, height;         // output crop
   int32_t layout, nout;          // QS_DEC_*, output samples per pixel (1 or 3)
-  int32_t two;                   // 1: the variant follows d_stop[job] (else variant 0)
+  int16_t two;                   // 1: the variant follows d_stop[job] (else variant 0)
+  int16_t upsampling;            // QS_DEC_UP_*: how subsampled chroma reaches luma resolution (the record keeps its size)
   int32_t tiles_x;               // output tiles of QS_DEC_TW x QS_DEC_TH pixels per tile row
   int32_t tile0, tiles;          // first workgroup of this job in its chunk's launch, and how many it has
   uint16_t q[3][64];             // the components' tables (natural order)
@@ -240,14 +246,94 @@ QS_DEC_HD void qd_idct_block(const int32_t* dq, uint8_t* dst, int stride) {
 // jdcolor.c (libjpeg 9, JCS_YCbCr): SCALEBITS 16, tables over the 256 chroma values
 #define QD_ONE_HALF (1 << 15)
 QS_DEC_HD int32_t qd_fix16(double x) { return (int32_t)(x * 65536.0 + 0.5); }
-QS_DEC_HD void qd_ycc_rgb(int y, int cb, int cr, uint8_t* out) {
+// cb_g: the constant of the Cb -> G table, the one entry in which the libraries differ (below)
+QS_DEC_HD void qd_ycc_rgb_g(int y, int cb, int cr, int32_t cb_g, uint8_t* out) {
   const int xb = cb - 128, xr = cr - 128;
   // (INT32 arithmetic: the products stay far below 2^31)
   const int crr = (int)((qd_fix16(1.402) * xr + QD_ONE_HALF) >> 16);
   const int cbb = (int)((qd_fix16(1.772) * xb + QD_ONE_HALF) >> 16);
-  const int g = (int)((-qd_fix16(0.714136286) * xr + (-qd_fix16(0.344136286) * xb + QD_ONE_HALF)) >> 16);
+  const int g = (int)((-qd_fix16(0.714136286) * xr + (-cb_g * xb + QD_ONE_HALF)) >> 16);
   auto lim = [](int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); };   // sample_range_limit
   out[0] = lim(y + crr);
   out[1] = lim(y + g);
   out[2] = lim(y + cbb);
+}
+// libjpeg 9 builds its tables from nine-digit constants, libjpeg-turbo and 6b from five-digit ones: FIX(1.40200),
+// FIX(1.77200) and FIX(0.71414) = FIX(0.714136286) = 46802 come out the same, FIX(0.34414) = 22554 does not
+// (FIX(0.344136286) = 22553), so turbo's green is one lower on a few (Cb, Cr) pairs.
+#define QD_CB_G_V9 22553
+#define QD_CB_G_TURBO 22554
+QS_DEC_HD void qd_ycc_rgb(int y, int cb, int cr, uint8_t* out) { qd_ycc_rgb_g(y, cb, cr, QD_CB_G_V9, out); }
+QS_DEC_HD void qd_ycc_rgb_turbo(int y, int cb, int cr, uint8_t* out) { qd_ycc_rgb_g(y, cb, cr, QD_CB_G_TURBO, out); }
+
+// ---- triangle-filter chroma upsampling (libjpeg-turbo / libjpeg 6b, jdsample.c) ---------------
+// A 2x-subsampled chroma component goes through the 8x8 islow at its own resolution and is then interpolated:
+//   2x1 (h2v1_fancy_upsample)  out[y][x] = (3 c[y][x>>1] + c[y][x even ? (x>>1)-1 : (x>>1)+1] + (x even ? 1 : 2)) >> 2
+//   1x2 (h1v2_fancy_upsample)  out[y][x] = (3 c[y>>1][x] + c[y even ? (y>>1)-1 : (y>>1)+1][x] + (y even ? 1 : 2)) >> 2
+//   2x2 (h2v2_fancy_upsample)  s[y][i] = 3 c[y>>1][i] + c[y even ? (y>>1)-1 : (y>>1)+1][i],
+//                              out[y][x] = (3 s[y][x>>1] + s[y][x even ? (x>>1)-1 : (x>>1)+1] + (x even ? 8 : 7)) >> 4
+// with every index clamped to the component's downsampled size Wc x Hc = ceil(width / hs) x ceil(height / vs) -- not to
+// the block grid: the IDCT's own samples beyond Wc / Hc never reach a pixel.  The horizontal filters are taken only
+// when Wc > 2 (jdsample.c: downsampled_width > 2); a narrower plane is replicated 2x horizontally, and for 2x2 also
+// vertically (h2v2_upsample).  4x1 has no filter: each sample four times (int_upsample).
+//
+// A tile holds each chroma component as a plane of blocks at chroma resolution: the blocks under its own
+// QS_DEC_TW x QS_DEC_TH pixels plus one block of context on each side the filter reaches across (left and right for
+// hs == 2, above and below for vs == 2).
+QS_DEC_HD int qd_tri_halo_x(int hs) { return hs == 2 ? 1 : 0; }      // context blocks on each side
+QS_DEC_HD int qd_tri_halo_y(int vs) { return vs == 2 ? 1 : 0; }
+#define QS_DEC_TRI_W 64          // the plane: at most 8 x 3 blocks (1x2), 6 x 3 (2x2), 6 x 2 (2x1), 2 x 2 (4x1)
+#define QS_DEC_TRI_H 24
+
+QS_DEC_HD int qd_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// One output column of a tile: the QS_DEC_TH samples of pixel column x, rows y0 .. y0 + QS_DEC_TH - 1 (y0 a multiple of
+// QS_DEC_TH), into out[r * ostride].  c: the component's plane, row stride `stride`, whose sample (0, 0) is sample
+// (ox, oy) of the component (negative at the image's left / top tiles); it must hold every sample (cx, cy) with
+// cx in {x / HS - 1, x / HS, x / HS + 1} and cy in y0 / VS - 1 .. (y0 + QS_DEC_TH) / VS after the clamp to
+// [0, Wc - 1] x [0, Hc - 1] -- nothing else is read.  Requires x / HS < Wc and y0 / VS < Hc.  Rows beyond the image
+// come out as the clamp gives them; the caller drops them.
+template <int HS, int VS>
+QS_DEC_HD void qd_tri_column(const uint8_t* c, int stride, int ox, int oy, int Wc, int Hc, int x, int y0, uint8_t* out,
+                             int ostride) {
+  constexpr int NR = QS_DEC_TH / VS;                       // chroma rows under the tile's rows
+  const bool fh = HS == 2 && Wc > 2;                       // the horizontal triangle filter
+  const int odd = x & 1;
+  const int cx = x / HS;
+  const int cxn = fh ? qd_clampi(odd ? cx + 1 : cx - 1, 0, Wc - 1) : cx;
+  const int cy0 = y0 / VS;
+  int t[NR + 2];                                           // rows cy0 - 1 .. cy0 + NR: 3 c[cx] + c[cxn] (fh), else c[cx]
+  QD_UNROLL
+  for (int j = (VS == 2 ? 0 : 1); j < (VS == 2 ? NR + 2 : NR + 1); ++j) {
+    const uint8_t* row = c + (qd_clampi(cy0 - 1 + j, 0, Hc - 1) - oy) * stride - ox;
+    t[j] = fh ? 3 * (int)row[cx] + (int)row[cxn] : (int)row[cx];
+  }
+  QD_UNROLL
+  for (int r = 0; r < QS_DEC_TH; ++r) {
+    int v;
+    if (VS == 2) {
+      const int j = 1 + (r >> 1), jn = (r & 1) ? j + 1 : j - 1;
+      if (HS == 1) v = (3 * t[j] + t[jn] + ((r & 1) ? 2 : 1)) >> 2;
+      else if (fh) v = (3 * t[j] + t[jn] + (odd ? 7 : 8)) >> 4;
+      else v = t[j];
+    } else {
+      v = fh ? (t[1 + r] + (odd ? 2 : 1)) >> 2 : t[1 + r];
+    }
+    out[r * ostride] = (uint8_t)v;
+  }
+}
+
+// qd_tri_column for a job's sampling (hs, vs) in {(2, 1), (1, 2), (2, 2), (4, 1)}
+QS_DEC_HD void qd_tri_column_any(int hs, int vs, const uint8_t* c, int stride, int ox, int oy, int Wc, int Hc, int x,
+                                 int y0, uint8_t* out, int ostride) {
+  if (hs == 2 && vs == 2) qd_tri_column<2, 2>(c, stride, ox, oy, Wc, Hc, x, y0, out, ostride);
+  else if (hs == 2) qd_tri_column<2, 1>(c, stride, ox, oy, Wc, Hc, x, y0, out, ostride);
+  else if (vs == 2) qd_tri_column<1, 2>(c, stride, ox, oy, Wc, Hc, x, y0, out, ostride);
+  else qd_tri_column<4, 1>(c, stride, ox, oy, Wc, Hc, x, y0, out, ostride);
+}
+
+// Whether block (bx, by) of a chroma component is one a tile's plane must hold: it lies in the component and carries at
+// least one sample inside the downsampled size (every clamped index falls into such a block).
+QS_DEC_HD bool qd_tri_block_needed(int bx, int by, int Wc, int Hc) {
+  return bx >= 0 && by >= 0 && bx * 8 < Wc && by * 8 < Hc;
 }

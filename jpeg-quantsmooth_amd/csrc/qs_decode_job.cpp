@@ -1,10 +1,11 @@
 // qs_decode_job.cpp -- the device decode to pixels of the flat C ABI (include/jpegqs_hip.h):
-// qs_hip_decode_device_batch_info / _prepare / qs_hip_decode_device_batch.  What libjpeg 9 delivers from
-// jpeg_read_scanlines (JDCT_ISLOW, default upsampling and output colour space) for the coefficient arrays of
-// qs_hip_job records -- typically the result of qs_hip_do_quantsmooth_device[_batch] -- computed on the device, every
-// job of a batch in one launch (qs_kernels_decode.hip).
+// qs_hip_decode_device_batch_info / _prepare (and their _opts forms) / qs_hip_decode_device_batch.  What libjpeg 9
+// delivers from jpeg_read_scanlines (JDCT_ISLOW, default upsampling and output colour space) for the coefficient arrays
+// of qs_hip_job records -- typically the result of qs_hip_do_quantsmooth_device[_batch] -- computed on the device, every
+// job of a batch in one launch (qs_kernels_decode.hip).  The chroma upsampling is per job (qs_hip_decode_opts):
+// libjpeg 9's DCT scaling, which is what the calls without opts do, or libjpeg-turbo's triangle filters.
 //
-// Workspace: one QsDecJob per job (geometry, tables, the job's tiles in its chunk's launch), written by prepare; its
+// Workspace: one QsDecJob per job (geometry, mode, tables, the job's tiles in its chunk's launch), written by prepare; its
 // layout and contents are a function of the jobs' geometry and tables alone.  The run passes the arrays and outputs in
 // the kernel arguments, QS_DEC_CHUNK jobs per launch.
 #include "qs_common.h"
@@ -80,8 +81,8 @@ int describe(const qs_hip_job* job, uint8_t* d_out, size_t pitch, QsDecJob* D, Q
 
 // the descriptors of a batch and, with d_out (the run), the kernel-argument records; the tile prefix restarts with
 // every chunk of QS_DEC_CHUNK jobs (one launch each)
-int describe_all(qs_hip_job* const* jobs, int njobs, uint8_t* const* d_out, const size_t* pitch,
-                 std::vector<QsDecJob>& D, std::vector<QsDecPtrs>* P, qs_hip_decode_info* info, const char* who) {
+int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_decode_opts* const* opts, uint8_t* const* d_out,
+                 const size_t* pitch, std::vector<QsDecJob>& D, std::vector<QsDecPtrs>* P, qs_hip_decode_info* info, const char* who) {
   if (!jobs || njobs < 1) return qs_fail(QS_HIP_EINVAL, "%s: %d jobs (at least one)", who, njobs);
   if (d_out && !pitch) return qs_fail(QS_HIP_EINVAL, "%s: null out_pitch", who);
   D.assign((size_t)njobs, QsDecJob());
@@ -92,6 +93,12 @@ int describe_all(qs_hip_job* const* jobs, int njobs, uint8_t* const* d_out, cons
     if (d_out && !out) return qs_fail(QS_HIP_EINVAL, "%s: job %d has no output buffer", who, i);
     if (int r = describe(jobs[i], out, d_out ? pitch[i] : 0, &D[i], P ? &(*P)[i] : nullptr, info ? &info[i] : nullptr,
                          Who(who, i).s)) return r;
+    if (const qs_hip_decode_opts* o = opts ? opts[i] : nullptr) {
+      if (o->upsampling != QS_HIP_UPSAMPLE_DCT && o->upsampling != QS_HIP_UPSAMPLE_TRIANGLE)
+        return qs_fail(QS_HIP_EINVAL, "%s: job %d: upsampling %d (QS_HIP_UPSAMPLE_DCT or QS_HIP_UPSAMPLE_TRIANGLE)", who, i,
+                       o->upsampling);
+      D[i].upsampling = o->upsampling == QS_HIP_UPSAMPLE_TRIANGLE ? QS_DEC_UP_TRIANGLE : QS_DEC_UP_DCT;
+    }
     if (i % QS_DEC_CHUNK == 0) tiles = 0;
     D[i].tile0 = (int)tiles;
     tiles += D[i].tiles;
@@ -102,29 +109,53 @@ int describe_all(qs_hip_job* const* jobs, int njobs, uint8_t* const* d_out, cons
 
 size_t workspace_bytes(int njobs) { return (size_t)njobs * sizeof(QsDecJob); }
 
+int info_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_decode_opts* const* opts, qs_hip_decode_info* per_job,
+              size_t* bytes, const char* who) {
+  if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
+  std::vector<QsDecJob> D;
+  if (int r = describe_all(jobs, njobs, opts, nullptr, nullptr, D, nullptr, per_job, who)) return r;
+  *bytes = workspace_bytes(njobs);
+  return QS_HIP_OK;
+}
+
+int prepare_impl(qs_hip_job* const* jobs, int njobs, const qs_hip_decode_opts* const* opts, void* d_workspace,
+                 size_t bytes, void* stream, const char* who) {
+  std::vector<QsDecJob> D;
+  if (int r = describe_all(jobs, njobs, opts, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
+  if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
+  if (int r = device_ok()) return r;
+  return upload(d_workspace, D, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" int qs_hip_decode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_decode_info* per_job,
                                                size_t* bytes) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_decode_device_batch_info";
-    if (!per_job || !bytes) return qs_fail(QS_HIP_EINVAL, "%s: null result", who);
-    std::vector<QsDecJob> D;
-    if (int r = describe_all(jobs, njobs, nullptr, nullptr, D, nullptr, per_job, who)) return r;
-    *bytes = workspace_bytes(njobs);
-    return QS_HIP_OK;
+    return info_impl(jobs, njobs, nullptr, per_job, bytes, "qs_hip_decode_device_batch_info");
+  });
+}
+
+extern "C" int qs_hip_decode_device_batch_info_opts(qs_hip_job* const* jobs, int njobs,
+                                                    const qs_hip_decode_opts* const* opts, qs_hip_decode_info* per_job,
+                                                    size_t* bytes) {
+  return guarded([&]() -> int {
+    return info_impl(jobs, njobs, opts, per_job, bytes, "qs_hip_decode_device_batch_info_opts");
   });
 }
 
 extern "C" int qs_hip_decode_device_batch_prepare(qs_hip_job* const* jobs, int njobs, void* d_workspace, size_t bytes,
                                                   void* stream) {
   return guarded([&]() -> int {
-    const char* who = "qs_hip_decode_device_batch_prepare";
-    std::vector<QsDecJob> D;
-    if (int r = describe_all(jobs, njobs, nullptr, nullptr, D, nullptr, nullptr, who)) return r;
-    if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
-    if (int r = device_ok()) return r;
-    return upload(d_workspace, D, static_cast<hipStream_t>(stream));
+    return prepare_impl(jobs, njobs, nullptr, d_workspace, bytes, stream, "qs_hip_decode_device_batch_prepare");
+  });
+}
+
+extern "C" int qs_hip_decode_device_batch_prepare_opts(qs_hip_job* const* jobs, int njobs,
+                                                       const qs_hip_decode_opts* const* opts, void* d_workspace,
+                                                       size_t bytes, void* stream) {
+  return guarded([&]() -> int {
+    return prepare_impl(jobs, njobs, opts, d_workspace, bytes, stream, "qs_hip_decode_device_batch_prepare_opts");
   });
 }
 
@@ -136,7 +167,7 @@ extern "C" int qs_hip_decode_device_batch(qs_hip_job* const* jobs, int njobs, co
     std::vector<QsDecJob> D;
     std::vector<QsDecPtrs> P;
     if (!d_out) return qs_fail(QS_HIP_EINVAL, "%s: null d_out", who);
-    if (int r = describe_all(jobs, njobs, d_out, out_pitch, D, &P, nullptr, who)) return r;
+    if (int r = describe_all(jobs, njobs, nullptr, d_out, out_pitch, D, &P, nullptr, who)) return r;
     if (int r = check_workspace(workspace_bytes(njobs), d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);

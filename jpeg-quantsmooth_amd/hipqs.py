@@ -102,6 +102,11 @@ class CompressOpts(C.Structure):
     _fields_ = [("downsampling", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class DecodeOpts(C.Structure):
+    """qs_hip_decode_opts: the chroma upsampling of one job of the device decode (UPSAMPLE_DCT / UPSAMPLE_TRIANGLE)"""
+    _fields_ = [("upsampling", C.c_int32)]
+
+
 class HuffTable(C.Structure):
     """qs_hip_huff_table: bits[l] = codes of length l, huffval = the symbols by increasing code length"""
     _fields_ = [("bits", C.c_uint8 * 17), ("huffval", C.c_uint8 * 256)]
@@ -155,6 +160,10 @@ COMPRESS_CHUNK = 44              # QS_HIP_COMPRESS_CHUNK: jobs per launch of the
 DOWNSAMPLE_BOX = 0               # QS_HIP_DOWNSAMPLE_BOX: do_fancy_downsampling = FALSE
 DOWNSAMPLE_DCT = 1               # QS_HIP_DOWNSAMPLE_DCT: libjpeg 9's default, 2x chroma through 16-point scaled DCTs
 DOWNSAMPLING = {"box": DOWNSAMPLE_BOX, "dct": DOWNSAMPLE_DCT}
+DECODE_CHUNK = 44                # QS_HIP_DECODE_CHUNK: jobs per launch of the device decode
+UPSAMPLE_DCT = 0                 # QS_HIP_UPSAMPLE_DCT: libjpeg 7..9, DCT-scaled chroma (the decode without opts)
+UPSAMPLE_TRIANGLE = 1            # QS_HIP_UPSAMPLE_TRIANGLE: libjpeg-turbo / 6b, 8x8 islow + jdsample.c's triangle filters
+UPSAMPLING = {"dct": UPSAMPLE_DCT, "triangle": UPSAMPLE_TRIANGLE}
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 # every symbol include/jpegqs_hip.h declares: (restype, argtypes)
@@ -188,6 +197,12 @@ ABI = {
                                                       C.c_void_p]),
     "qs_hip_decode_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_decode_device_batch_info_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                        C.POINTER(C.POINTER(DecodeOpts)), C.POINTER(DecodeInfo),
+                                                        C.POINTER(C.c_size_t)]),
+    "qs_hip_decode_device_batch_prepare_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                           C.POINTER(C.POINTER(DecodeOpts)), C.c_void_p, C.c_size_t,
+                                                           C.c_void_p]),
     "qs_hip_encode_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(EncodeInfo),
                                                    C.POINTER(C.c_size_t)]),
     "qs_hip_encode_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(HuffTables)),
@@ -534,23 +549,55 @@ class HipQS:
                                                                 d_workspace, nbytes, d_stop, stream))
 
     # -- device decode to pixels (a list of device_job() Jobs) ---------------------------
-    def decode_batch_info(self, jobs):
-        """qs_hip_decode_device_batch_info (no device needed) -> (list of dict(width, height, channels, layout),
-        the batch's workspace bytes)"""
+    @staticmethod
+    def _decode_opt_ptrs(opts, n):
+        """opts: one entry per job -- None (the dct mode), "dct" / "triangle", an UPSAMPLE_* value or a DecodeOpts -> (the
+        pointer array, what it points to: keep it alive over the call)"""
+        if len(opts) != n:
+            raise ValueError(f"decode opts: {len(opts)} entries for {n} jobs")
+        keep = []
+        for o in opts:
+            if o is None or isinstance(o, DecodeOpts):
+                keep.append(o)
+                continue
+            if isinstance(o, str):
+                if o not in UPSAMPLING:
+                    raise ValueError(f"decode opts: upsampling {o!r} (one of {sorted(UPSAMPLING)})")
+                o = UPSAMPLING[o]
+            rec = DecodeOpts()
+            rec.upsampling = int(o)
+            keep.append(rec)
+        arr = (C.POINTER(DecodeOpts) * max(1, n))(*[C.pointer(o) if o is not None else None for o in keep])
+        return arr, keep
+
+    def decode_batch_info(self, jobs, opts=None):
+        """qs_hip_decode_device_batch_info[_opts] (no device needed) -> (list of dict(width, height, channels, layout),
+        the batch's workspace bytes).  opts: None (the call without opts: every job in the dct mode), or one entry per
+        job: None, "dct", "triangle" (libjpeg-turbo's triangle-filter chroma upsampling) or a DecodeOpts"""
         per = (DecodeInfo * max(1, len(jobs)))()
         total = C.c_size_t(0)
-        self._check(self.lib.qs_hip_decode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        if opts is None:
+            self._check(self.lib.qs_hip_decode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
+        else:
+            arr, _keep = self._decode_opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_decode_device_batch_info_opts(self._job_ptrs(jobs), len(jobs), arr, per,
+                                                                      C.byref(total)))
         return [{f: int(getattr(per[i], f)) for f, _ in DecodeInfo._fields_} for i in range(len(jobs))], int(total.value)
 
     @staticmethod
     def _outs(d_out, pitch):
         return (C.c_void_p * max(1, len(d_out)))(*d_out), (C.c_size_t * max(1, len(pitch)))(*pitch)
 
-    def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None) -> None:
-        """qs_hip_decode_device_batch_prepare: geometry and tables into the workspace (synchronises `stream`; not inside
-        a capture)"""
-        self._check(self.lib.qs_hip_decode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), d_workspace, nbytes,
-                                                                stream))
+    def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, opts=None) -> None:
+        """qs_hip_decode_device_batch_prepare[_opts]: geometry, modes and tables into the workspace (synchronises
+        `stream`; not inside a capture); opts as decode_batch_info takes them"""
+        if opts is None:
+            self._check(self.lib.qs_hip_decode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), d_workspace, nbytes,
+                                                                    stream))
+        else:
+            arr, _keep = self._decode_opt_ptrs(opts, len(jobs))
+            self._check(self.lib.qs_hip_decode_device_batch_prepare_opts(self._job_ptrs(jobs), len(jobs), arr,
+                                                                         d_workspace, nbytes, stream))
 
     def decode_batch(self, jobs, d_stop, d_out, pitch, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_decode_device_batch: enqueue the decode of every job (one launch per 44 jobs); d_out[i] = device

@@ -233,12 +233,21 @@ def _decode_job(hip, coefs, quants, im, res, who, torch):
     return job
 
 
-def _decode_enqueue(jobs, dev, stop, outs, workspace, who):
-    """the decode's workspace (prepared outside any capture when the geometry or tables changed), the outputs, the run"""
+def _upsampling(value, who):
+    from .hipqs import UPSAMPLING
+    if not isinstance(value, str) or value not in UPSAMPLING:
+        raise ValueError(f"{who}: upsampling {value!r}: \"dct\" (libjpeg 7..9, DCT-scaled chroma) or \"triangle\" "
+                         f"(libjpeg-turbo / 6b, triangle-filter chroma upsampling)")
+    return value
+
+
+def _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes=None):
+    """the decode's workspace (prepared outside any capture when the geometry, tables or modes changed), the outputs,
+    the run.  modes: None (the calls without opts) or one "dct" / "triangle" per job"""
     import torch
     hip = _hip()
-    per, total = hip.decode_batch_info(jobs)
-    key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs)
+    per, total = hip.decode_batch_info(jobs, modes)
+    key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs) + (() if modes is None else ("upsampling", tuple(modes)))
     if workspace is None:
         workspace = Workspace()
     if workspace.key != key:
@@ -247,7 +256,8 @@ def _decode_enqueue(jobs, dev, stop, outs, workspace, who):
                                f"geometry (workspace=...): preparing one synchronises")
         if workspace.nbytes < total or workspace.buf.device != dev:      # (filled in place: decode() returns no dict)
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.decode_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+        hip.decode_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream,
+                                 modes)
         workspace.key = key
     if outs is None:
         outs = [None] * len(jobs)
@@ -275,10 +285,15 @@ def _check_stop(stop, n, dev, who, torch):
 
 
 def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, out=None,
-           workspace: Workspace | None = None):
+           workspace: Workspace | None = None, upsampling="dct"):
     """Decode coefficient tensors to pixels on the current stream, exactly as libjpeg 9 does (JDCT_ISLOW, its default
     upsampling -- 2x chroma by DCT scaling -- and default output colour space).  Returns a uint8 CUDA tensor
     (image_height, image_width, C): C = 1 for grayscale, 3 (RGB) for YCbCr and RGB images.
+
+    upsampling="dct": libjpeg 7..9's DCT-scaled chroma.  upsampling="triangle": the pixels of libjpeg-turbo and
+    libjpeg 6b (what Pillow, OpenCV and torchvision decode with) -- the 8x8 IDCT at chroma resolution, then jdsample.c's
+    triangle filters, and turbo's colour tables (its green is one lower than libjpeg 9's on a few (Cb, Cr) pairs).
+    Grayscale and RGB-kept images without subsampling come out the same in both.  Anything else raises ValueError.
 
     coefs, quants, hsamp, vsamp, colorspace: as quantsmooth_ takes them; image_size = (width, height) is required.
     result: what quantsmooth_ returned for these coefs -- its output tables and replacement chroma are used, and for
@@ -289,19 +304,27 @@ def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
     r = decode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                            image_size=image_size)],
                      result=None if result is None else dict(stop=result["stop"], images=[result]),
-                     outs=None if out is None else [out], workspace=workspace, _who="decode")
+                     outs=None if out is None else [out], workspace=workspace, upsampling=upsampling, _who="decode")
     return r["images"][0]
 
 
-def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None = None, _who="decode_batch") -> dict:
+def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None = None, upsampling="dct",
+                 _who="decode_batch") -> dict:
     """decode on many images in one call (one kernel launch for up to 44 images).  images[i]: a dict with decode's
-    per-image arguments (coefs, quants, hsamp, vsamp, colorspace, image_size).  result: what quantsmooth_batch_ returned
+    per-image arguments (coefs, quants, hsamp, vsamp, colorspace, image_size, and optionally upsampling, which overrides
+    this call's upsampling= for that image: one batch may mix modes).  result: what quantsmooth_batch_ returned
     for these images, in the same order.  outs: optional preallocated outputs.  Returns dict(images=[uint8 tensors],
-    workspace=Workspace)."""
+    workspace=Workspace).  A change of mode prepares the workspace again (outside a capture), as a change of geometry
+    does."""
     import torch
     who = _who
+    _upsampling(upsampling, who)
     if not isinstance(images, (list, tuple)) or not images:
         raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    modes = [upsampling if not isinstance(im, dict) or im.get("upsampling") is None
+             else _upsampling(im["upsampling"], f"{who}: image {i}") for i, im in enumerate(images)]
+    if all(m == "dct" for m in modes):
+        modes = None                                                    # (the calls without opts)
     for i, im in enumerate(images):
         if isinstance(im, dict) and im.get("image_size") is None:
             raise ValueError(f"{who}: image {i} has no image_size: the decode needs (width, height)")
@@ -327,7 +350,7 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
     if result is not None:
         stop = result["stop"]
         _check_stop(stop, len(images), dev, who, torch)
-    px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who)
+    px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes)
     return dict(images=px, workspace=workspace)
 
 

@@ -14,7 +14,8 @@ Prints one JSON line.
 8192^2 4:2:0 and --images x 1080p 4:2:0 in one batch, as time per call and GB/s of coefficients read plus samples
 written; and, for 8192^2 4:2:0, the host alternative it replaces: the copy of the coefficients to the host plus
 libjpeg 9's single-thread decode (tests/libjpeg9_decode.c, whose time includes writing the coefficients to an in-memory
-JPEG first).
+JPEG first).  --upsampling triangle runs the same three cases in the decode's triangle mode (libjpeg-turbo's chroma
+upsampling; no host alternative is timed).
 
 --encode times the device entropy coder (torch_qs.encode_scan_batch with the standard tables) on the same three cases:
 the encode plus the device-to-host copy of `len` bytes, next to the host alternative it replaces -- the copy of the
@@ -51,7 +52,7 @@ mode's: the gray case must.
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
                                        [--decode | --encode | --read [--split] [--no-host] | --compress]
                                        [--restart N | --restart-rows N]
-                                       [--downsampling box|dct]"""
+                                       [--downsampling box|dct] [--upsampling dct|triangle]"""
 import argparse
 import json
 import sys
@@ -82,6 +83,8 @@ def main():
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     ap.add_argument("--split", action="store_true",
                     help="--read: the split route (segments of an interval in parallel); works without a restart option")
+    ap.add_argument("--upsampling", choices=["dct", "triangle"], default="dct",
+                    help="--decode: dct (libjpeg 9's DCT-scaled chroma) or triangle (libjpeg-turbo's triangle filters)")
     ap.add_argument("--no-host", action="store_true", help="--read: do not time libjpeg's read of the file")
     ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
     ap.add_argument("--downsampling", choices=["box", "dct"], default="box",
@@ -212,15 +215,17 @@ def bench_decode(a):
     cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1)]),
              ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3)]),
              (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3)] * a.images)]
-    out = dict(tool="bench_device_batch", leg="decode", device=torch.cuda.get_device_name(dev), results=[])
+    out = dict(tool="bench_device_batch", leg="decode", upsampling=a.upsampling, device=torch.cuda.get_device_name(dev),
+               results=[])
+    mode = dict(upsampling=a.upsampling) if a.upsampling != "dct" else {}      # (dct: the call as it always was)
     for name, ims in cases:
         images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], quants=im["quants"], hsamp=im["hsamp"],
                        vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
         ws = torch_qs.Workspace()
-        outs = torch_qs.decode_batch(images, workspace=ws)["images"]
+        outs = torch_qs.decode_batch(images, workspace=ws, **mode)["images"]
         nbytes = sum(sum(c.numel() * 2 for c in im["coefs"]) for im in images) + sum(o.numel() for o in outs)
         for _ in range(3):
-            torch_qs.decode_batch(images, outs=outs, workspace=ws)
+            torch_qs.decode_batch(images, outs=outs, workspace=ws, **mode)
         torch.cuda.synchronize()
         ms = []
         for _ in range(a.repeats):
@@ -228,14 +233,14 @@ def bench_decode(a):
             calls = 20
             e0.record(stream)
             for _ in range(calls):
-                torch_qs.decode_batch(images, outs=outs, workspace=ws)
+                torch_qs.decode_batch(images, outs=outs, workspace=ws, **mode)
             e1.record(stream)
             e1.synchronize()
             ms.append(e0.elapsed_time(e1) / calls)
         med = float(np.median(ms))
         row = dict(case=name, images=len(images), mbytes=round(nbytes / 1e6, 1), ms=[round(m, 4) for m in ms],
                    median_ms=round(med, 4), gb_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
-        if name == "8192x8192_420":
+        if name == "8192x8192_420" and a.upsampling == "dct":       # (libjpeg 9 is the host alternative of the dct mode)
             with tempfile.TemporaryDirectory() as td:
                 lj9 = LibJpeg9(Path(td))
                 torch.cuda.synchronize()
