@@ -429,6 +429,75 @@ int qs_hip_encode_device_batch_files(qs_hip_job *const *jobs, int njobs, const q
 		int optimize, const int32_t *d_stop, uint8_t *const *d_out, const size_t *out_capacity, uint64_t *d_len,
 		int32_t *d_status, qs_hip_huff_tables *d_tables /* device, [njobs], may be NULL */,
 		void *d_scratch, size_t scratch_bytes, void *d_workspace, size_t bytes, void *stream);
+/* ---- progressive files (spectral selection) on the device ----
+ * d_out[i] receives the PROGRESSIVE file libjpeg 9 writes for jpeg_write_coefficients with cinfo.scan_info set to the
+ * job's script, and d_len[i] its length: head (SOI .. SOF2, the caller's: jpeg_file.compose_parts(progressive=True)),
+ * then per scan the DHT markers of that scan's own optimal tables (progressive mode forces optimize_coding; a DC scan
+ * writes the DC tables of its components, an AC scan the AC table of its component, each table once, in component
+ * order, directly in front of the scan's SOS), DRI whenever the scan's interval differs from the last one written (0 at
+ * the start), the SOS header and the entropy-coded segment, then EOI.
+ * A script is what libjpeg's validate_script accepts as progressive with Ah = 0 in every scan: scans in any component
+ * order, not necessarily every coefficient, an AC scan (1 <= Ss <= Se <= 63) with one component and behind a DC scan
+ * (Ss = Se = 0) of that component, every component with a DC scan, Al within 0 .. 10 (such a script has at most
+ * QS_HIP_MAX_SCANS scans).
+ * Anything libjpeg refuses: QS_HIP_EINVAL from info and prepare, naming the scan -- a scan that interleaves more than 10
+ * blocks per MCU included (the frame as a whole may have more: libjpeg's limit is per scan).  A script libjpeg accepts
+ * that has a refinement scan (Ah > 0): QS_HIP_ENOTSUP, naming the scan -- successive approximation is not implemented.
+ * A script libjpeg accepts as sequential multi-scan (the first scan is 0 .. 63): QS_HIP_ENOTSUP.
+ * DC scan: the value coded is coef[0] >> Al (arithmetic), the difference goes to the previous block of the component in
+ * scan order; several components are interleaved in the coder's MCU order with its dummy blocks, one component runs
+ * over width_in_blocks x height_in_blocks.  A category above 11: status 1.  AC scan: blocks in raster order over
+ * width_in_blocks x height_in_blocks, per coefficient |c| >> Al with the sign put back, run/size symbols with 0xF0 per
+ * 16 zeros, more than 10 bits after the shift: status 1; a block that ends in zeros inside the band adds 1 to the EOB
+ * run, which is written (symbol n << 4, n = floor(log2 run), and the low n bits) in front of the next symbol, at every
+ * restart boundary, at 0x7FFF and at the end of the scan.  Restart intervals count in the scan's own MCUs (one block in
+ * a one-component scan; restart_in_rows in the scan's MCU rows), as libjpeg's per_scan_setup does.
+ * component_id: the ids the SOS headers name (they must be the head's); all 0: jpeg_set_colorspace's for the job's colour
+ * space.  Huffman table slots are jpeg_set_colorspace's, as everywhere in the coder.
+ *   info     per job the number of scans, each scan's MCU count and the interval DRI carries (geometry variant 0), and
+ *            max_body_bytes: a bound on the file's length without its head.  *workspace_bytes and *scratch_bytes: what
+ *            prepare and the run need (both 256-byte aligned device memory).  The unstuffed stream of a scan is sized by
+ *            its own worst case per block: 27 bits in a DC scan, (Se - Ss + 1) * 26 + 30 in an AC scan (csrc/
+ *            qs_encode_prog.h).
+ *   prepare  writes the scan jobs' descriptors and every scan's DRI / SOS bytes into the workspace (synchronises
+ *            `stream`; not inside a capture) and remembers the plan under the workspace's address.
+ *   files    ENQUEUES the run on `stream`: no allocation, no synchronisation, no copy from host memory, no other stream;
+ *            a capture is a linear graph whose launch count follows from the batch and the scripts alone.  The unit of
+ *            work is a (job, scan) pair; all pairs of the batch go through the coder's stages side by side, in chunks
+ *            of QS_HIP_ENCODE_CHUNK pairs: 1 launch per chunk of jobs, then per chunk of pairs 11 (state and histogram
+ *            reset, block flags, head scan, EOB runs, histogram, the table kernel, sizes, bit scan, emit, the two
+ *            stuffing counts), then 1 framing launch per chunk of jobs and 1 stuffing launch per chunk of pairs.
+ *            frames[i]: d_head / head_bytes per geometry variant (d_mid is not looked at); variant 1 is used where the
+ *            whole-file run uses it (up_wblk > 0 and d_stop[i] != 0; d_stop NULL: variant 0).
+ *            d_status[i]: 0; 1 a refused coefficient in any scan; 5 a table whose code lengths pass 32; 2 capacity;
+ *            4 a workspace the run finds no prepare for (every job of the batch) -- precedence 4, 1, 5, 2.  With 1, 4
+ *            or 5 d_len[i] is 0 and the buffer unspecified; with 2 d_len[i] is exact and the buffer holds the file's
+ *            first out_capacity[i] bytes.  Nothing is stored at or beyond out_capacity[i].
+ *            A run with another number of jobs than the prepare saw: QS_HIP_EINVAL. */
+#define QS_HIP_MAX_SCANS 256
+typedef struct {
+	int32_t ncomp, comp[4];            /* comps_in_scan, component_index[] (frame order) */
+	int32_t Ss, Se, Ah, Al;
+} qs_hip_encode_scan;                  /* = jpeg_scan_info */
+typedef struct {
+	const qs_hip_encode_scan *scans;
+	int32_t nscans;
+	int32_t restart_interval, restart_in_rows;
+	int32_t component_id[QS_HIP_MAXC];
+} qs_hip_encode_prog_opts;
+typedef struct {
+	int32_t nscans;
+	int32_t mcus[QS_HIP_MAX_SCANS], interval[QS_HIP_MAX_SCANS];
+	uint64_t max_body_bytes;
+} qs_hip_encode_prog_info;
+int qs_hip_encode_progressive_device_batch_info(qs_hip_job *const *jobs, int njobs,
+		const qs_hip_encode_prog_opts *const *opts, qs_hip_encode_prog_info *per_job, size_t *workspace_bytes,
+		size_t *scratch_bytes);
+int qs_hip_encode_progressive_device_batch_prepare(qs_hip_job *const *jobs, int njobs,
+		const qs_hip_encode_prog_opts *const *opts, void *d_workspace, size_t bytes, void *stream);
+int qs_hip_encode_progressive_device_batch_files(qs_hip_job *const *jobs, int njobs, const qs_hip_encode_frame *frames,
+		const int32_t *d_stop, uint8_t *const *d_out, const size_t *out_capacity, uint64_t *d_len, int32_t *d_status,
+		void *d_scratch, size_t scratch_bytes, void *d_workspace, size_t bytes, void *stream);
 /* ---- device scan reader (the bytes of a JPEG scan with restart intervals -> device-resident coefficient arrays) ----
  * What libjpeg 9 leaves in its coefficient arrays after jpeg_read_coefficients (jdhuff.c decode_mcu: the DC prediction
  * runs as int and is stored as JCOEF, AC values by HUFF_EXTEND, de-zigzagged), for ONE sequential Huffman scan (SOF0 /

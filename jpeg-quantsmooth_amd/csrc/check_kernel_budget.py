@@ -68,25 +68,30 @@ SPLIT_READ_KERNELS = ("qrs_map", "qrs_decode", "qrs_count", "qrs_tile_scan", "qr
 # the decode to pixels (qs_kernels_decode.hip): a lane's block, its IDCT workspace and the rows of the triangle filter
 # are arrays indexed by unrolled loops -- they stay in registers only as long as every index is a constant
 DECODE_KERNELS = ("qs_decode_kernel",)
+# the progressive run (qs_kernels_encode_prog.inc): a lane's block is an array indexed by an unrolled walk over the band,
+# whose bounds are run-time values -- it stays in registers only as long as every index is a constant
+PROG_KERNELS = ("qp_begin", "qp_nofile", "qp_flags", "qp_headscan", "qp_runs", "qp_size", "qp_emit", "qp_frame")
+INSTANCES = {"qp_size": 2}         # template instantiations of one name (every other kernel: one)
 
 
 def main_no_scratch(prefix, path):
-    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS and DECODE_KERNELS that starts with the
-    prefix is there and has no scratch"""
-    want = [k for k in SPLIT_READ_KERNELS + DECODE_KERNELS if k.startswith(prefix)]
+    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS, DECODE_KERNELS and PROG_KERNELS that starts
+    with the prefix is there (in all its instantiations) and has no scratch"""
+    want = [k for k in SPLIT_READ_KERNELS + DECODE_KERNELS + PROG_KERNELS if k.startswith(prefix)]
     recs = kernel_records(open(path).read())
     bad = 0
     for k in want:
-        hits = {n: r for n, r in recs.items() if re.search(rf"\d+{k}[E\d]", n)}
-        if len(hits) != 1 or "private_segment_fixed_size" not in next(iter(hits.values())):
-            print(f"check_kernel_budget: ERROR: expected the metadata of one kernel {k} in {path}, found {sorted(hits)}", file=sys.stderr)
+        hits = {n: r for n, r in recs.items() if re.search(rf"\d+{k}[EI\d]", n)}
+        if len(hits) != INSTANCES.get(k, 1) or any("private_segment_fixed_size" not in r for r in hits.values()):
+            count = {1: "one kernel"}.get(INSTANCES.get(k, 1), f"{INSTANCES.get(k, 1)} kernels")
+            print(f"check_kernel_budget: ERROR: expected the metadata of {count} {k} in {path}, found {sorted(hits)}", file=sys.stderr)
             bad += 1
             continue
-        (n, r), = hits.items()
-        scratch = r["private_segment_fixed_size"]
-        print(f"check_kernel_budget: {n}: {r.get('vgpr_count')} VGPRs, {scratch} B scratch, {r.get('group_segment_fixed_size')} B LDS"
-              + (" -- ERROR: scratch" if scratch else ""), file=sys.stderr if scratch else sys.stdout)
-        bad += bool(scratch)
+        for n, r in sorted(hits.items()):
+            scratch = r["private_segment_fixed_size"]
+            print(f"check_kernel_budget: {n}: {r.get('vgpr_count')} VGPRs, {scratch} B scratch, {r.get('group_segment_fixed_size')} B LDS"
+                  + (" -- ERROR: scratch" if scratch else ""), file=sys.stderr if scratch else sys.stdout)
+            bad += bool(scratch)
     return 1 if bad or not want else 0
 
 

@@ -18,6 +18,7 @@
 #include "qs_stage.h"
 #include "qs_encode.h"
 #include "qs_huff.h"
+#include "qs_encode_prog.h"
 
 #include <algorithm>
 #include <mutex>
@@ -87,8 +88,10 @@ int derive(const qs_hip_huff_table& t, bool is_dc, uint32_t* out, int nout, cons
 }
 
 // one geometry: the sampling factors hs / vs, array strides and slots of its components
+// any_mcu: the caller codes the frame scan by scan (the progressive run) -- more than 10 blocks in the frame's MCU are its
+// to judge per scan, and the geometry comes back with the frame's MCU grid
 int geometry(const qs_hip_job* job, const int* hs, const int* vs, const int* stride, const int* rows, const int* slot,
-             QsEncGeom* g, const char* who) {
+             QsEncGeom* g, const char* who, bool any_mcu = false) {
   const int W = job->image_width, H = job->image_height;
   int d = 0;
   switch (qs_enc_geometry(job->ncomp, W, H, hs, vs, stride, rows, slot, g, &d)) {
@@ -96,13 +99,19 @@ int geometry(const qs_hip_job* job, const int* hs, const int* vs, const int* str
     case QS_GEOM_SHORT:
       return qs_fail(QS_HIP_EINVAL, "%s: component %d has %d x %d blocks, a %d x %d image sampled %dx%d needs %d x %d", who, d,
                      stride[d], rows[d], W, H, hs[d], vs[d], g->nw[d], g->nh[d]);
-    case QS_GEOM_MCU: return qs_fail(QS_HIP_ENOTSUP, "%s: %d blocks in an MCU; libjpeg takes at most 10", who, d);
+    case QS_GEOM_MCU:
+      if (any_mcu) {
+        qp_complete_frame(W, H, d, g);
+        return QS_HIP_OK;
+      }
+      return qs_fail(QS_HIP_ENOTSUP, "%s: %d blocks in an MCU; libjpeg takes at most 10", who, d);
     case QS_GEOM_SCAN: return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 blocks in the scan", who);
     default: return qs_fail(QS_HIP_EINVAL, "%s: bad job", who);      // (describe has looked at ncomp and the image)
   }
 }
 
-int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, qs_hip_encode_info* info, const char* who) {
+int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, qs_hip_encode_info* info, const char* who,
+             bool any_mcu = false) {
   if (int r = check_job(job, who)) return r;
   const int n = job->ncomp;
   if (job->image_width <= 0 || job->image_height <= 0 || job->image_width > 65500 || job->image_height > 65500)
@@ -144,7 +153,7 @@ int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays,
         P->nblk[slot[c]] = stride[c] * rows[c];
       }
     }
-    if (int rc = geometry(job, hs, vs, stride, rows, slot, &D->g[v], who)) return rc;
+    if (int rc = geometry(job, hs, vs, stride, rows, slot, &D->g[v], who, any_mcu)) return rc;
   }
   D->two = up ? 1 : 0;
   if (info) {
@@ -443,6 +452,11 @@ int prepare_opts(qs_hip_job* const* jobs, int njobs, const qs_hip_huff_tables* c
 }
 
 }  // namespace
+
+// describe() for the progressive run's driver (csrc/qs_encode_prog_job.cpp), which judges the MCU size scan by scan
+int qs_enc_describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, const char* who) {
+  return describe(job, D, P, need_arrays, nullptr, who, true);
+}
 
 extern "C" int qs_hip_encode_device_batch_info(qs_hip_job* const* jobs, int njobs, qs_hip_encode_info* per_job,
                                                size_t* bytes) {

@@ -683,3 +683,6 @@ void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, bool restart, hipSt
   if (restart) qe_launch<true>(a, wgs, swgs, s);
   else qe_launch<false>(a, wgs, swgs, s);
 }
+
+// the progressive run: its kernels stand on the ones above
+#include "qs_kernels_encode_prog.inc"

@@ -134,6 +134,27 @@ class EncodeOpts(C.Structure):
     _fields_ = [("restart_interval", C.c_int32), ("restart_in_rows", C.c_int32)]
 
 
+MAX_SCANS = 256                  # QS_HIP_MAX_SCANS: scans of one progressive script
+
+
+class EncodeScan(C.Structure):
+    """qs_hip_encode_scan: one scan of a progressive script (jpeg_scan_info)"""
+    _fields_ = [("ncomp", C.c_int32), ("comp", C.c_int32 * 4), ("Ss", C.c_int32), ("Se", C.c_int32), ("Ah", C.c_int32),
+                ("Al", C.c_int32)]
+
+
+class EncodeProgOpts(C.Structure):
+    """qs_hip_encode_prog_opts: the script and the restart settings of one job of the progressive run"""
+    _fields_ = [("scans", C.POINTER(EncodeScan)), ("nscans", C.c_int32), ("restart_interval", C.c_int32),
+                ("restart_in_rows", C.c_int32), ("component_id", C.c_int32 * MAXC)]
+
+
+class EncodeProgInfo(C.Structure):
+    """qs_hip_encode_prog_info: one job of the progressive run (qs_hip_encode_progressive_device_batch_info)"""
+    _fields_ = [("nscans", C.c_int32), ("mcus", C.c_int32 * MAX_SCANS), ("interval", C.c_int32 * MAX_SCANS),
+                ("max_body_bytes", C.c_uint64)]
+
+
 class ReadOpts(C.Structure):
     """qs_hip_read_opts: the Huffman tables of a file by DHT id (has_* 0: the standard table, ids 0 / 1), Td / Ta of each
     component and the DRI value"""
@@ -225,6 +246,17 @@ ABI = {
                                                     C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                     C.c_void_p]),
+    "qs_hip_encode_progressive_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                               C.POINTER(C.POINTER(EncodeProgOpts)),
+                                                               C.POINTER(EncodeProgInfo), C.POINTER(C.c_size_t),
+                                                               C.POINTER(C.c_size_t)]),
+    "qs_hip_encode_progressive_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                                  C.POINTER(C.POINTER(EncodeProgOpts)), C.c_void_p,
+                                                                  C.c_size_t, C.c_void_p]),
+    "qs_hip_encode_progressive_device_batch_files": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(EncodeFrame),
+                                                                C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                C.c_size_t, C.c_void_p]),
     "qs_hip_read_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
                                                  C.POINTER(ReadInfo), C.POINTER(C.c_size_t)]),
     "qs_hip_read_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(ReadOpts)),
@@ -774,6 +806,61 @@ class HipQS:
         self._check(self.lib.qs_hip_encode_device_batch_files(self._job_ptrs(jobs), len(jobs), fr, 1 if optimize else 0,
                                                               d_stop, outs, caps, d_len, d_status, d_tables, d_scratch,
                                                               scratch_bytes, d_workspace, nbytes, stream))
+
+    # -- progressive files (spectral selection) ---------------------------------------------
+    @staticmethod
+    def prog_opts(script, restart_interval=0, restart_in_rows=0, component_id=None) -> EncodeProgOpts:
+        """a qs_hip_encode_prog_opts: script = [(component indices, Ss, Se, Ah, Al)] (jpeg_file.spectral_script);
+        component_id None: jpeg_set_colorspace's ids"""
+        script = list(script)
+        arr = (EncodeScan * max(1, len(script)))()
+        for r, (comps, ss, se, ah, al) in zip(arr, script):
+            comps = list(comps)
+            r.ncomp = len(comps)
+            for k, c in enumerate(comps[:4]):
+                r.comp[k] = int(c)
+            r.Ss, r.Se, r.Ah, r.Al = int(ss), int(se), int(ah), int(al)
+        o = EncodeProgOpts(C.cast(arr, C.POINTER(EncodeScan)), len(script), int(restart_interval), int(restart_in_rows))
+        for k, v in enumerate(component_id or ()):
+            o.component_id[k] = int(v)
+        o._scans = arr                                                  # (kept alive with the record)
+        return o
+
+    @staticmethod
+    def _prog_opt_ptrs(opts, n):
+        if len(opts) != n:
+            raise ValueError("one EncodeProgOpts per job")
+        return (C.POINTER(EncodeProgOpts) * max(1, n))(*[C.pointer(o) for o in opts])
+
+    def encode_progressive_info(self, jobs, opts):
+        """qs_hip_encode_progressive_device_batch_info; no device needed -> (list of dict(nscans, mcus, interval,
+        max_body_bytes), workspace bytes, scratch bytes)"""
+        per = (EncodeProgInfo * max(1, len(jobs)))()
+        ws, sc = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.qs_hip_encode_progressive_device_batch_info(self._job_ptrs(jobs), len(jobs),
+                                                                         self._prog_opt_ptrs(opts, len(jobs)), per,
+                                                                         C.byref(ws), C.byref(sc)))
+        return [dict(nscans=int(p.nscans), mcus=list(p.mcus[:p.nscans]), interval=list(p.interval[:p.nscans]),
+                     max_body_bytes=int(p.max_body_bytes)) for p in per[:len(jobs)]], int(ws.value), int(sc.value)
+
+    def encode_progressive_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_encode_progressive_device_batch_prepare: the scan jobs and their DRI / SOS bytes into the workspace
+        (synchronises `stream`; not inside a capture)"""
+        self._check(self.lib.qs_hip_encode_progressive_device_batch_prepare(self._job_ptrs(jobs), len(jobs),
+                                                                            self._prog_opt_ptrs(opts, len(jobs)),
+                                                                            d_workspace, nbytes, stream))
+
+    def encode_progressive_files(self, jobs, frames, d_stop, d_out, capacity, d_len: int, d_status: int, d_scratch: int,
+                                 scratch_bytes: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_encode_progressive_device_batch_files: enqueue whole progressive files into d_out[i]; frames: one
+        EncodeFrame per job (its heads: SOI .. SOF2)"""
+        outs, caps = self._outs(d_out, capacity)
+        if len(frames) != len(jobs):
+            raise ValueError("one EncodeFrame per job")
+        fr = (EncodeFrame * max(1, len(jobs)))(*frames)
+        self._check(self.lib.qs_hip_encode_progressive_device_batch_files(self._job_ptrs(jobs), len(jobs), fr, d_stop, outs,
+                                                                          caps, d_len, d_status, d_scratch, scratch_bytes,
+                                                                          d_workspace, nbytes, stream))
 
     # -- device scan reader (a list of device_job() Jobs over the arrays to fill) ---------
     @staticmethod

@@ -47,11 +47,13 @@ def _dht(index: int, table) -> bytes:
 
 
 def compose_parts(quants, hsamp, vsamp, colorspace: int, image_size, dc_tables=None, ac_tables=None,
-                  restart_interval: int = 0):
+                  restart_interval: int = 0, progressive: bool = False):
     """-> (head, mid): the bytes of compose()'s file around its DHT markers and its segment.  head: SOI .. SOF, closed by
     the DHT markers when dc_tables / ac_tables are given; mid: DRI (when restart_interval is not 0) and the SOS header.
     head + [the DHT markers, where head has none] + mid + segment + FF D9 is compose()'s file: what the device's whole-file
-    run (qs_hip_encode_device_batch_files) takes as a qs_hip_encode_frame"""
+    run (qs_hip_encode_device_batch_files) takes as a qs_hip_encode_frame.
+    progressive: SOF2 in place of SOF0 / SOF1 and nothing else -- the head of a progressive file, whose scans are the
+    progressive run's (qs_hip_encode_progressive_device_batch_files); mid is then of no use"""
     if not 0 <= int(restart_interval) <= 65535:
         raise ValueError(f"restart_interval {restart_interval}: 0 .. 65535")
     if (dc_tables is None) != (ac_tables is None):
@@ -73,7 +75,7 @@ def compose_parts(quants, hsamp, vsamp, colorspace: int, image_size, dc_tables=N
         body = b"".join(struct.pack(">H", int(v)) for v in z) if prec else bytes(int(v) for v in z)
         out.append(_marker(0xDB, bytes([(prec << 4) | ci]) + body))
     sof = struct.pack(">BHHB", 8, h, w, n) + b"".join(bytes([ids[ci], (hsamp[ci] << 4) | vsamp[ci], ci]) for ci in range(n))
-    out.append(_marker(0xC1 if wide else 0xC0, sof))
+    out.append(_marker(0xC2 if progressive else 0xC1 if wide else 0xC0, sof))
     if dc_tables is not None:
         sent = set()
         for ci in range(n):
@@ -96,6 +98,83 @@ def compose(segment: bytes, quants, hsamp, vsamp, colorspace: int, image_size, d
     interval in MCUs; libjpeg writes DRI behind the last DHT whenever it is not 0, also when it exceeds the MCU count"""
     head, mid = compose_parts(quants, hsamp, vsamp, colorspace, image_size, dc_tables, ac_tables, restart_interval)
     return head + mid + bytes(segment) + b"\xff\xd9"
+
+
+# ---- scan scripts of progressive files (jpeg_scan_info: what cjpeg -scans reads) ------------------------------------------
+
+def scan(comps, ss: int, se: int, ah: int = 0, al: int = 0):
+    """one scan of a script: (component indices in frame order, Ss, Se, Ah, Al)"""
+    return (tuple(int(c) for c in comps), int(ss), int(se), int(ah), int(al))
+
+
+def spectral_script(ncomp: int):
+    """the DC scan over all components, then per component the bands 1-5 and 6-63, Al = 0 throughout: libjpeg's
+    jpeg_simple_progression without its successive-approximation steps"""
+    out = [scan(range(ncomp), 0, 0)]
+    for c in range(ncomp):
+        out += [scan([c], 1, 5), scan([c], 6, 63)]
+    return out
+
+
+class ScriptError(ValueError):
+    """a scan script libjpeg's validate_script refuses (or takes as sequential); .scan: where, or None"""
+
+    def __init__(self, msg, scan_index=None):
+        super().__init__(msg if scan_index is None else f"scan {scan_index}: {msg}")
+        self.scan = scan_index
+
+
+def validate_script(script, ncomp: int) -> bool:
+    """validate_script of jcmaster.c (libjpeg 9) for a progressive script on a frame of ncomp components.  -> True when
+    every scan has Ah = 0 (what the device writes), False when the script is valid but holds refinement scans; raises
+    ScriptError for what libjpeg refuses and for a script it takes as sequential multi-scan (first scan 0 .. 63)"""
+    script = list(script)
+    if not script:
+        raise ScriptError("no scans")
+    if script[0][1] == 0 and script[0][2] == 63:                       # libjpeg validates it by its sequential rules
+        sent = set()
+        for i, (comps, ss, se, ah, al) in enumerate(script):
+            if not 1 <= len(comps) <= 4 or any(not 0 <= c < ncomp for c in comps) \
+                    or any(b <= a for a, b in zip(comps, comps[1:])):
+                raise ScriptError("1 .. 4 components of the frame, in frame order", i)
+            if (ss, se, ah, al) != (0, 63, 0, 0) or sent & set(comps):
+                raise ScriptError("a scan of a sequential script that is not 0 .. 63 with Ah = Al = 0, or a component "
+                                  "sent twice", i)
+            sent |= set(comps)
+        if len(sent) != ncomp:
+            raise ScriptError("a component the sequential script does not send")
+        raise ScriptError("a sequential multi-scan script, not a progressive one", 0)
+    last = [[-1] * 64 for _ in range(ncomp)]
+    spectral = True
+    for i, (comps, ss, se, ah, al) in enumerate(script):
+        if not 1 <= len(comps) <= 4:
+            raise ScriptError("1 .. 4 components in a scan", i)
+        for k, c in enumerate(comps):
+            if not 0 <= c < ncomp:
+                raise ScriptError("a component index out of range", i)
+            if k and c <= comps[k - 1]:
+                raise ScriptError("components out of frame order", i)
+        if not (0 <= ss <= se <= 63 and 0 <= ah <= 10 and 0 <= al <= 10):
+            raise ScriptError("Ss <= Se within 0 .. 63 and Ah, Al within 0 .. 10", i)
+        if ss == 0 and se != 0:
+            raise ScriptError("DC and AC coefficients in one scan", i)
+        if ss != 0 and len(comps) != 1:
+            raise ScriptError("an AC scan carries one component", i)
+        for c in comps:
+            if ss != 0 and last[c][0] < 0:
+                raise ScriptError("an AC scan before the component's DC scan", i)
+            for k in range(ss, se + 1):
+                if last[c][k] < 0:
+                    if ah != 0:
+                        raise ScriptError("a first scan of a coefficient with Ah > 0", i)
+                elif ah != last[c][k] or al != ah - 1:
+                    raise ScriptError("a coefficient sent again without Ah = the last Al and Al = Ah - 1", i)
+                last[c][k] = al
+        spectral &= ah == 0
+    for c in range(ncomp):
+        if last[c][0] < 0:
+            raise ScriptError(f"component {c} has no DC scan")
+    return spectral
 
 
 # ---- the inverse: the markers of a file in front of its one scan ----------------------------------------------------------

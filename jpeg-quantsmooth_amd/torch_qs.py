@@ -682,7 +682,7 @@ def _file_frames(images, result, opts, optimize, huffman, who):
 
 
 def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=None, workspace: Workspace | None = None,
-                      restart_interval=None, restart_in_rows=None) -> dict:
+                      restart_interval=None, restart_in_rows=None, scans=None) -> dict:
     """Complete baseline JPEG files in device memory, byte for byte what libjpeg 9 writes for jpeg_write_coefficients
     (encode_batch's files), on the current stream and without host synchronisation: qs_hip_encode_device_batch_files.
 
@@ -699,9 +699,103 @@ def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=
     Returns dict(files=[uint8 tensors], len=int64 tensor, status=int32 tensor, tables, workspace): file i is
     files[i][:len[i]] when status[i] is 0.  status as encode_scan_batch, plus 5: a table with a code length above 32
     (libjpeg's "Huffman code size table overflow").  tables: with optimize a uint8 tensor (len(images), 1096) of
-    qs_hip_huff_tables records (huffman_of_tables reads one), else None."""
+    qs_hip_huff_tables records (huffman_of_tables reads one), else None.
+    scans: None (the baseline file above), or a progressive scan script -- [(component indices, Ss, Se, Ah, Al)] as
+    jpeg_file.spectral_script makes it, one for all images or a list of scripts, one per image -- for the PROGRESSIVE file
+    libjpeg writes with cinfo.scan_info set (qs_hip_encode_progressive_device_batch_files): SOF2, every scan with its own
+    optimal tables in front of it.  It requires optimize=True (libjpeg forces it) and every scan with Ah = 0; `tables` is
+    then None.  The restart keywords count in each scan's own MCUs."""
+    if scans is not None:
+        if not optimize or huffman is not None:
+            raise ValueError("encode_file_batch: a scan script requires optimize=True and no huffman (progressive mode forces "
+                             "optimal tables)")
+        return _encode_progressive_batch(images, result, scans, outs, workspace, "encode_file_batch",
+                                         _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"))
     return _encode_file_batch(images, result, optimize, huffman, outs, workspace, "encode_file_batch",
                               _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"))
+
+
+def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts):
+    import torch
+    from . import jpeg_file
+    jobs, dev, stop = _encode_jobs(images, result, who, torch)
+    hip = _hip()
+    n = len(jobs)
+    scans = list(scans)
+    if not scans:
+        raise ValueError(f"{who}: an empty scan script")
+    # a scan is (components, Ss, Se, Ah, Al): its second entry is a number, a script's second entry is a scan
+    per_image = [scans] * n if len(scans[0]) == 5 and not isinstance(scans[0][1], (list, tuple)) else [list(s) for s in scans]
+    if len(per_image) != n:
+        raise ValueError(f"{who}: one scan script per image")
+    for i, (script, im) in enumerate(zip(per_image, images)):
+        if not jpeg_file.validate_script(script, len(im["coefs"])):
+            raise ValueError(f"{who}: image {i}: the script holds refinement scans (Ah > 0), which are not implemented")
+    popts = [hip.prog_opts(script, *(opts[i] if opts is not None else (0, 0))) for i, script in enumerate(per_image)]
+    per, total, scratch_bytes = hip.encode_progressive_info(jobs, popts)
+    heads = []                                                          # per image and geometry variant: SOI .. SOF2
+    for i, im in enumerate(images):
+        res = None if result is None else result["images"][i]
+        ncomp = len(im["coefs"])
+        hs, vs = list(im.get("hsamp") or [1] * ncomp), list(im.get("vsamp") or [1] * ncomp)
+        quants = res["quants"] if res is not None else im.get("quants")
+        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
+        variants = [(hs, vs)]
+        if res is not None and res.get("coef_up") is not None:
+            variants = [([int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)),
+                        (hs, vs)]
+        if quants is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+        heads.append([jpeg_file.compose_parts(quants, vh, vv, cs, tuple(im["image_size"]), progressive=True)[0] for vh, vv in variants])
+    key = ("progressive", tuple(tuple(map(tuple, s)) for s in per_image), tuple(opts or ()),
+           tuple(_key(job, 0, 0) for job in jobs), tuple(tuple(h) for h in heads), str(dev))
+    if workspace is None:
+        workspace = Workspace()
+    if workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call with the same "
+                               f"geometry, scripts and markers (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.encode_progressive_prepare(jobs, popts, workspace.buf.data_ptr(), workspace.nbytes,
+                                       torch.cuda.current_stream(dev).cuda_stream)
+        blob, frames_at = bytearray(), []
+        for variants in heads:
+            frames_at.append([])
+            for head in variants:
+                frames_at[-1].append((len(blob), len(head)))
+                blob += head
+        buf = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+        base = buf.data_ptr()
+        frames = []
+        for variants in frames_at:
+            v = variants + [None] * (2 - len(variants))
+            frames.append(hip.encode_frame(head=[None if e is None else (base + e[0], e[1]) for e in v]))
+        workspace.files = dict(key=key, buf=buf, frames=frames, scratch=torch.empty(max(1, scratch_bytes), dtype=torch.uint8, device=dev),
+                               fixed=[max(e[1] for e in variants) for variants in frames_at])
+        workspace.key = key
+    fs = workspace.files
+    if outs is None:
+        outs = [None] * n
+    if len(outs) != n:
+        raise ValueError(f"{who}: one output (or None) per image")
+    bufs = []
+    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
+        if o is None:
+            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
+            o = torch.empty(fs["fixed"][i] + min(inf["max_body_bytes"], 4096 + 600 * inf["nscans"] + 40 * blocks), dtype=torch.uint8,
+                            device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
+                or not o.is_contiguous() or o.numel() < 1:
+            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
+        bufs.append(o)
+    length = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    hip.encode_progressive_files(jobs, fs["frames"], None if stop is None else stop.data_ptr(), [o.data_ptr() for o in bufs],
+                                 [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(), fs["scratch"].data_ptr(),
+                                 int(fs["scratch"].numel()), workspace.buf.data_ptr(), workspace.nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream)
+    return dict(files=bufs, len=length, status=status, tables=None, workspace=workspace)
 
 
 def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, opts):
@@ -761,9 +855,17 @@ def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, 
 
 
 def encode_file(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, optimize=True,
-                huffman=None, out=None, workspace: Workspace | None = None, restart_interval=None, restart_in_rows=None) -> dict:
+                huffman=None, out=None, workspace: Workspace | None = None, restart_interval=None, restart_in_rows=None,
+                scans=None) -> dict:
     """encode_file_batch on one image -> dict(file, len, status, tables, workspace); len and status are device tensors of
     one element"""
+    if scans is not None:
+        r = encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
+                                    image_size=image_size)],
+                              result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
+                              huffman=huffman, outs=None if out is None else [out], workspace=workspace,
+                              restart_interval=restart_interval, restart_in_rows=restart_in_rows, scans=list(scans))
+        return dict(file=r["files"][0], len=r["len"], status=r["status"], tables=None, workspace=r["workspace"])
     r = _encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                                  image_size=image_size)],
                            None if result is None else dict(stop=result["stop"], images=[result]), optimize, huffman,

@@ -30,6 +30,12 @@ the plain run -- and, separately, the wall time of the route it replaces as a wh
 with its two host round trips; and the file sizes with the standard and with the optimized tables.  Exits non-zero
 unless the first file of each case is libjpeg's optimized file.
 
+--encode --progressive times the progressive run (torch_qs.encode_file_batch(scans=jpeg_file.spectral_script(n)): every
+(job, scan) pair through histogram, table kernel, coder and framing) on the same three cases, in device time, next to the
+baseline whole-file run with optimized tables on the same arrays in the same process, with the ratio of the two and the
+sizes of the progressive and the baseline-optimized files.  Exits non-zero unless the first file of each case is the
+file libjpeg writes with that script (tests/libjpeg9_encode_prog.c).
+
 --read times the device scan reader (torch_qs.read_batch) on the same three cases, on files the device coder wrote with
 --restart N / --restart-rows N: the upload of the file from pinned memory plus the read, and the read alone, next to the
 host route it replaces -- libjpeg 9's jpeg_read_coefficients on one core (tests/libjpeg9_decode.c read: its time
@@ -50,7 +56,7 @@ route and the comparison, tests/libjpeg9_compress_fancy.c) and reports whether e
 mode's: the gray case must.
 
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode | --read [--split] [--no-host] | --compress]
+                                       [--decode | --encode [--optimize-files | --progressive] | --read [--split] [--no-host] | --compress]
                                        [--restart N | --restart-rows N]
                                        [--downsampling box|dct] [--upsampling dct|triangle]"""
 import argparse
@@ -80,6 +86,8 @@ def main():
                     help="--encode: write a restart marker every N MCU rows (libjpeg's restart_in_rows)")
     ap.add_argument("--optimize-files", action="store_true",
                     help="--encode: time the whole-file run with optimized tables next to the histogram run plus the plain run")
+    ap.add_argument("--progressive", action="store_true",
+                    help="--encode: time the progressive run (spectral selection) next to the baseline whole-file run")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     ap.add_argument("--split", action="store_true",
                     help="--read: the split route (segments of an interval in parallel); works without a restart option")
@@ -96,6 +104,8 @@ def main():
         return bench_read(a)
     if a.decode:
         return bench_decode(a)
+    if a.encode and a.progressive:
+        return bench_encode_progressive(a)
     if a.encode and a.optimize_files:
         return bench_encode_files(a)
     if a.encode:
@@ -445,6 +455,79 @@ def bench_encode_files(a):
     bad = [r["case"] for r in out["results"] if not r["identical"]]
     if bad:
         raise SystemExit(f"bench_device_batch --encode --optimize-files: {bad}: the file is not libjpeg's optimized file")
+
+
+def bench_encode_progressive(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import synth_image
+    pkg = jpegqs_pkg.load()
+    torch_qs, jpeg_file = pkg.torch_qs, pkg.jpeg_file
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows) if a.restart or a.restart_rows else {}
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1, amp=30)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
+             (f"{a.images}x1920x1080_420", [synth_image(rng, (1920, 1080), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
+    out = dict(tool="bench_device_batch", leg="encode --progressive", device=torch.cuda.get_device_name(dev), results=[])
+    if rst:
+        out["restart"] = rst
+    for name, ims in cases:
+        unit = [np.ones(64, np.uint16)] * len(ims[0]["coefs"])
+        images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], quants=unit, hsamp=im["hsamp"],
+                       vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
+        script = jpeg_file.spectral_script(len(ims[0]["coefs"]))
+        wp, wf = torch_qs.Workspace(), torch_qs.Workspace()
+        r = torch_qs.encode_file_batch(images, workspace=wp, scans=script, **rst)
+        pfiles, plens = r["files"], [int(v) for v in r["len"].cpu().tolist()]
+        assert r["status"].cpu().tolist() == [0] * len(images), "the default capacity did not hold the progressive file"
+        b = torch_qs.encode_file_batch(images, workspace=wf, **rst)
+        bfiles, blens = b["files"], [int(v) for v in b["len"].cpu().tolist()]
+        assert b["status"].cpu().tolist() == [0] * len(images)
+
+        def progressive_run():
+            torch_qs.encode_file_batch(images, outs=pfiles, workspace=wp, scans=script, **rst)
+
+        def baseline_run():
+            torch_qs.encode_file_batch(images, outs=bfiles, workspace=wf, **rst)
+
+        def med(fn, calls):
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(a.repeats):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1) / calls)
+            return round(float(np.median(ms)), 3), [round(m, 3) for m in ms]
+
+        b_ms, b_all = med(baseline_run, 10)
+        p_ms, p_all = med(progressive_run, 10)
+        b2_ms, b2_all = med(baseline_run, 10)                        # (again, behind the other: the pair's own spread)
+        first = pfiles[0][:plens[0]].cpu().numpy().tobytes()
+        row = dict(case=name, images=len(images), scans=len(script), progressive_ms=p_ms, progressive_windows=p_all,
+                   baseline_optimized_ms=b_ms, baseline_windows=b_all, baseline_again_ms=b2_ms, baseline_again_windows=b2_all,
+                   progressive_over_baseline=round(p_ms / min(b_ms, b2_ms), 3), progressive_bytes=sum(plens),
+                   baseline_optimized_bytes=sum(blens), progressive_over_baseline_bytes=round(sum(plens) / sum(blens), 4))
+        with tempfile.TemporaryDirectory() as td:
+            from encode_prog_oracle import LibJpeg9EncProg
+            row["identical"] = bool(LibJpeg9EncProg(Path(td)).write(dict(ims[0], quants=unit), script, a.restart or 0,
+                                                                    a.restart_rows or 0) == first)
+        out["results"].append(row)
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    if bad:
+        raise SystemExit(f"bench_device_batch --encode --progressive: {bad}: the file is not libjpeg's progressive file")
 
 
 def bench_read(a):
