@@ -429,7 +429,7 @@ int qs_hip_encode_device_batch_files(qs_hip_job *const *jobs, int njobs, const q
 		int optimize, const int32_t *d_stop, uint8_t *const *d_out, const size_t *out_capacity, uint64_t *d_len,
 		int32_t *d_status, qs_hip_huff_tables *d_tables /* device, [njobs], may be NULL */,
 		void *d_scratch, size_t scratch_bytes, void *d_workspace, size_t bytes, void *stream);
-/* ---- progressive files (spectral selection) on the device ----
+/* ---- progressive files (spectral selection, and successive approximation behind a flag) on the device ----
  * d_out[i] receives the PROGRESSIVE file libjpeg 9 writes for jpeg_write_coefficients with cinfo.scan_info set to the
  * job's script, and d_len[i] its length: head (SOI .. SOF2, the caller's: jpeg_file.compose_parts(progressive=True)),
  * then per scan the DHT markers of that scan's own optimal tables (progressive mode forces optimize_coding; a DC scan
@@ -442,8 +442,21 @@ int qs_hip_encode_device_batch_files(qs_hip_job *const *jobs, int njobs, const q
  * QS_HIP_MAX_SCANS scans).
  * Anything libjpeg refuses: QS_HIP_EINVAL from info and prepare, naming the scan -- a scan that interleaves more than 10
  * blocks per MCU included (the frame as a whole may have more: libjpeg's limit is per scan).  A script libjpeg accepts
- * that has a refinement scan (Ah > 0): QS_HIP_ENOTSUP, naming the scan -- successive approximation is not implemented.
+ * that has a refinement scan (Ah > 0): QS_HIP_ENOTSUP, naming the scan ("refinement scans are not implemented"), unless
+ * the job's opts->flags has QS_HIP_PROG_REFINE (below).
  * A script libjpeg accepts as sequential multi-scan (the first scan is 0 .. 63): QS_HIP_ENOTSUP.
+ * flags = QS_HIP_PROG_REFINE: every script libjpeg accepts as progressive is written, refinement scans included, up to
+ * QS_HIP_MAX_SCANS scans (a valid longer script: QS_HIP_ENOTSUP; any other flag bit: QS_HIP_EINVAL).  DC refinement (Ss =
+ * Se = 0, Ah > 0): one bit per block, (coef[0] >> Al) & 1, a dummy block repeating the bit before it; no symbols, so no
+ * DHT marker, and its SOS names table 0 for every component (jcmarker.c emit_sos).  AC refinement (Ss >= 1, Ah > 0):
+ * with a = |c| >> Al, a coefficient with a == 1 is newly nonzero -- symbol (run << 4) | 1 and its sign bit, with 0xF0 per
+ * 16 zeros in front of it -- one with a > 1 sends the correction bit a & 1 behind the next symbol of the block, or, behind
+ * the block's last symbol, with the EOB run: the run's symbol is followed by the buffered correction bits of all its
+ * blocks, and it is written in front of the next block with a newly nonzero coefficient, at a restart boundary, at the
+ * end, at 0x7FFF blocks or once more than 937 bits are buffered.  No range check: status 1 cannot arise in such a scan.
+ * Worst case per block 1 bit and (Se - Ss + 1) * 17 + 14 bits.  A chunk of pairs with a refinement scan adds 7 + R
+ * launches, R = ceil(log2(ceil(blocks of the longest restart interval or scan / 15))) rounds of pointer doubling, which
+ * follows from the geometry alone.
  * DC scan: the value coded is coef[0] >> Al (arithmetic), the difference goes to the previous block of the component in
  * scan order; several components are interleaved in the coder's MCU order with its dummy blocks, one component runs
  * over width_in_blocks x height_in_blocks.  A category above 11: status 1.  AC scan: blocks in raster order over
@@ -475,6 +488,7 @@ int qs_hip_encode_device_batch_files(qs_hip_job *const *jobs, int njobs, const q
  *            first out_capacity[i] bytes.  Nothing is stored at or beyond out_capacity[i].
  *            A run with another number of jobs than the prepare saw: QS_HIP_EINVAL. */
 #define QS_HIP_MAX_SCANS 256
+#define QS_HIP_PROG_REFINE 1
 typedef struct {
 	int32_t ncomp, comp[4];            /* comps_in_scan, component_index[] (frame order) */
 	int32_t Ss, Se, Ah, Al;
@@ -484,6 +498,7 @@ typedef struct {
 	int32_t nscans;
 	int32_t restart_interval, restart_in_rows;
 	int32_t component_id[QS_HIP_MAXC];
+	int32_t flags;                     /* 0, or QS_HIP_PROG_REFINE: refinement scans (Ah > 0) are written */
 } qs_hip_encode_prog_opts;
 typedef struct {
 	int32_t nscans;

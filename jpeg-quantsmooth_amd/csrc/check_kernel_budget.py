@@ -70,8 +70,9 @@ SPLIT_READ_KERNELS = ("qrs_map", "qrs_decode", "qrs_count", "qrs_tile_scan", "qr
 DECODE_KERNELS = ("qs_decode_kernel",)
 # the progressive run (qs_kernels_encode_prog.inc): a lane's block is an array indexed by an unrolled walk over the band,
 # whose bounds are run-time values -- it stays in registers only as long as every index is a constant
-PROG_KERNELS = ("qp_begin", "qp_nofile", "qp_flags", "qp_headscan", "qp_runs", "qp_size", "qp_emit", "qp_frame")
-INSTANCES = {"qp_size": 2}         # template instantiations of one name (every other kernel: one)
+PROG_KERNELS = ("qp_begin", "qp_nofile", "qp_flags", "qp_headscan", "qp_runs", "qp_size", "qp_emit", "qp_frame",
+                "qr_flags", "qr_wsum", "qr_wscan", "qr_next", "qr_hop")      # qr_: the refinement scans' own
+INSTANCES = {"qp_size": 4, "qp_emit": 2}     # template instantiations of one name (every other kernel: one)
 
 
 def main_no_scratch(prefix, path):

@@ -1,6 +1,8 @@
-// qs_encode_prog.h -- progressive JPEG files (spectral selection, Ah = 0) from device-resident coefficient arrays
+// qs_encode_prog.h -- progressive JPEG files (spectral selection; refinement scans, Ah > 0, behind QS_HIP_PROG_REFINE) from
+// device-resident coefficient arrays
 // (qs_hip_encode_progressive_device_batch_*): what the kernels (csrc/qs_kernels_encode_prog.inc), the host driver
-// (csrc/qs_encode_prog_job.cpp) and a plain host build (tests/encode_prog_host.cpp) share.  DESIGN.md section 17.
+// (csrc/qs_encode_prog_job.cpp) and the plain host builds (tests/encode_prog_host.cpp, tests/encode_refine_host.cpp) share.
+// DESIGN.md sections 17 and 17.1.
 //
 // The file is head (SOI .. SOF2, the caller's) | per scan: the DHT markers of the scan's own optimal tables, DRI where
 // the scan's interval differs from the last one written, the SOS header, the entropy-coded segment | EOI -- what
@@ -12,6 +14,13 @@
 //   AC scan   (Se - Ss + 1) * (16 + 10) + (16 + 14)    (every band coefficient a symbol of its own, plus one EOB-run
 //                                                       symbol with up to 14 appended bits, written by the run's last block)
 // A 1..63 band gives 1668 bits = 208.5 bytes: more than the baseline coder's 1665 bits per block.
+// Refinement scans (Ah > 0; jchuff.c encode_mcu_DC_refine / encode_mcu_AC_refine /
+// emit_buffered_bits):
+//   DC refinement   1                                  (the bit itself: no symbol, no table)
+//   AC refinement   (Se - Ss + 1) * 17 + 14            (a newly nonzero coefficient is a symbol and its sign, any other at
+//                                                       most one bit -- a correction bit, or its share of a 0xF0; the run
+//                                                       symbol of the piece the block starts, which needs a coefficient
+//                                                       that is not newly nonzero: 16 + 14 in place of that one's 16)
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -22,6 +31,12 @@
 #define QP_DC_MAXBITS 27
 #define QP_AC_MAXBITS(Ss, Se) (((Se) - (Ss) + 1) * 26 + 30)
 #define QP_MAXBITS QP_AC_MAXBITS(1, 63)
+#define QR_CORR_MAX 937            // MAX_CORR_BITS - DCTSIZE2 + 1: emit_eobrun is forced once more bits than this are buffered
+#define QR_TAIL_MAX 63             // correction bits one block adds to the buffer
+#define QR_PIECE_MIN (QR_CORR_MAX / QR_TAIL_MAX + 1)   // blocks it takes to pass QR_CORR_MAX: 15
+#define QR_DC_MAXBITS 1
+#define QR_AC_MAXBITS(Ss, Se) (((Se) - (Ss) + 1) * 17 + 14)
+#define QR_HD QS_ENC_HD __attribute__((always_inline))   // the walk over the band keeps the block in registers only inlined
 // words the emit kernel stages per workgroup: 256 blocks of QP_MAXBITS and up to 7 pad bits each behind up to 31 bits
 #define QP_LDS_WORDS ((31 + QS_ENC_WG * (QP_MAXBITS + 7) + 31) / 32)
 #define QP_MID_MAX (6 + 4 + 2 + 2 * 4 + 3 + 1)   // DRI marker and the longest SOS header, rounded up
@@ -240,6 +255,96 @@ QS_ENC_HD void qp_eobrun(int run, int tb, Sink& s) {
   s.ac(tb, n << 4, (uint32_t)run & ((1u << n) - 1u), n);
 }
 
+// ---- refinement scans (Ah > 0); the sink also takes raw(bits, n <= 32): bits without a symbol ----
+
+// correction bits in the order they were buffered: the first one on top
+struct QrBits {
+  uint64_t v;
+  int n;                           // at most QR_TAIL_MAX
+};
+template <class Sink>
+QR_HD void qr_put_bits(Sink& s, const QrBits& b) {
+  if (b.n > 32) s.raw((uint32_t)(b.v >> 32), b.n - 32);
+  if (b.n > 0) s.raw((uint32_t)b.v, b.n > 32 ? 32 : b.n);
+}
+struct QrNullSink {
+  QS_ENC_HD void ac(int, int, uint32_t, int) {}
+  QS_ENC_HD void raw(uint32_t, int) {}
+};
+
+// encode_mcu_DC_refine for one block: the bit Al of the DC (arithmetic shift)
+template <class Sink>
+QR_HD void qr_dc_refine(int dc, int Al, Sink& s) {
+  s.raw((uint32_t)(dc >> Al) & 1u, 1);
+}
+
+template <int K>
+QR_HD void qr_eob_steps(const int16_t* v, int Ss, int Se, int Al, int& eob) {
+  if constexpr (K < 64) {
+    if (K >= Ss && K <= Se) {
+      const int c = v[QP_ZZ[K]];
+      if (((c < 0 ? -c : c) >> Al) == 1) eob = K;
+    }
+    qr_eob_steps<K + 1>(v, Ss, Se, Al, eob);
+  }
+}
+template <int K, class Sink>
+QR_HD void qr_ac_steps(const int16_t* v, int Ss, int Se, int Al, int tb, int eob, int& run, QrBits& br, Sink& s) {
+  if constexpr (K < 64) {
+    if (K >= Ss && K <= Se) {
+      const int c = v[QP_ZZ[K]];
+      const uint32_t t = (uint32_t)(c < 0 ? -c : c) >> Al;
+      if (t == 0) {
+        ++run;
+      } else {
+        for (;;) {
+          // 0xF0 per 16 zeros in front of it, but not behind the last new coefficient: those are folded into the EOB run
+          const bool zrl = run > 15 && K <= eob;
+          if (!zrl && t > 1) {                     // nonzero before this scan: one correction bit, and the run goes on
+            br.v = (br.v << 1) | (t & 1u);
+            ++br.n;
+            break;
+          }
+          // either symbol takes the correction bits buffered so far behind it
+          s.ac(tb, zrl ? 0xF0 : (run << 4) | 1, (zrl || c < 0) ? 0u : 1u, zrl ? 0 : 1);
+          qr_put_bits(s, br);
+          br.v = 0;
+          br.n = 0;
+          if (!zrl) {
+            run = 0;
+            break;
+          }
+          run -= 16;
+        }
+      }
+    }
+    qr_ac_steps<K + 1>(v, Ss, Se, Al, tb, eob, run, br, s);
+  }
+}
+// encode_mcu_AC_refine for one block, without the EOB run: the symbols the block itself writes, and *tail: the correction
+// bits it leaves in the buffer.  -> QP_F_WRITES: it has a newly nonzero coefficient (its first symbol is preceded by the
+// pending run); QP_F_ENDZ: it adds 1 to the EOB run and *tail to the run's buffered bits (r > 0 || BR > 0)
+template <class Sink>
+QR_HD uint32_t qr_ac_refine(const int16_t* v, int Ss, int Se, int Al, int tb, Sink& s, QrBits* tail) {
+  int eob = 0, run = 0;
+  qr_eob_steps<1>(v, Ss, Se, Al, eob);
+  QrBits br = {0, 0};
+  qr_ac_steps<1>(v, Ss, Se, Al, tb, eob, run, br, s);
+  *tail = br;
+  return (eob > 0 ? QP_F_WRITES : 0u) | ((run > 0 || br.n > 0) ? QP_F_ENDZ : 0u);
+}
+// The same block in the form the kernels write: its own symbols, then the symbol of the run piece that STARTS with it
+// (piece: its length, 0: none starts here), then its tail.  libjpeg writes a piece's symbol and then the tails of all its
+// blocks, behind the symbols of a writing first block: the same bits, and each block's share of them is contiguous
+template <class Sink>
+QR_HD uint32_t qr_ac_block(const int16_t* v, int Ss, int Se, int Al, int tb, int piece, Sink& s) {
+  QrBits tail;
+  const uint32_t f = qr_ac_refine(v, Ss, Se, Al, tb, s, &tail);
+  if (piece) qp_eobrun(piece, tb, s);
+  if (f & QP_F_ENDZ) qr_put_bits(s, tail);
+  return f;
+}
+
 // The EOB runs of an AC scan, block by block.  A "head" is a block that writes or starts a restart interval; `head` is
 // the last one at or before block b, fhead its flags, per the blocks of an interval, next_writes whether block b + 1
 // writes.  A run starts at the head (behind it when the head does not end in zeros), takes every block up to the next
@@ -302,6 +407,7 @@ struct QpHistSink {
   uint32_t (*h)[257];                              // [4][257]: DC 0, DC 1, AC 0, AC 1
   void dc(int tb, int cat, uint32_t) { ++h[tb][cat]; }
   void ac(int tb, int sym, uint32_t, int) { ++h[2 + tb][sym]; }
+  void raw(uint32_t, int) {}
 };
 
 // a byte buffer that counts past its capacity and stores below it
@@ -326,6 +432,14 @@ struct QpBitSink {
     if (!sz) flags |= QS_ENC_F_NOCODE;
     acc = (acc << (sz + nb)) | ((uint64_t)(e & 0xffffu) << nb) | val;
     n += sz + nb;
+    drain();
+  }
+  void raw(uint32_t val, int nb) {                 // nb <= 32 bits without a symbol
+    acc = (acc << nb) | val;
+    n += nb;
+    drain();
+  }
+  void drain() {
     while (n >= 8) {
       n -= 8;
       const uint32_t b = (uint32_t)(acc >> n) & 0xffu;
@@ -355,36 +469,59 @@ static inline uint32_t qp_scan_serial(const QsEncGeom& g, const QpArrays& A, con
                                       Sink& s, Boundary boundary) {
   uint32_t flags = 0;
   int eobrun = 0;
+  // AC refinement: libjpeg's bit_buffer, the tails of the run's blocks in order, and BE, their bits
+  QrBits* be = (r.Ah && r.Ss) ? new QrBits[QP_EOB_MAX] : nullptr;
+  int be_bits = 0;
+  auto flush = [&]() {                               // emit_eobrun
+    if (!eobrun) return;
+    qp_eobrun(eobrun, tbl[0], s);
+    if (be)
+      for (int i = 0; i < eobrun; ++i) qr_put_bits(s, be[i]);
+    eobrun = 0;
+    be_bits = 0;
+  };
   const int rim = (ri && ri < g.mcus) ? ri : 0;
   for (int b = 0; b < g.nblocks; ++b) {
     const int m = b / g.bpm;
     if (rim && b > 0 && b % g.bpm == 0 && m % rim == 0) {
-      if (eobrun) qp_eobrun(eobrun, tbl[0], s);
-      eobrun = 0;
+      flush();
       boundary(m / rim - 1);
     }
     int c, prev;
     const int16_t* v = qp_block_at(g, A, b, rim, &c, &prev);
     if (r.Ss == 0) {
       const int cur = v ? v[0] : prev;
-      flags |= qp_dc_first((cur >> r.Al) - (prev >> r.Al), tbl[c], s);
+      if (r.Ah) qr_dc_refine(cur, r.Al, s);
+      else flags |= qp_dc_first((cur >> r.Al) - (prev >> r.Al), tbl[c], s);
       continue;
     }
     static const int16_t zero[64] = {0};
     if (!v) v = zero;
+    if (r.Ah) {
+      QrNullSink none;
+      QrBits tail;
+      const uint32_t f = qr_ac_refine(v, r.Ss, r.Se, r.Al, tbl[0], none, &tail);
+      if (f & QP_F_WRITES) {                         // (its first symbol, 0xF0 or a new coefficient, is preceded by the run)
+        flush();
+        qr_ac_refine(v, r.Ss, r.Se, r.Al, tbl[0], s, &tail);
+      }
+      if (f & QP_F_ENDZ) {
+        be[eobrun++] = tail;
+        be_bits += tail.n;
+        if (eobrun == QP_EOB_MAX || be_bits > QR_CORR_MAX) flush();
+      }
+      continue;
+    }
     const uint32_t f = qp_ac_flags(v, r.Ss, r.Se, r.Al);
     if (f & QP_F_WRITES) {
-      if (eobrun) qp_eobrun(eobrun, tbl[0], s);
-      eobrun = 0;
+      flush();
       flags |= qp_ac_first(v, r.Ss, r.Se, r.Al, tbl[0], s);
     }
     if (f & QP_F_ENDZ)
-      if (++eobrun == QP_EOB_MAX) {
-        qp_eobrun(eobrun, tbl[0], s);
-        eobrun = 0;
-      }
+      if (++eobrun == QP_EOB_MAX) flush();
   }
-  if (eobrun) qp_eobrun(eobrun, tbl[0], s);
+  flush();
+  delete[] be;
   return flags;
 }
 
@@ -404,6 +541,13 @@ struct QpScan {
   uint64_t off_wghead;             // int32[nwg]: the last head among a workgroup's blocks, -1: none
   uint64_t off_wgcarry;            // int32[nwg]: the last head in front of the workgroup
   uint64_t off_eob;                // uint16[nwg * 256]: the run piece that ends at each block
+  // refinement scans (Ah > 0).  An AC refinement scan keeps in off_flags QP_F_* | tail bits << 2, in off_wghead the sum
+  // of each workgroup's cut weights, in off_wgcarry their exclusive scan, in off_eob the piece that STARTS at each block
+  // if one does
+  int32_t Ah, pad;
+  uint64_t off_w;                  // uint32[nwg * 256]: exclusive scan of the cut weights inside the workgroup
+  uint64_t off_jump[2];            // int32[nwg * 256] each: where the piece after the one that starts here starts
+  uint64_t off_reach;              // uint8[nwg * 256]: a piece starts here
 };
 struct QpJob {
   int32_t sj0, nscans;             // its scan jobs

@@ -1,4 +1,4 @@
-// qs_encode_prog_job.cpp -- progressive files (spectral selection) of the flat C ABI (include/jpegqs_hip.h):
+// qs_encode_prog_job.cpp -- progressive files (spectral selection, refinement scans behind a flag) of the flat C ABI (include/jpegqs_hip.h):
 // qs_hip_encode_progressive_device_batch_info / _prepare / _files.  DESIGN.md section 17.
 //
 // A job with a script of n scans becomes n scan jobs: QsEncJob descriptors with the scan's own geometry (csrc/
@@ -20,7 +20,8 @@
 #include <unordered_map>
 
 int qs_enc_describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, const char* who);   // qs_encode_job.cpp
-void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArgs& h, int wgs, int swgs, hipStream_t s);
+void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArgs& h, int wgs, int swgs, int refine,
+                           hipStream_t s);
 void qs_launch_encode_prog_stuff(const QsEncArgs& a, int swgs, hipStream_t s);
 void qs_launch_encode_prog_begin(const QpJobArgs& a, hipStream_t s);
 void qs_launch_encode_prog_frame(const QpJobArgs& a, hipStream_t s);
@@ -30,6 +31,8 @@ static_assert(sizeof(qs_hip_encode_scan) == sizeof(QpScanRec), "qs_hip_encode_sc
 static_assert(QS_HIP_MAX_SCANS == QP_MAX_SCANS, "one limit");
 static_assert(sizeof(QpJobArgs) <= 4096, "kernel arguments: 4 KiB at most");
 static_assert(QP_MAXBITS <= 0xffff, "a block's bits travel as uint16");
+static_assert(QR_AC_MAXBITS(1, 63) <= QP_MAXBITS, "the emit kernel's LDS image holds a refinement scan's blocks");
+static_assert(QS_HIP_PROG_REFINE == 1, "the one flag");
 
 namespace {
 
@@ -39,6 +42,7 @@ struct Plan {
   std::vector<QpScan> X;
   std::vector<QpJob> Q;            // per job
   std::vector<QsEncJob> full;      // per job: the frame's geometry the plan was made for
+  std::vector<int> refine;         // per chunk of scan jobs: -1 without a refinement scan, else its rounds of qr_hop
   std::vector<uint8_t> mids;       // the DRI / SOS bytes, and where they go in the workspace
   uint64_t off_mids = 0, off_x = 0, off_q = 0;
   uint64_t total = 0;
@@ -88,6 +92,7 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
   for (int i = 0; i < njobs; ++i) {
     const qs_hip_encode_prog_opts* o = opts[i];
     if (!o || !o->scans) return qs_fail(QS_HIP_EINVAL, "%s: job %d has no script", who, i);
+    if (o->flags & ~QS_HIP_PROG_REFINE) return qs_fail(QS_HIP_EINVAL, "%s: job %d: flags %#x", who, i, (unsigned)o->flags);
     QsEncJob full;
     if (int r = qs_enc_describe(jobs[i], &full, nullptr, false, Who(who, i).s)) return r;
     const int nc = jobs[i]->ncomp;
@@ -97,6 +102,12 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
     switch (qp_validate_script(recs, o->nscans, nc, &bad, &why)) {
       case QP_SCRIPT_OK: break;
       case QP_SCRIPT_REFINE:
+        if (o->flags & QS_HIP_PROG_REFINE) {
+          if (o->nscans > QP_MAX_SCANS)
+            return qs_fail(QS_HIP_ENOTSUP, "%s: job %d: a valid script of %d scans; at most %d are written", who, i, o->nscans,
+                           QP_MAX_SCANS);
+          break;
+        }
         return qs_fail(QS_HIP_ENOTSUP, "%s: job %d, scan %d: %s: refinement scans are not implemented", who, i, bad, why);
       case QP_SCRIPT_SEQUENTIAL:
         return qs_fail(QS_HIP_ENOTSUP, "%s: job %d, scan %d: %s is not a progressive file", who, i, bad, why);
@@ -132,6 +143,7 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
       X.Ss = r.Ss;
       X.Se = r.Se;
       X.Al = r.Al;
+      X.Ah = r.Ah;
       X.job = i;
       uint8_t sos[QP_MID_MAX];
       int n = 0;
@@ -143,20 +155,20 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
       for (int c = 0; c < r.ncomp; ++c) {
         const int tb = full.tbl[r.comp[c]];
         J.tbl[c] = tb;
-        // jcmarker.c emit_sos: a DC scan names no AC table, an AC scan no DC table
+        // jcmarker.c emit_sos: a DC scan names no AC table, an AC scan no DC table, a DC refinement no table at all
         sos[n++] = (uint8_t)ids[r.comp[c]];
-        sos[n++] = (uint8_t)(r.Ss == 0 ? tb << 4 : tb);
+        sos[n++] = (uint8_t)(r.Ss == 0 ? (r.Ah ? 0 : tb << 4) : tb);
         const int w = (r.Ss == 0 ? 0 : 2) + tb;                      // each table once, in component order
         bool sent = false;
         for (int t = 0; t < X.ntab; ++t) sent |= X.tab[t] == w;
-        if (!sent) X.tab[X.ntab++] = w;
+        if (!sent && !(r.Ss == 0 && r.Ah)) X.tab[X.ntab++] = w;          // (a DC refinement has no symbols: no DHT)
       }
       X.actb = J.tbl[0];
       sos[n++] = (uint8_t)r.Ss;
       sos[n++] = (uint8_t)r.Se;
       sos[n++] = (uint8_t)((r.Ah << 4) | r.Al);
       uint64_t nint = 1;
-      int nblocks = 0;
+      int nblocks = 0, rounds = r.Ah ? 0 : -1;
       for (int v = 0; v < (full.two ? 2 : 1); ++v) {
         int detail = 0;
         if (qp_scan_geometry(full.g[v], r, &J.g[v], &detail) != QS_GEOM_OK)
@@ -168,6 +180,15 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
         J.ri[v] = ri >= g.mcus ? 0 : (int)ri;                        // (one interval covers the scan: no marker)
         if (J.ri[v]) nint = std::max<uint64_t>(nint, (uint64_t)ceil_div(g.mcus, J.ri[v]));
         nblocks = std::max(nblocks, g.nblocks);
+        if (r.Ah && r.Ss) {
+          // a run stays inside a restart interval and cuts a piece every QR_PIECE_MIN blocks at the soonest: after k rounds
+          // of qr_hop every piece start less than 2^k pieces behind the run's start is marked
+          const long long per = (long long)(J.ri[v] ? J.ri[v] : g.mcus) * g.bpm;
+          const long long pieces = ceil_div(std::min<long long>(per, g.nblocks), (long long)QR_PIECE_MIN);
+          int k = 0;
+          while ((1LL << k) < pieces) ++k;
+          rounds = std::max(rounds, k);
+        }
         // jcmarker.c write_scan_header: DRI when the interval differs from the last one written
         mid_at.push_back(P.mids.size());
         if ((int)ri != last_dri[v]) {
@@ -184,12 +205,15 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
         }
       }
       if (!full.two) mid_at.push_back(P.mids.size());
-      const uint64_t mb = r.Ss == 0 ? QP_DC_MAXBITS : QP_AC_MAXBITS(r.Ss, r.Se);
+      const uint64_t mb = r.Ah ? (r.Ss == 0 ? QR_DC_MAXBITS : QR_AC_MAXBITS(r.Ss, r.Se))
+                               : (r.Ss == 0 ? QP_DC_MAXBITS : QP_AC_MAXBITS(r.Ss, r.Se));
       maxbits.push_back(mb);
       if (per_job)   // every byte stuffed; per interval end a pad byte that may be stuffed and the marker; the markers
         per_job[i].max_body_bytes += 2 * (((uint64_t)nblocks * mb + 7) / 8 + 1) + 4 * (nint - 1) + 2 * (21 + 256) + QP_MID_MAX;
       J.nwg = ceil_div(nblocks, QS_ENC_WG);
       nints.push_back(nint);
+      if (P.D.size() % QS_ENC_CHUNK == 0) P.refine.push_back(-1);
+      P.refine.back() = std::max(P.refine.back(), rounds);
       P.D.push_back(J);
       P.X.push_back(X);
     }
@@ -231,6 +255,12 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
     X.off_wghead = L.take((uint64_t)J.nwg * 4);
     X.off_wgcarry = L.take((uint64_t)J.nwg * 4);
     X.off_eob = L.take(slots * 2);
+    if (X.Ah && X.Ss) {
+      X.off_w = L.take(slots * 4);
+      X.off_jump[0] = L.take(slots * 4);
+      X.off_jump[1] = L.take(slots * 4);
+      X.off_reach = L.take(slots);
+    }
     X.off_mid[0] = P.off_mids + mid_at[2 * j];
     X.off_mid[1] = P.off_mids + mid_at[2 * j + 1];
   }
@@ -404,7 +434,7 @@ extern "C" int qs_hip_encode_progressive_device_batch_files(qs_hip_job* const* j
       h.n = a.n;
       h.optimize = 1;
       const QsEncJob& last = P.D[j0 + a.n - 1];
-      qs_launch_encode_prog(a, d_scans + j0, h, last.wg0 + last.nwg, last.swg0 + last.nswg, s);
+      qs_launch_encode_prog(a, d_scans + j0, h, last.wg0 + last.nwg, last.swg0 + last.nswg, P.refine[j0 / QS_ENC_CHUNK], s);
     }
     for (int j0 = 0; j0 < njobs; j0 += QS_ENC_CHUNK) qs_launch_encode_prog_frame(job_args(j0), s);
     for (size_t j0 = 0; j0 < nsj; j0 += QS_ENC_CHUNK) {

@@ -40,7 +40,10 @@ struct QeShared {
 };
 
 // exclusive scan over the workgroup's 256 lanes; *total = the sum
-__device__ uint32_t qe_exscan(uint32_t v, uint32_t* sc, uint32_t* total) {
+// (this and the three helpers below are inlined by force: the compiler stops inlining into a kernel of more than 1100
+// basic blocks, which the AC refinement's emit kernel is, and a helper that is called takes the kernel's arguments by
+// address -- a copy of all of them in scratch)
+__device__ __forceinline__ uint32_t qe_exscan(uint32_t v, uint32_t* sc, uint32_t* total) {
   const int t = threadIdx.x;
   sc[t] = v;
   __syncthreads();
@@ -58,19 +61,19 @@ __device__ uint32_t qe_exscan(uint32_t v, uint32_t* sc, uint32_t* total) {
 
 // which job of the chunk owns workgroup `wg` (wg0 / nwg or swg0 / nswg: STUFF)
 template <bool STUFF>
-__device__ int qe_find_job(const QsEncArgs& a, int wg) {
+__device__ __forceinline__ int qe_find_job(const QsEncArgs& a, int wg) {
   int k = 0;
   for (int i = 1; i < a.n; ++i)
     if (wg >= (STUFF ? a.swg0[i] : a.wg0[i])) k = i;
   return k;
 }
 
-__device__ int qe_variant(const QsEncArgs& a, const QsEncJob& J, int k) {
+__device__ __forceinline__ int qe_variant(const QsEncArgs& a, const QsEncJob& J, int k) {
   return (J.two && a.d_stop && a.d_stop[a.job0 + k] != 0) ? 1 : 0;
 }
 
 // geometry of the chosen variant, the job's addresses and its code tables into LDS
-__device__ void qe_stage(const QsEncArgs& a, const QsEncJob& J, int k, int variant, QeShared& S) {
+__device__ __forceinline__ void qe_stage(const QsEncArgs& a, const QsEncJob& J, int k, int variant, QeShared& S) {
   const int t = threadIdx.x;
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&J.g[variant]);
   if (t < (int)(sizeof(QsEncGeom) / 4)) reinterpret_cast<uint32_t*>(&S.g)[t] = src[t];

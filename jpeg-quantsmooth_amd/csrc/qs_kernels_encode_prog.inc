@@ -14,6 +14,15 @@
 //   qp_emit      qe_emit<true> with them
 //   qp_frame     per job: scan offsets from the scans' lengths, d_len, d_status, and every byte outside the segments
 //   qp_nofile    a workspace the run finds no prepare for: status 4
+// Refinement scans (Ah > 0, section 17.1) have kernels of their own, launched for a chunk that holds one; the Ah = 0
+// kernels above pass their scan jobs by, and the other way round:
+//   qr_flags     AC refinement: per block QP_F_* and the number of correction bits it leaves buffered (its tail)
+//   qr_wsum      per block its cut weight -- the tail, and QR_CORR_MAX + 1 where the next block is a head -- scanned
+//                inside the workgroup
+//   qr_wscan     one workgroup per scan job: the weights in front of each workgroup
+//   qr_next      per block, by binary search on the scanned weights: where a run piece that starts there ends
+//   qr_hop       pointer doubling from the run starts, one launch per round: marks where pieces do start
+//   qp_size / qp_emit <REFINE>   the DC and AC refinement coders; a piece's symbol is written by its FIRST block
 #include "qs_encode_prog.h"
 
 void qs_launch_huff_tables(const QsHuffArgs& a, hipStream_t s);   // qs_kernels_huff.hip
@@ -63,7 +72,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_flags(QsEncArgs a, const QpScan*
   const QsEncJob& J = a.jobs[k];
   const QpScan& X = xs[k];
   const int lw = wg - J.wg0;
-  if (lw >= J.nwg || X.Ss == 0) return;
+  if (lw >= J.nwg || X.Ss == 0 || X.Ah) return;
   const int variant = qe_variant(a, J, k);
   qe_stage(a, J, k, variant, S);
   const int b = lw * QS_ENC_WG + t;
@@ -85,7 +94,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_headscan(QsEncArgs a, const QpSc
   const int k = blockIdx.x, t = threadIdx.x;
   const QsEncJob& J = a.jobs[k];
   const QpScan& X = xs[k];
-  if (X.Ss == 0) return;
+  if (X.Ss == 0 || X.Ah) return;
   const int32_t* wghead = reinterpret_cast<const int32_t*>(a.ws + X.off_wghead);
   int32_t* wgcarry = reinterpret_cast<int32_t*>(a.ws + X.off_wgcarry);
   int carry = -1;
@@ -110,7 +119,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_runs(QsEncArgs a, const QpScan* 
   const QsEncJob& J = a.jobs[k];
   const QpScan& X = xs[k];
   const int lw = wg - J.wg0;
-  if (lw >= J.nwg || X.Ss == 0) return;
+  if (lw >= J.nwg || X.Ss == 0 || X.Ah) return;
   const int variant = qe_variant(a, J, k);
   const int nblocks = J.g[variant].nblocks, per = qp_per(J, variant);
   const uint8_t* flags = a.ws + X.off_flags;
@@ -127,6 +136,171 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_runs(QsEncArgs a, const QpScan* 
   reinterpret_cast<uint16_t*>(a.ws + X.off_eob)[b] = (uint16_t)eob;
 }
 
+// ---- refinement scans ----
+
+__device__ __forceinline__ void qr_raw(QeSizeSink& s, uint32_t, int nb) { s.bits += (uint32_t)nb; }
+__device__ __forceinline__ void qr_raw(QeHistSink&, uint32_t, int) {}
+__device__ __forceinline__ void qr_raw(QeEmitSink& s, uint32_t val, int nb) { s.raw(val, nb); }
+// the coder's sinks with raw(): bits without a symbol
+template <class Base>
+struct QrSink {
+  Base& base;
+  __device__ __forceinline__ void ac(int tb, int sym, uint32_t bits, int nb) { base.ac(tb, sym, bits, nb); }
+  __device__ __forceinline__ void raw(uint32_t val, int nb) { qr_raw(base, val, nb); }
+};
+
+// the DC libjpeg sees at scan block b: a dummy block repeats the one before it (qe_dc)
+__device__ __forceinline__ int qr_dc(const QeShared& S, int b) {
+  const QsEncGeom& g = S.g;
+  const int m = b / g.bpm, k = b - m * g.bpm;
+  int c = 0;
+  for (int ci = 1; ci < g.ncomp; ++ci)
+    if (k >= g.first[ci]) c = ci;
+  return qe_dc(S, m, c, k - g.first[c]);
+}
+
+// this workgroup's place in an AC refinement scan job of the chunk: false when it has none
+struct QrAt {
+  int k, lw, variant, nblocks, per;
+};
+__device__ __forceinline__ bool qr_at(const QsEncArgs& a, const QpScan* xs, QrAt& q) {
+  q.k = qe_find_job<false>(a, blockIdx.x);
+  const QsEncJob& J = a.jobs[q.k];
+  const QpScan& X = xs[q.k];
+  q.lw = (int)blockIdx.x - J.wg0;
+  if (q.lw >= J.nwg || X.Ss == 0 || !X.Ah) return false;
+  q.variant = qe_variant(a, J, q.k);
+  q.nblocks = J.g[q.variant].nblocks;
+  q.per = qp_per(J, q.variant);
+  return true;
+}
+
+__global__ void __launch_bounds__(QS_ENC_WG) qr_flags(QsEncArgs a, const QpScan* xs) {
+  __shared__ QeShared S;
+  QrAt q;
+  if (!qr_at(a, xs, q)) return;
+  const QsEncJob& J = a.jobs[q.k];
+  const QpScan& X = xs[q.k];
+  qe_stage(a, J, q.k, q.variant, S);
+  const int b = q.lw * QS_ENC_WG + threadIdx.x;
+  uint32_t f = 0;
+  if (b < q.nblocks) {
+    QeBlock B;
+    qe_load(S, J, b, 0, B);
+    QrNullSink none;
+    QrBits tail;
+    f = qr_ac_refine(B.v, X.Ss, X.Se, X.Al, 0, none, &tail);
+    f |= (uint32_t)tail.n << 2;
+  }
+  (a.ws + X.off_flags)[b] = (uint8_t)f;
+}
+
+// a head: a block that writes or starts a restart interval; no piece runs into it
+__device__ __forceinline__ bool qr_head(const uint8_t* flags, int b, int per) {
+  return (flags[b] & QP_F_WRITES) || b % per == 0;
+}
+
+__global__ void __launch_bounds__(QS_ENC_WG) qr_wsum(QsEncArgs a, const QpScan* xs) {
+  __shared__ uint32_t sc[QS_ENC_WG];
+  QrAt q;
+  if (!qr_at(a, xs, q)) return;
+  const QpScan& X = xs[q.k];
+  const uint8_t* flags = a.ws + X.off_flags;
+  const int b = q.lw * QS_ENC_WG + threadIdx.x;
+  uint32_t w = 0;
+  if (b < q.nblocks) {
+    const uint32_t f = flags[b];
+    if (f & QP_F_ENDZ) w = f >> 2;
+    if (b + 1 < q.nblocks && qr_head(flags, b + 1, q.per)) w += QR_CORR_MAX + 1;   // any piece that reaches b ends there
+  }
+  uint32_t total;
+  const uint32_t ex = qe_exscan(w, sc, &total);
+  reinterpret_cast<uint32_t*>(a.ws + X.off_w)[b] = ex;
+  if (threadIdx.x == 0) reinterpret_cast<uint32_t*>(a.ws + X.off_wghead)[q.lw] = total;
+}
+
+// (sums modulo 2^32: qr_next takes differences over at most QP_EOB_MAX blocks, which are far below that)
+__global__ void __launch_bounds__(QS_ENC_WG) qr_wscan(QsEncArgs a, const QpScan* xs) {
+  __shared__ uint32_t sc[QS_ENC_WG];
+  const int k = blockIdx.x, t = threadIdx.x;
+  const QsEncJob& J = a.jobs[k];
+  const QpScan& X = xs[k];
+  if (X.Ss == 0 || !X.Ah) return;
+  const uint32_t* wsum = reinterpret_cast<const uint32_t*>(a.ws + X.off_wghead);
+  uint32_t* woff = reinterpret_cast<uint32_t*>(a.ws + X.off_wgcarry);
+  uint32_t carry = 0;
+  for (int base = 0; base < J.nwg; base += QS_ENC_WG) {
+    const int i = base + t;
+    uint32_t total;
+    const uint32_t ex = qe_exscan(i < J.nwg ? wsum[i] : 0, sc, &total);
+    if (i < J.nwg) woff[i] = carry + ex;
+    carry += total;
+  }
+}
+
+// A piece that starts at block b takes blocks until the EOB run reaches QP_EOB_MAX or the buffered bits pass QR_CORR_MAX
+// (jchuff.c: the check follows the block that was added), and never runs into a head: the first j >= b whose weights
+// from b on pass QR_CORR_MAX, at most QP_EOB_MAX blocks on.  The search takes 15 steps whatever the data.
+__global__ void __launch_bounds__(QS_ENC_WG) qr_next(QsEncArgs a, const QpScan* xs) {
+  QrAt q;
+  if (!qr_at(a, xs, q)) return;
+  const QpScan& X = xs[q.k];
+  const uint8_t* flags = a.ws + X.off_flags;
+  const uint32_t* W = reinterpret_cast<const uint32_t*>(a.ws + X.off_w);
+  const uint32_t* woff = reinterpret_cast<const uint32_t*>(a.ws + X.off_wgcarry);
+  const int b = q.lw * QS_ENC_WG + threadIdx.x;
+  int jump = b, len = 0, start = 0;
+  if (b < q.nblocks && (flags[b] & QP_F_ENDZ)) {
+    const uint32_t w0 = W[b] + woff[b / QS_ENC_WG];
+    int lo = b, hi = min(b + QP_EOB_MAX - 1, q.nblocks - 1);
+    for (int it = 0; it < 15; ++it)
+      if (lo < hi) {
+        const int mid = (lo + hi) >> 1;             // (mid + 1 <= hi: a block of the scan)
+        if (W[mid + 1] + woff[(mid + 1) / QS_ENC_WG] - w0 > QR_CORR_MAX) hi = mid;
+        else lo = mid + 1;
+      }
+    len = lo - b + 1;
+    const int nx = lo + 1;
+    if (nx < q.nblocks && !qr_head(flags, nx, q.per)) jump = nx;   // (else the run ends with this piece: it points at itself)
+    // a run starts at a head that leaves a tail, or behind one that leaves none (every other block leaves one)
+    start = qr_head(flags, b, q.per) || !(flags[b - 1] & QP_F_ENDZ);
+  }
+  if (b < q.nblocks) {
+    reinterpret_cast<int32_t*>(a.ws + X.off_jump[0])[b] = jump;
+    reinterpret_cast<uint16_t*>(a.ws + X.off_eob)[b] = (uint16_t)len;
+    (a.ws + X.off_reach)[b] = (uint8_t)start;
+  }
+}
+
+// Round `round`: in[b] is 2^round pieces on from b.  Every marked block marks in[b], then the distance doubles.  A block
+// marked in this same round may or may not be seen: whatever it marks is a piece start too, 2^round pieces on from one
+__global__ void __launch_bounds__(QS_ENC_WG) qr_hop(QsEncArgs a, const QpScan* xs, int round) {
+  QrAt q;
+  if (!qr_at(a, xs, q)) return;
+  const QpScan& X = xs[q.k];
+  const int32_t* in = reinterpret_cast<const int32_t*>(a.ws + X.off_jump[round & 1]);
+  int32_t* out = reinterpret_cast<int32_t*>(a.ws + X.off_jump[(round & 1) ^ 1]);
+  uint8_t* reach = a.ws + X.off_reach;
+  const int b = q.lw * QS_ENC_WG + threadIdx.x;
+  if (b >= q.nblocks) return;
+  const int j = in[b];
+  out[b] = in[j];
+  if (j != b && reach[b]) reach[j] = 1;
+}
+
+template <class Sink>
+__device__ __forceinline__ uint32_t qr_encode(const uint8_t* ws, const QpScan& X, const QeShared& S, const QeBlock& B, int b,
+                                              Sink& base) {
+  QrSink<Sink> s{base};
+  if (X.Ss == 0) {
+    qr_dc_refine(qr_dc(S, b), X.Al, s);
+    return 0;
+  }
+  const int piece = (ws + X.off_reach)[b] ? reinterpret_cast<const uint16_t*>(ws + X.off_eob)[b] : 0;
+  qr_ac_block(B.v, X.Ss, X.Se, X.Al, X.actb, piece, s);
+  return 0;                                          // (no range check in a refinement scan)
+}
+
 // the block's own symbols and the run piece behind them, on any sink
 template <class Sink>
 __device__ __forceinline__ uint32_t qp_encode(const QsEncArgs& a, const QpScan& X, const QeBlock& B, int b, Sink& s) {
@@ -141,7 +315,14 @@ __device__ __forceinline__ uint32_t qp_encode(const QsEncArgs& a, const QpScan& 
   return flags;
 }
 
-template <bool HIST>
+template <bool REFINE, class Sink>
+__device__ __forceinline__ uint32_t qp_code(const QsEncArgs& a, const QpScan& X, const QeShared& S, const QeBlock& B, int b,
+                                            Sink& s) {
+  if constexpr (REFINE) return qr_encode(a.ws, X, S, B, b, s);
+  else return qp_encode(a, X, B, b, s);
+}
+
+template <bool HIST, bool REFINE>
 __global__ void __launch_bounds__(QS_ENC_WG) qp_size(QsEncArgs a, const QpScan* xs) {
   __shared__ QeShared S;
   __shared__ uint32_t hist[HIST ? 4 * 257 : 1];
@@ -150,7 +331,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_size(QsEncArgs a, const QpScan* 
   const QsEncJob& J = a.jobs[k];
   const QpScan& X = xs[k];
   const int lw = wg - J.wg0;
-  if (lw >= J.nwg) return;
+  if (lw >= J.nwg || (X.Ah != 0) != REFINE) return;
   if (HIST)
     for (int i = t; i < 4 * 257; i += QS_ENC_WG) hist[i] = 0;
   const int variant = qe_variant(a, J, k);
@@ -159,13 +340,13 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_size(QsEncArgs a, const QpScan* 
   uint32_t bits = 0, flags = 0;
   if (b < S.g.nblocks) {
     QeBlock B;
-    qe_load(S, J, b, J.ri[variant], B);
+    if (!REFINE || X.Ss != 0) qe_load(S, J, b, J.ri[variant], B);   // (a DC refinement reads the DC alone: qr_dc)
     if (HIST) {
       QeHistSink s{hist};
-      flags = qp_encode(a, X, B, b, s);
+      flags = qp_code<REFINE>(a, X, S, B, b, s);
     } else {
       QeSizeSink s(S);
-      flags = qp_encode(a, X, B, b, s) | s.flags;
+      flags = qp_code<REFINE>(a, X, S, B, b, s) | s.flags;
       bits = s.bits;
     }
   }
@@ -187,6 +368,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_size(QsEncArgs a, const QpScan* 
   }
 }
 
+template <bool REFINE>
 __global__ void __launch_bounds__(QS_ENC_WG) qp_emit(QsEncArgs a, const QpScan* xs) {
   constexpr uint32_t LDS_WORDS = QP_LDS_WORDS;
   __shared__ QeShared S;
@@ -196,7 +378,7 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_emit(QsEncArgs a, const QpScan* 
   const QsEncJob& J = a.jobs[k];
   const QpScan& X = xs[k];
   const int lw = wg - J.wg0;
-  if (lw >= J.nwg) return;
+  if (lw >= J.nwg || (X.Ah != 0) != REFINE) return;
   if (qe_state(a, J)->dead) return;
   uint32_t wgbits = reinterpret_cast<const uint32_t*>(a.ws + J.off_wgsum)[lw];
   if (wgbits == 0) return;
@@ -226,8 +408,8 @@ __global__ void __launch_bounds__(QS_ENC_WG) qp_emit(QsEncArgs a, const QpScan* 
     QeEmitSink s(S, words, lead + ex + shift, LDS_WORDS);
     if (mine) {
       QeBlock B;
-      qe_load(S, J, b, J.ri[variant], B);
-      qp_encode(a, X, B, b, s);
+      if (!REFINE || X.Ss != 0) qe_load(S, J, b, J.ri[variant], B);
+      qp_code<REFINE>(a, X, S, B, b, s);
     }
     if (pad) s.raw((1u << pad) - 1u, (int)pad);
     s.flush();
@@ -322,7 +504,10 @@ __global__ void __launch_bounds__(256) qp_frame(QpJobArgs a) {
 // The progressive run.  Per chunk of scan jobs (`a`, with d_counts / codes / tstatus / d_len / d_status / d_stop set to
 // the scratch arrays): everything up to each scan's stuffed length; qs_launch_encode_prog_stuff stores the segments once
 // qp_frame has placed them.
-void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArgs& h, int wgs, int swgs, hipStream_t s) {
+// refine: -1 when the chunk holds no refinement scan, else the rounds of qr_hop its longest run of an AC refinement scan
+// needs (from the geometry: qp_refine_rounds)
+void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArgs& h, int wgs, int swgs, int refine,
+                           hipStream_t s) {
   const dim3 lanes(QS_ENC_WG);
   QsEncArgs hist = a;                                // the histogram pass: counts, and no code words yet
   hist.codes = nullptr;
@@ -332,14 +517,24 @@ void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArg
     hipLaunchKernelGGL(qp_flags, dim3(wgs), lanes, 0, s, a, xs);
     hipLaunchKernelGGL(qp_headscan, dim3(a.n), lanes, 0, s, a, xs);
     hipLaunchKernelGGL(qp_runs, dim3(wgs), lanes, 0, s, a, xs);
-    hipLaunchKernelGGL(qp_size<true>, dim3(wgs), lanes, 0, s, hist, xs);
+    hipLaunchKernelGGL((qp_size<true, false>), dim3(wgs), lanes, 0, s, hist, xs);
+  }
+  if (wgs > 0 && refine >= 0) {
+    hipLaunchKernelGGL(qr_flags, dim3(wgs), lanes, 0, s, a, xs);
+    hipLaunchKernelGGL(qr_wsum, dim3(wgs), lanes, 0, s, a, xs);
+    hipLaunchKernelGGL(qr_wscan, dim3(a.n), lanes, 0, s, a, xs);
+    hipLaunchKernelGGL(qr_next, dim3(wgs), lanes, 0, s, a, xs);
+    for (int r = 0; r < refine; ++r) hipLaunchKernelGGL(qr_hop, dim3(wgs), lanes, 0, s, a, xs, r);
+    hipLaunchKernelGGL((qp_size<true, true>), dim3(wgs), lanes, 0, s, hist, xs);
   }
   qs_launch_huff_tables(h, s);
   QsEncArgs code = a;
   code.d_counts = nullptr;
-  if (wgs > 0) hipLaunchKernelGGL(qp_size<false>, dim3(wgs), lanes, 0, s, code, xs);
+  if (wgs > 0) hipLaunchKernelGGL((qp_size<false, false>), dim3(wgs), lanes, 0, s, code, xs);
+  if (wgs > 0 && refine >= 0) hipLaunchKernelGGL((qp_size<false, true>), dim3(wgs), lanes, 0, s, code, xs);
   hipLaunchKernelGGL(qe_scan_bits<true>, dim3(a.n), lanes, 0, s, code);
-  if (wgs > 0) hipLaunchKernelGGL(qp_emit, dim3(wgs), lanes, 0, s, code, xs);
+  if (wgs > 0) hipLaunchKernelGGL(qp_emit<false>, dim3(wgs), lanes, 0, s, code, xs);
+  if (wgs > 0 && refine >= 0) hipLaunchKernelGGL(qp_emit<true>, dim3(wgs), lanes, 0, s, code, xs);
   if (swgs > 0) hipLaunchKernelGGL(qe_ff_count<true>, dim3(swgs), lanes, 0, s, code);
   hipLaunchKernelGGL(qe_ff_scan, dim3(a.n), lanes, 0, s, code);
 }

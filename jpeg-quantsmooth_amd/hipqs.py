@@ -135,6 +135,7 @@ class EncodeOpts(C.Structure):
 
 
 MAX_SCANS = 256                  # QS_HIP_MAX_SCANS: scans of one progressive script
+PROG_REFINE = 1                  # QS_HIP_PROG_REFINE: qs_hip_encode_prog_opts.flags, refinement scans are written
 
 
 class EncodeScan(C.Structure):
@@ -146,7 +147,7 @@ class EncodeScan(C.Structure):
 class EncodeProgOpts(C.Structure):
     """qs_hip_encode_prog_opts: the script and the restart settings of one job of the progressive run"""
     _fields_ = [("scans", C.POINTER(EncodeScan)), ("nscans", C.c_int32), ("restart_interval", C.c_int32),
-                ("restart_in_rows", C.c_int32), ("component_id", C.c_int32 * MAXC)]
+                ("restart_in_rows", C.c_int32), ("component_id", C.c_int32 * MAXC), ("flags", C.c_int32)]
 
 
 class EncodeProgInfo(C.Structure):
@@ -809,9 +810,10 @@ class HipQS:
 
     # -- progressive files (spectral selection) ---------------------------------------------
     @staticmethod
-    def prog_opts(script, restart_interval=0, restart_in_rows=0, component_id=None) -> EncodeProgOpts:
-        """a qs_hip_encode_prog_opts: script = [(component indices, Ss, Se, Ah, Al)] (jpeg_file.spectral_script);
-        component_id None: jpeg_set_colorspace's ids"""
+    def prog_opts(script, restart_interval=0, restart_in_rows=0, component_id=None, refinement=False) -> EncodeProgOpts:
+        """a qs_hip_encode_prog_opts: script = [(component indices, Ss, Se, Ah, Al)] (jpeg_file.spectral_script,
+        jpeg_file.simple_progression); component_id None: jpeg_set_colorspace's ids; refinement: QS_HIP_PROG_REFINE, without
+        which a script with an Ah > 0 scan is refused"""
         script = list(script)
         arr = (EncodeScan * max(1, len(script)))()
         for r, (comps, ss, se, ah, al) in zip(arr, script):
@@ -823,6 +825,7 @@ class HipQS:
         o = EncodeProgOpts(C.cast(arr, C.POINTER(EncodeScan)), len(script), int(restart_interval), int(restart_in_rows))
         for k, v in enumerate(component_id or ()):
             o.component_id[k] = int(v)
+        o.flags = PROG_REFINE if refinement else 0
         o._scans = arr                                                  # (kept alive with the record)
         return o
 

@@ -116,6 +116,23 @@ def spectral_script(ncomp: int):
     return out
 
 
+def simple_progression(ncomp: int, colorspace: int):
+    """libjpeg 9's jpeg_simple_progression (jcparam.c), the script of cjpeg -progressive: for YCbCr (colorspace 3) with three
+    components its ten scans, for every other frame the all-purpose script of 2 + 4 * ncomp scans.  Four respectively
+    1 + 2 * ncomp of them are refinement scans (Ah > 0)"""
+    allc = range(ncomp)                                                # (ncomp <= 4: one DC scan carries all components)
+    if ncomp == 3 and colorspace == 3:
+        return [scan(allc, 0, 0, 0, 1), scan([0], 1, 5, 0, 2), scan([2], 1, 63, 0, 1), scan([1], 1, 63, 0, 1),
+                scan([0], 6, 63, 0, 2), scan([0], 1, 63, 2, 1), scan(allc, 0, 0, 1, 0), scan([2], 1, 63, 1, 0),
+                scan([1], 1, 63, 1, 0), scan([0], 1, 63, 1, 0)]
+    out = [scan(allc, 0, 0, 0, 1)]
+    out += [scan([c], 1, 5, 0, 2) for c in allc] + [scan([c], 6, 63, 0, 2) for c in allc]
+    out += [scan([c], 1, 63, 2, 1) for c in allc]
+    out += [scan(allc, 0, 0, 1, 0)]
+    out += [scan([c], 1, 63, 1, 0) for c in allc]
+    return out
+
+
 class ScriptError(ValueError):
     """a scan script libjpeg's validate_script refuses (or takes as sequential); .scan: where, or None"""
 

@@ -682,7 +682,7 @@ def _file_frames(images, result, opts, optimize, huffman, who):
 
 
 def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=None, workspace: Workspace | None = None,
-                      restart_interval=None, restart_in_rows=None, scans=None) -> dict:
+                      restart_interval=None, restart_in_rows=None, scans=None, refinement=False) -> dict:
     """Complete baseline JPEG files in device memory, byte for byte what libjpeg 9 writes for jpeg_write_coefficients
     (encode_batch's files), on the current stream and without host synchronisation: qs_hip_encode_device_batch_files.
 
@@ -704,18 +704,21 @@ def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=
     jpeg_file.spectral_script makes it, one for all images or a list of scripts, one per image -- for the PROGRESSIVE file
     libjpeg writes with cinfo.scan_info set (qs_hip_encode_progressive_device_batch_files): SOF2, every scan with its own
     optimal tables in front of it.  It requires optimize=True (libjpeg forces it) and every scan with Ah = 0; `tables` is
-    then None.  The restart keywords count in each scan's own MCUs."""
+    then None.  The restart keywords count in each scan's own MCUs.
+    refinement=True: scripts with successive-approximation refinement scans (Ah > 0) are written too, such as
+    jpeg_file.simple_progression, the script of cjpeg -progressive."""
     if scans is not None:
         if not optimize or huffman is not None:
             raise ValueError("encode_file_batch: a scan script requires optimize=True and no huffman (progressive mode forces "
                              "optimal tables)")
         return _encode_progressive_batch(images, result, scans, outs, workspace, "encode_file_batch",
-                                         _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"))
+                                         _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"),
+                                         bool(refinement))
     return _encode_file_batch(images, result, optimize, huffman, outs, workspace, "encode_file_batch",
                               _restart_opts(restart_interval, restart_in_rows, len(images), "encode_file_batch"))
 
 
-def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts):
+def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts, refinement=False):
     import torch
     from . import jpeg_file
     jobs, dev, stop = _encode_jobs(images, result, who, torch)
@@ -729,9 +732,10 @@ def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts)
     if len(per_image) != n:
         raise ValueError(f"{who}: one scan script per image")
     for i, (script, im) in enumerate(zip(per_image, images)):
-        if not jpeg_file.validate_script(script, len(im["coefs"])):
+        if not jpeg_file.validate_script(script, len(im["coefs"])) and not refinement:
             raise ValueError(f"{who}: image {i}: the script holds refinement scans (Ah > 0), which are not implemented")
-    popts = [hip.prog_opts(script, *(opts[i] if opts is not None else (0, 0))) for i, script in enumerate(per_image)]
+    popts = [hip.prog_opts(script, *(opts[i] if opts is not None else (0, 0)), refinement=refinement)
+             for i, script in enumerate(per_image)]
     per, total, scratch_bytes = hip.encode_progressive_info(jobs, popts)
     heads = []                                                          # per image and geometry variant: SOI .. SOF2
     for i, im in enumerate(images):
@@ -747,7 +751,7 @@ def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts)
         if quants is None:
             raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
         heads.append([jpeg_file.compose_parts(quants, vh, vv, cs, tuple(im["image_size"]), progressive=True)[0] for vh, vv in variants])
-    key = ("progressive", tuple(tuple(map(tuple, s)) for s in per_image), tuple(opts or ()),
+    key = ("progressive", refinement, tuple(tuple(map(tuple, s)) for s in per_image), tuple(opts or ()),
            tuple(_key(job, 0, 0) for job in jobs), tuple(tuple(h) for h in heads), str(dev))
     if workspace is None:
         workspace = Workspace()
@@ -856,7 +860,7 @@ def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, 
 
 def encode_file(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, optimize=True,
                 huffman=None, out=None, workspace: Workspace | None = None, restart_interval=None, restart_in_rows=None,
-                scans=None) -> dict:
+                scans=None, refinement=False) -> dict:
     """encode_file_batch on one image -> dict(file, len, status, tables, workspace); len and status are device tensors of
     one element"""
     if scans is not None:
@@ -864,7 +868,8 @@ def encode_file(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, 
                                     image_size=image_size)],
                               result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
                               huffman=huffman, outs=None if out is None else [out], workspace=workspace,
-                              restart_interval=restart_interval, restart_in_rows=restart_in_rows, scans=list(scans))
+                              restart_interval=restart_interval, restart_in_rows=restart_in_rows, scans=list(scans),
+                              refinement=refinement)
         return dict(file=r["files"][0], len=r["len"], status=r["status"], tables=None, workspace=r["workspace"])
     r = _encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                                  image_size=image_size)],

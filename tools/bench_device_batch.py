@@ -35,6 +35,9 @@ unless the first file of each case is libjpeg's optimized file.
 baseline whole-file run with optimized tables on the same arrays in the same process, with the ratio of the two and the
 sizes of the progressive and the baseline-optimized files.  Exits non-zero unless the first file of each case is the
 file libjpeg writes with that script (tests/libjpeg9_encode_prog.c).
+--encode --progressive --script simple adds, per case, the run of jpeg_file.simple_progression (libjpeg's own script, four of
+its ten YCbCr scans refinement scans) next to the spectral run and the baseline run on the same arrays, the file sizes, and
+the time of the worst case of the refinement scans' run cutting (worst_case_last_bit_scan).
 
 --read times the device scan reader (torch_qs.read_batch) on the same three cases, on files the device coder wrote with
 --restart N / --restart-rows N: the upload of the file from pinned memory plus the read, and the read alone, next to the
@@ -56,7 +59,7 @@ route and the comparison, tests/libjpeg9_compress_fancy.c) and reports whether e
 mode's: the gray case must.
 
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode [--optimize-files | --progressive] | --read [--split] [--no-host] | --compress]
+                                       [--decode | --encode [--optimize-files | --progressive [--script simple]] | --read [--split] [--no-host] | --compress]
                                        [--restart N | --restart-rows N]
                                        [--downsampling box|dct] [--upsampling dct|triangle]"""
 import argparse
@@ -88,6 +91,9 @@ def main():
                     help="--encode: time the whole-file run with optimized tables next to the histogram run plus the plain run")
     ap.add_argument("--progressive", action="store_true",
                     help="--encode: time the progressive run (spectral selection) next to the baseline whole-file run")
+    ap.add_argument("--script", choices=["spectral", "simple"], default="spectral",
+                    help="--encode --progressive: simple also times jpeg_file.simple_progression (libjpeg's script, with "
+                         "refinement scans) on the same arrays, and the worst case of its run cutting")
     ap.add_argument("--read", action="store_true", help="time the device scan reader instead (needs --restart / --restart-rows)")
     ap.add_argument("--split", action="store_true",
                     help="--read: the split route (segments of an interval in parallel); works without a restart option")
@@ -514,6 +520,33 @@ def bench_encode_progressive(a):
         b_ms, b_all = med(baseline_run, 10)
         p_ms, p_all = med(progressive_run, 10)
         b2_ms, b2_all = med(baseline_run, 10)                        # (again, behind the other: the pair's own spread)
+        simple = None
+        if a.script == "simple":
+            # libjpeg's own script on the same arrays, in the same process; blocks read: the sum of the scans' blocks
+            sscript = jpeg_file.simple_progression(len(ims[0]["coefs"]), ims[0]["colorspace"])
+            wsim = torch_qs.Workspace()
+            rs = torch_qs.encode_file_batch(images, workspace=wsim, scans=sscript, refinement=True, **rst)
+            sfiles, slens = rs["files"], [int(v) for v in rs["len"].cpu().tolist()]
+            assert rs["status"].cpu().tolist() == [0] * len(images), "the default capacity did not hold the simple_progression file"
+
+            def simple_run():
+                torch_qs.encode_file_batch(images, outs=sfiles, workspace=wsim, scans=sscript, refinement=True, **rst)
+
+            s_ms, s_all = med(simple_run, 10)
+            p2_ms, p2_all = med(progressive_run, 10)
+
+            def blocks_read(sc):
+                return sum(int(np.prod(ims[0]["coefs"][c].shape[:2])) for comps, *_r in sc for c in comps)
+            simple = dict(scans=len(sscript), simple_ms=s_ms, simple_windows=s_all, spectral_again_ms=p2_ms,
+                          spectral_again_windows=p2_all, simple_over_spectral=round(s_ms / min(p_ms, p2_ms), 3),
+                          blocks_read_simple_over_spectral=round(blocks_read(sscript) / blocks_read(script), 3),
+                          simple_bytes=sum(slens), simple_over_spectral_bytes=round(sum(slens) / sum(plens), 4),
+                          simple_over_baseline_bytes=round(sum(slens) / sum(blens), 4))
+            with tempfile.TemporaryDirectory() as td:
+                from encode_prog_oracle import LibJpeg9EncProg
+                simple["identical"] = bool(LibJpeg9EncProg(Path(td)).write(dict(ims[0], quants=unit), sscript, a.restart or 0,
+                                                                           a.restart_rows or 0)
+                                           == sfiles[0][:slens[0]].cpu().numpy().tobytes())
         first = pfiles[0][:plens[0]].cpu().numpy().tobytes()
         row = dict(case=name, images=len(images), scans=len(script), progressive_ms=p_ms, progressive_windows=p_all,
                    baseline_optimized_ms=b_ms, baseline_windows=b_all, baseline_again_ms=b2_ms, baseline_again_windows=b2_all,
@@ -523,11 +556,43 @@ def bench_encode_progressive(a):
             from encode_prog_oracle import LibJpeg9EncProg
             row["identical"] = bool(LibJpeg9EncProg(Path(td)).write(dict(ims[0], quants=unit), script, a.restart or 0,
                                                                     a.restart_rows or 0) == first)
+        if simple is not None:
+            row["simple_progression"] = simple
         out["results"].append(row)
+    if a.script == "simple":
+        out["worst_case_last_bit_scan"] = worst_case_refinement(a, torch, torch_qs, dev, med)
     print(json.dumps(out), flush=True)
-    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    bad = [r["case"] for r in out["results"] if not r["identical"] or not r.get("simple_progression", {}).get("identical", True)]
     if bad:
         raise SystemExit(f"bench_device_batch --encode --progressive: {bad}: the file is not libjpeg's progressive file")
+
+
+def worst_case_refinement(a, torch, torch_qs, dev, med):
+    """8192 x 8192 gray with every AC coefficient +-2 or +-3: the last-bit scan of the band 1-63 writes no symbol of its
+    own, every block leaves 63 correction bits, and the whole scan is one EOB run that is cut every 15 blocks -- the worst
+    case of the run cutting.  The scan's time is the difference between the scripts with and without it; the AC scan that
+    sends the band first is the ordinary scan of the same size next to it"""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    coef = (rng.integers(2, 4, (1024, 1024, 64)) * rng.choice([-1, 1], (1024, 1024, 64))).astype(np.int16)
+    image = [dict(coefs=[torch.from_numpy(coef).to(dev)], quants=[np.ones(64, np.uint16)], hsamp=[1], vsamp=[1], colorspace=1,
+                  image_size=(8192, 8192))]
+    scripts = dict(dc=[((0,), 0, 0, 0, 0)], dc_ac=[((0,), 0, 0, 0, 0), ((0,), 1, 63, 0, 1)],
+                   dc_ac_refine=[((0,), 0, 0, 0, 0), ((0,), 1, 63, 0, 1), ((0,), 1, 63, 1, 0)])
+    ms = {}
+    for name, sc in scripts.items():
+        ws = torch_qs.Workspace()
+        r = torch_qs.encode_file_batch(image, workspace=ws, scans=sc, refinement=True)
+        assert r["status"].cpu().tolist() == [0], name
+        files = r["files"]
+
+        def run():
+            torch_qs.encode_file_batch(image, outs=files, workspace=ws, scans=sc, refinement=True)
+        ms[name], _all = med(run, 10)
+        ms[name + "_bytes"] = int(r["len"][0])
+    return dict(case="8192x8192_gray_all_nonzero", ms=ms, ac_first_scan_ms=round(ms["dc_ac"] - ms["dc"], 3),
+                last_bit_scan_ms=round(ms["dc_ac_refine"] - ms["dc_ac"], 3),
+                last_bit_over_ac_first=round((ms["dc_ac_refine"] - ms["dc_ac"]) / (ms["dc_ac"] - ms["dc"]), 3))
 
 
 def bench_read(a):
