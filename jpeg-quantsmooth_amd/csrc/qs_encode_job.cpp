@@ -7,22 +7,20 @@
 // around the segment (qs_kernels_huff.hip): it shares enqueue() with the plain run and keeps its
 // own arrays in the caller's scratch, never in the workspace.  qs_hip_huff_optimal[_device]: csrc/qs_huff.h.
 //
-// Workspace: the QsEncJob descriptors of the batch, then per job its scratch arrays (block code lengths, workgroup
-// sums and offsets, the unstuffed stream at its worst-case size, the stuffing counts, the restart intervals' offsets)
-// -- a function of the jobs' geometry and restart options alone; the code tables in the descriptors come from prepare's
-// `tables`.  The run calls have no options: every prepare notes, under the workspace's address, the batch size, which
-// launch chunks hold a restart job and how large the workspace must be (prepared()); the run looks that up.  A
-// workspace it does not find there runs as one without restart jobs, as every workspace did before there were options;
-// should its descriptors hold an interval after all, the kernels end those jobs with status 4.
+// Workspace: the QsEncJob descriptors of the batch, then per job the arrays of one coded scan (csrc/qs_encode_plan.h, with
+// the restart rule, the scratch and the registry of prepared workspaces) -- a function of the jobs' geometry and restart
+// options alone; the code tables in the descriptors come from prepare's `tables`.  The run calls describe the batch
+// again and take from the registry only the batch size, which launch chunks hold a restart job and how large the
+// workspace must be.  A workspace they do not find there runs as one without restart jobs, as every workspace did before
+// there were options; should its descriptors hold an interval after all, the kernels end those jobs with status 4.
 #include "qs_common.h"
 #include "qs_stage.h"
 #include "qs_encode.h"
 #include "qs_huff.h"
 #include "qs_encode_prog.h"
+#include "qs_encode_plan.h"
 
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
 void qs_launch_encode(const QsEncArgs& a, int wgs, int swgs, bool restart, hipStream_t s);
 void qs_launch_huff_optimal(const uint32_t* d_counts, int ntables, uint8_t* d_tables, int32_t* d_status, hipStream_t s);
@@ -165,44 +163,14 @@ int describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays,
   return QS_HIP_OK;
 }
 
-// jcmaster.c (per_scan_setup): restart_in_rows wins and is counted in the geometry's MCU rows, limited to 16 bits.
-// -> the interval the kernels work with: 0 where no marker is written (none asked for, or one interval covers the scan)
-int restart_interval(const qs_hip_encode_opts* o, const QsEncGeom& g) {
-  if (!o) return 0;
-  const long long ri = o->restart_in_rows > 0 ? std::min<long long>((long long)o->restart_in_rows * g.mcus_x, 65535)
-                                              : o->restart_interval;
-  return ri >= g.mcus ? 0 : (int)ri;
-}
-
-// what every prepare leaves for the run calls, by workspace address: the launch chunks that hold a restart job (empty:
-// none), and the workspace size the options need.  At most QS_ENC_PREPARED_MAX entries: the one prepared longest ago
-// goes first, and runs from then on as a workspace without restart jobs (status 4 for a job that has one) until it is
-// prepared again
-#define QS_ENC_PREPARED_MAX 4096
+// what every prepare leaves for the run calls: the launch chunks that hold a restart job (empty: none), and the workspace
+// size the options need.  A workspace that left the registry runs without restart jobs (status 4 for a job that has one)
 struct Prepared {
   int njobs;
   uint64_t total;
-  uint64_t age;
   std::vector<uint8_t> chunk_restart;
 };
-std::mutex g_prepared_mutex;
-uint64_t g_prepared_clock = 0;
-std::unordered_map<const void*, Prepared>& prepared() {
-  static std::unordered_map<const void*, Prepared> m;
-  return m;
-}
-void remember(const void* d_workspace, Prepared p) {
-  std::lock_guard<std::mutex> lock(g_prepared_mutex);
-  auto& m = prepared();
-  p.age = ++g_prepared_clock;
-  m[d_workspace] = std::move(p);
-  if (m.size() > QS_ENC_PREPARED_MAX) {
-    auto oldest = m.begin();
-    for (auto it = m.begin(); it != m.end(); ++it)
-      if (it->second.age < oldest->second.age) oldest = it;
-    m.erase(oldest);
-  }
-}
+QsPrepared<Prepared> g_prepared(4096);
 
 // the descriptors of a batch with their workspace layout; returns the workspace size in *total
 int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* const* opts, bool need_arrays,
@@ -221,57 +189,21 @@ int describe_all(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_opts* c
     if (i % QS_ENC_CHUNK == 0) wgs = swgs = 0;
     const int nblocks = std::max(J.g[0].nblocks, J.two ? J.g[1].nblocks : 0);
     const qs_hip_encode_opts* o = opts ? opts[i] : nullptr;
-    if (o && (o->restart_interval < 0 || o->restart_interval > 65535 || o->restart_in_rows < 0))
-      return qs_fail(QS_HIP_EINVAL, "%s: job %d: restart_interval %d (0 .. 65535), restart_in_rows %d (0 or more)", who, i,
-                     o->restart_interval, o->restart_in_rows);
+    if (o)
+      if (int r = qs_enc_check_restart(o->restart_interval, o->restart_in_rows, who, i)) return r;
     uint64_t nint = 1;                                              // restart intervals of the scan, at most
     for (int v = 0; v < (J.two ? 2 : 1); ++v) {
-      J.ri[v] = restart_interval(o, J.g[v]);
+      J.ri[v] = o ? qs_enc_restart(o->restart_interval, o->restart_in_rows, J.g[v]) : 0;
       if (J.ri[v]) nint = std::max<uint64_t>(nint, (uint64_t)ceil_div(J.g[v].mcus, J.ri[v]));
     }
-    J.nwg = ceil_div(nblocks, QS_ENC_WG);
-    J.wg0 = (int)wgs;
-    wgs += J.nwg;
-    const uint64_t slots = (uint64_t)J.nwg * QS_ENC_WG;
     // (the launch grid of the stuffing kernels does not depend on the options: the run calls do not see them)
-    const uint64_t plain_cap = align_up((slots * QS_ENC_MAXBITS + 7) / 8, 16) + 16;
-    J.raw_cap = plain_cap + align_up(nint - 1, 16);                 // less than a byte of padding per interval end
-    const uint64_t chunks = (J.raw_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK;
-    J.nswg = (int)std::min<uint64_t>((plain_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK, QS_ENC_SWG_MAX);
-    J.swg0 = (int)swgs;
-    swgs += J.nswg;
-    if (wgs > 0x7fffffffLL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
-    J.off_state = L.take(sizeof(QsEncState));
-    J.off_bits = L.take(slots * 2);
-    J.off_wgsum = L.take((uint64_t)J.nwg * 4);
-    J.off_wgoff = L.take((uint64_t)J.nwg * 8);
-    J.off_raw = L.take(J.raw_cap);
-    J.off_ffcnt = L.take(chunks * 4);
-    J.off_ffoff = L.take(chunks * 8);
-    J.off_rrel = L.take(nint * 4);
-    J.off_rd = L.take((nint + 1) * 8);
-    J.off_rp = L.take((nint + 1) * 8);
+    if (int r = qs_enc_scan_layout(L, J, wgs, swgs, nblocks, nint, QS_ENC_MAXBITS, false, who)) return r;
     // every byte stuffed; per interval end a pad byte that may be stuffed, and the two bytes of the marker
     if (info) info[i].max_segment_bytes = 2 * (((uint64_t)nblocks * QS_ENC_MAXBITS + 7) / 8) + 4 * (nint - 1);
   }
   *total = L.total;
   return QS_HIP_OK;
 }
-
-// the whole-file run's scratch (qs_hip_encode_files_scratch_bytes): byte offsets of its arrays
-struct FilesScratch {
-  uint64_t counts, codes, tables, prefix, tstatus, total;
-  explicit FilesScratch(int njobs) {
-    const uint64_t n = (uint64_t)std::max(njobs, 0);
-    Layout L;
-    counts = L.take(n * 4 * 257 * 4);
-    codes = L.take(n * QS_ENC_CODES * 4);
-    tables = L.take(n * QS_ENC_TABLES_BYTES);
-    prefix = L.take(n * 8);
-    tstatus = L.take(n * 4);
-    total = L.total;
-  }
-};
 
 // what the whole-file run adds to a run (null: the plain run)
 struct FilesRun {
@@ -298,7 +230,7 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
       P[(size_t)i].cap = out_capacity[i];
     }
   }
-  const FilesScratch FS(njobs);
+  const QsEncScratch FS((uint64_t)njobs);               // (qs_hip_encode_files_scratch_bytes)
   if (F) {
     if (F->frames)
       for (int i = 0; i < njobs; ++i) {
@@ -318,19 +250,13 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
   }
   if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
   // the kernels to launch follow what prepare wrote at this address.  An address not known here (a copy of a prepared
-  // workspace, or one of more than QS_ENC_PREPARED_MAX) runs without restarts, as it always did; the kernels give
-  // status 4 to a job whose descriptor has an interval nevertheless, so a lost marker is never silent
-  std::vector<uint8_t> chunk_restart;
-  {
-    std::lock_guard<std::mutex> lock(g_prepared_mutex);
-    auto it = prepared().find(d_workspace);
-    if (it != prepared().end()) {
-      if (it->second.njobs != njobs)
-        return qs_fail(QS_HIP_EINVAL, "%s: the workspace was prepared for %d jobs, the call has %d", who, it->second.njobs,
-                       njobs);
-      total = it->second.total;
-      chunk_restart = it->second.chunk_restart;
-    }
+  // workspace, or one that left the registry) runs without restarts, as it always did; the kernels give status 4 to a
+  // job whose descriptor has an interval nevertheless, so a lost marker is never silent
+  const std::shared_ptr<const Prepared> prep = g_prepared.find(d_workspace);
+  if (prep) {
+    if (prep->njobs != njobs)
+      return qs_fail(QS_HIP_EINVAL, "%s: the workspace was prepared for %d jobs, the call has %d", who, prep->njobs, njobs);
+    total = prep->total;
   }
   if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
   if (int r = device_ok()) return r;
@@ -352,7 +278,7 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
       a.swg0[k] = D[(size_t)j0 + k].swg0;
     }
     const QsEncJob& last = D[(size_t)j0 + a.n - 1];
-    const bool restart = !chunk_restart.empty() && chunk_restart[(size_t)(j0 / QS_ENC_CHUNK)];
+    const bool restart = prep && prep->chunk_restart[(size_t)(j0 / QS_ENC_CHUNK)];
     a.restart = restart ? 1 : 0;
     const int wgs = last.wg0 + last.nwg, swgs = last.swg0 + last.nswg;
     if (!F) {
@@ -365,12 +291,8 @@ int enqueue(qs_hip_job* const* jobs, int njobs, const int32_t* d_stop, uint8_t* 
     memset(&h, 0, sizeof h);
     h.jobs = a.jobs;
     h.d_stop = d_stop;
-    h.counts = reinterpret_cast<uint32_t*>(sc + FS.counts);
-    h.codes = reinterpret_cast<uint32_t*>(sc + FS.codes);
-    h.tables = sc + FS.tables;
+    qs_enc_huff_scratch(h, sc, FS);
     h.d_tables = reinterpret_cast<uint8_t*>(F->d_tables);
-    h.prefix = reinterpret_cast<uint64_t*>(sc + FS.prefix);
-    h.tstatus = reinterpret_cast<int32_t*>(sc + FS.tstatus);
     h.d_len = d_len;
     h.d_status = d_status;
     h.job0 = j0;
@@ -443,17 +365,16 @@ int prepare_opts(qs_hip_job* const* jobs, int njobs, const qs_hip_huff_tables* c
     if (int r = check_workspace(total, d_workspace, bytes, who)) return r;
     if (int r = device_ok()) return r;
     if (int r = upload(d_workspace, D, static_cast<hipStream_t>(stream))) return r;
-    Prepared p{njobs, total, 0, std::vector<uint8_t>((size_t)ceil_div(njobs, QS_ENC_CHUNK), 0)};
+    Prepared p{njobs, total, std::vector<uint8_t>((size_t)ceil_div(njobs, QS_ENC_CHUNK), 0)};
     for (int i = 0; i < njobs; ++i)
       if (D[(size_t)i].ri[0] || D[(size_t)i].ri[1]) p.chunk_restart[(size_t)(i / QS_ENC_CHUNK)] = 1;
-    remember(d_workspace, std::move(p));
+    g_prepared.store(d_workspace, std::move(p));
     return QS_HIP_OK;
   });
 }
 
 }  // namespace
 
-// describe() for the progressive run's driver (csrc/qs_encode_prog_job.cpp), which judges the MCU size scan by scan
 int qs_enc_describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, const char* who) {
   return describe(job, D, P, need_arrays, nullptr, who, true);
 }
@@ -501,7 +422,7 @@ extern "C" int qs_hip_encode_device_batch_histogram(qs_hip_job* const* jobs, int
   });
 }
 
-extern "C" size_t qs_hip_encode_files_scratch_bytes(int njobs) { return (size_t)FilesScratch(njobs).total; }
+extern "C" size_t qs_hip_encode_files_scratch_bytes(int njobs) { return (size_t)QsEncScratch((uint64_t)std::max(njobs, 0)).total; }
 
 extern "C" int qs_hip_encode_device_batch_files(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_frame* frames,
                                                 int optimize, const int32_t* d_stop, uint8_t* const* d_out,

@@ -4,22 +4,18 @@
 // A job with a script of n scans becomes n scan jobs: QsEncJob descriptors with the scan's own geometry (csrc/
 // qs_encode_prog.h: qp_scan_geometry), restart interval and workspace arrays, so that the coder's shared kernels run on
 // them as on any job, and QpScan records with what only the progressive kernels need.
-// Workspace: QsEncJob[scan jobs], QpScan[scan jobs], QpJob[jobs], then per scan job the coder's arrays, the EOB-run
-// arrays and the bytes of its DRI / SOS markers.  Scratch: the whole-file run's arrays per scan job (counts, code words,
-// tables, prefix, table status) and each scan job's length, status and d_stop.
-// The run has no options: prepare notes the plan under the workspace's address, the run looks it up.  A workspace it
-// does not find there gives every job status 4.
+// Workspace: QsEncJob[scan jobs], QpScan[scan jobs], QpJob[jobs], the bytes of the DRI / SOS markers, then per scan job
+// the arrays of one coded scan (csrc/qs_encode_plan.h, with the restart rule, the scratch and the registry of prepared
+// workspaces) and the EOB-run arrays.  Scratch: the whole-file run's arrays and each scan job's length, status and d_stop.
+// The registry holds the whole plan; a workspace the run does not find there gives every job status 4.
 #include "qs_common.h"
 #include "qs_stage.h"
 #include "qs_encode.h"
 #include "qs_encode_prog.h"
+#include "qs_encode_plan.h"
 
 #include <algorithm>
-#include <memory>
-#include <mutex>
-#include <unordered_map>
 
-int qs_enc_describe(const qs_hip_job* job, QsEncJob* D, QsEncPtrs* P, bool need_arrays, const char* who);   // qs_encode_job.cpp
 void qs_launch_encode_prog(const QsEncArgs& a, const QpScan* xs, const QsHuffArgs& h, int wgs, int swgs, int refine,
                            hipStream_t s);
 void qs_launch_encode_prog_stuff(const QsEncArgs& a, int swgs, hipStream_t s);
@@ -46,33 +42,18 @@ struct Plan {
   std::vector<uint8_t> mids;       // the DRI / SOS bytes, and where they go in the workspace
   uint64_t off_mids = 0, off_x = 0, off_q = 0;
   uint64_t total = 0;
-  uint64_t age = 0;
 };
+QsPrepared<Plan> g_plans(256);
 
-struct Scratch {                   // byte offsets of the scratch arrays, all per scan job
-  uint64_t counts, codes, tables, prefix, tstatus, seglen, sstatus, sstop, total;
-  explicit Scratch(size_t nsj) {
-    Layout L;
-    counts = L.take(nsj * 4 * 257 * 4);
-    codes = L.take(nsj * QS_ENC_CODES * 4);
-    tables = L.take(nsj * QS_ENC_TABLES_BYTES);
-    prefix = L.take(nsj * 8);
-    tstatus = L.take(nsj * 4);
+struct Scratch : QsEncScratch {    // the whole-file run's arrays per scan job, and each scan job's length, status and d_stop
+  uint64_t seglen, sstatus, sstop;
+  explicit Scratch(size_t nsj) : QsEncScratch(nsj) {
     seglen = L.take(nsj * 8);
     sstatus = L.take(nsj * 4);
     sstop = L.take(nsj * 4);
     total = L.total;
   }
 };
-
-#define QP_PREPARED_MAX 256
-std::mutex g_mutex;
-uint64_t g_clock = 0;
-// (shared: a run takes its plan under the lock and makes its launches outside it, also while another prepare replaces it)
-std::unordered_map<const void*, std::shared_ptr<const Plan>>& plans() {
-  static std::unordered_map<const void*, std::shared_ptr<const Plan>> m;
-  return m;
-}
 
 // jpeg_set_colorspace's component ids
 void default_ids(int cs, int32_t* id) {
@@ -88,6 +69,7 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
   P = Plan();
   P.njobs = njobs;
   std::vector<uint64_t> maxbits, nints;             // per scan job: the worst case of one block, its intervals at most
+  std::vector<int> nblks;                           // ... and its blocks at most
   std::vector<uint64_t> mid_at;                     // per scan job and variant: offset into P.mids
   for (int i = 0; i < njobs; ++i) {
     const qs_hip_encode_prog_opts* o = opts[i];
@@ -117,9 +99,7 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
     }
     if (o->nscans > QP_MAX_SCANS)                    // (no script of Ah = 0 scans that passes is that long)
       return qs_fail(QS_HIP_EINVAL, "%s: job %d: %d scans, at most %d", who, i, o->nscans, QP_MAX_SCANS);
-    if (o->restart_interval < 0 || o->restart_interval > 65535 || o->restart_in_rows < 0)
-      return qs_fail(QS_HIP_EINVAL, "%s: job %d: restart_interval %d (0 .. 65535), restart_in_rows %d (0 or more)", who, i,
-                     o->restart_interval, o->restart_in_rows);
+    if (int r = qs_enc_check_restart(o->restart_interval, o->restart_in_rows, who, i)) return r;
     int32_t ids[4];
     default_ids(jobs[i]->colorspace, ids);
     if (o->component_id[0] | o->component_id[1] | o->component_id[2] | o->component_id[3])
@@ -174,10 +154,8 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
         if (qp_scan_geometry(full.g[v], r, &J.g[v], &detail) != QS_GEOM_OK)
           return qs_fail(QS_HIP_EINVAL, "%s: job %d, scan %d: %d blocks in an MCU; libjpeg takes at most 10", who, i, s, detail);
         const QsEncGeom& g = J.g[v];
-        // jcmaster.c per_scan_setup: restart_in_rows wins, counted in this scan's MCU rows, limited to 16 bits
-        const long long ri = o->restart_in_rows > 0 ? std::min<long long>((long long)o->restart_in_rows * g.mcus_x, 65535)
-                                                    : o->restart_interval;
-        J.ri[v] = ri >= g.mcus ? 0 : (int)ri;                        // (one interval covers the scan: no marker)
+        int ri = 0;                                                  // (counted in this scan's MCUs)
+        J.ri[v] = qs_enc_restart(o->restart_interval, o->restart_in_rows, g, &ri);
         if (J.ri[v]) nint = std::max<uint64_t>(nint, (uint64_t)ceil_div(g.mcus, J.ri[v]));
         nblocks = std::max(nblocks, g.nblocks);
         if (r.Ah && r.Ss) {
@@ -191,17 +169,17 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
         }
         // jcmarker.c write_scan_header: DRI when the interval differs from the last one written
         mid_at.push_back(P.mids.size());
-        if ((int)ri != last_dri[v]) {
+        if (ri != last_dri[v]) {
           const uint8_t dri[6] = {0xff, 0xdd, 0, 4, (uint8_t)(ri >> 8), (uint8_t)ri};
           P.mids.insert(P.mids.end(), dri, dri + 6);
-          last_dri[v] = (int)ri;
+          last_dri[v] = ri;
           X.mid_bytes[v] = 6;
         }
         P.mids.insert(P.mids.end(), sos, sos + n);
         X.mid_bytes[v] += (uint32_t)n;
         if (v == 0 && per_job) {
           per_job[i].mcus[s] = g.mcus;
-          per_job[i].interval[s] = (int32_t)ri;
+          per_job[i].interval[s] = ri;
         }
       }
       if (!full.two) mid_at.push_back(P.mids.size());
@@ -210,7 +188,7 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
       maxbits.push_back(mb);
       if (per_job)   // every byte stuffed; per interval end a pad byte that may be stuffed and the marker; the markers
         per_job[i].max_body_bytes += 2 * (((uint64_t)nblocks * mb + 7) / 8 + 1) + 4 * (nint - 1) + 2 * (21 + 256) + QP_MID_MAX;
-      J.nwg = ceil_div(nblocks, QS_ENC_WG);
+      nblks.push_back(nblocks);
       nints.push_back(nint);
       if (P.D.size() % QS_ENC_CHUNK == 0) P.refine.push_back(-1);
       P.refine.back() = std::max(P.refine.back(), rounds);
@@ -229,28 +207,9 @@ int make_plan(qs_hip_job* const* jobs, int njobs, const qs_hip_encode_prog_opts*
   for (size_t j = 0; j < nsj; ++j) {
     QsEncJob& J = P.D[j];
     QpScan& X = P.X[j];
-    const uint64_t nint = nints[j];
     if (j % QS_ENC_CHUNK == 0) wgs = swgs = 0;
-    J.wg0 = (int)wgs;
-    wgs += J.nwg;
+    if (int r = qs_enc_scan_layout(L, J, wgs, swgs, nblks[j], nints[j], maxbits[j], true, who)) return r;
     const uint64_t slots = (uint64_t)J.nwg * QS_ENC_WG;
-    const uint64_t plain_cap = align_up((slots * maxbits[j] + 7) / 8, 16) + 16;
-    J.raw_cap = plain_cap + align_up(nint - 1, 16);                 // less than a byte of padding per interval end
-    const uint64_t chunks = (J.raw_cap + QS_ENC_SCHUNK - 1) / QS_ENC_SCHUNK;
-    J.nswg = (int)std::min<uint64_t>(chunks, QS_ENC_SWG_MAX);
-    J.swg0 = (int)swgs;
-    swgs += J.nswg;
-    if (wgs > 0x7fffffffLL) return qs_fail(QS_HIP_EINVAL, "%s: more than 2^31 workgroups in one launch", who);
-    J.off_state = L.take(sizeof(QsEncState));
-    J.off_bits = L.take(slots * 2);
-    J.off_wgsum = L.take((uint64_t)J.nwg * 4);
-    J.off_wgoff = L.take((uint64_t)J.nwg * 8);
-    J.off_raw = L.take(J.raw_cap);
-    J.off_ffcnt = L.take(chunks * 4);
-    J.off_ffoff = L.take(chunks * 8);
-    J.off_rrel = L.take(nint * 4);
-    J.off_rd = L.take((nint + 1) * 8);
-    J.off_rp = L.take((nint + 1) * 8);
     X.off_flags = L.take(slots);
     X.off_wghead = L.take((uint64_t)J.nwg * 4);
     X.off_wgcarry = L.take((uint64_t)J.nwg * 4);
@@ -301,16 +260,7 @@ extern "C" int qs_hip_encode_progressive_device_batch_prepare(qs_hip_job* const*
     HIP_TRY(hipMemcpyAsync(ws + P.off_q, P.Q.data(), P.Q.size() * sizeof(QpJob), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(ws + P.off_mids, P.mids.data(), P.mids.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                // (pageable sources: they must outlive the copies)
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto& m = plans();
-    P.age = ++g_clock;
-    m[d_workspace] = std::make_shared<const Plan>(std::move(P));
-    if (m.size() > QP_PREPARED_MAX) {                // the plan prepared longest ago goes: its workspace runs to status 4
-      auto oldest = m.begin();
-      for (auto it = m.begin(); it != m.end(); ++it)
-        if (it->second->age < oldest->second->age) oldest = it;
-      m.erase(oldest);
-    }
+    g_plans.store(d_workspace, std::move(P));        // (a plan that leaves the registry: its workspace runs to status 4)
     return QS_HIP_OK;
   });
 }
@@ -327,12 +277,7 @@ extern "C" int qs_hip_encode_progressive_device_batch_files(qs_hip_job* const* j
     if (!frames || !d_out || !out_capacity || !d_len || !d_status) return qs_fail(QS_HIP_EINVAL, "%s: null argument", who);
     if (!workspace_ok(d_workspace, bytes, 0)) return qs_fail(QS_HIP_EINVAL, "%s: no workspace (256-byte aligned)", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::shared_ptr<const Plan> plan;
-    {
-      std::lock_guard<std::mutex> lock(g_mutex);     // (held for the lookup alone: runs do not wait for each other)
-      auto it = plans().find(d_workspace);
-      if (it != plans().end()) plan = it->second;
-    }
+    const std::shared_ptr<const Plan> plan = g_plans.find(d_workspace);
     if (!plan) {
       if (int r = device_ok()) return r;
       qs_launch_encode_prog_nofile(d_len, d_status, njobs, s);
@@ -425,11 +370,7 @@ extern "C" int qs_hip_encode_progressive_device_batch_files(qs_hip_job* const* j
       memset(&h, 0, sizeof h);
       h.jobs = a.jobs;
       h.d_stop = a.d_stop;
-      h.counts = a.d_counts;
-      h.codes = reinterpret_cast<uint32_t*>(sc + FS.codes);
-      h.tables = sc + FS.tables;
-      h.prefix = reinterpret_cast<uint64_t*>(sc + FS.prefix);
-      h.tstatus = reinterpret_cast<int32_t*>(sc + FS.tstatus);
+      qs_enc_huff_scratch(h, sc, FS);
       h.job0 = a.job0;
       h.n = a.n;
       h.optimize = 1;

@@ -446,6 +446,71 @@ def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts=None)
     return per, workspace
 
 
+def _encode_outs(outs, images, per, dev, default_bytes, who, torch):
+    """the output buffers of an encode call: outs[i] as the caller gave it, checked, or a new one of
+    default_bytes(i, per[i], the blocks of image i) bytes"""
+    if outs is None:
+        outs = [None] * len(images)
+    if len(outs) != len(images):
+        raise ValueError(f"{who}: one output (or None) per image")
+    bufs = []
+    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
+        if o is None:
+            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
+            o = torch.empty(default_bytes(i, inf, blocks), dtype=torch.uint8, device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
+                or not o.is_contiguous() or o.numel() < 1:
+            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
+        bufs.append(o)
+    return bufs
+
+
+def _len_status(n, dev, torch):
+    """the `len` and `status` tensors of an encode call"""
+    return torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+
+
+def _image_variants(images, result, who):
+    """per image its geometry variants as [(hsamp, vsamp)], its quants and its colour space: variant 0 is what the device
+    codes when stop reads 0 (the replacement chroma at 1x1 when the smoothing made one), variant 1 the original sampling"""
+    out = []
+    for i, im in enumerate(images):
+        res = None if result is None else result["images"][i]
+        ncomp = len(im["coefs"])
+        hs, vs = list(im.get("hsamp") or [1] * ncomp), list(im.get("vsamp") or [1] * ncomp)
+        quants = res["quants"] if res is not None else im.get("quants")
+        if quants is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
+        variants = [(hs, vs)]
+        if res is not None and res.get("coef_up") is not None:
+            variants = [([int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)),
+                        (hs, vs)]
+        out.append((variants, quants, cs))
+    return out
+
+
+def _marker_blob(hip, parts, dev, torch):
+    """parts[i][v] = the marker byte strings of image i's variant v -- (head, mid), or (head,) alone -- in one device buffer
+    -> (the buffer, one EncodeFrame per image, per image the bytes of its longest variant)"""
+    blob, at = bytearray(), []
+    for variants in parts:
+        at.append([])
+        for strings in variants:
+            at[-1].append([])
+            for s in strings:
+                at[-1][-1].append((len(blob), len(s)))
+                blob += s
+    buf = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+    base = buf.data_ptr()
+    frames = []
+    for variants in at:
+        v = variants + [None] * (2 - len(variants))
+        frames.append(hip.encode_frame(*[[None if e is None else (base + e[k][0], e[k][1]) for e in v]
+                                         for k in range(len(variants[0]))]))
+    return buf, frames, [max(sum(nb for _at, nb in e) for e in variants) for variants in at]
+
+
 def encode_scan_batch(images, *, result=None, huffman=None, outs=None, workspace: Workspace | None = None,
                       restart_interval=None, restart_in_rows=None) -> dict:
     """The entropy-coded segment of each image's baseline scan, exactly the bytes libjpeg 9 writes between the SOS header
@@ -474,22 +539,9 @@ def _encode_scan_batch(images, result, huffman, outs, workspace, who, opts=None)
     hip = _hip()
     tabs, tabkey = _huff_tables(hip, huffman, len(jobs), who)
     per, workspace = _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts)
-    if outs is None:
-        outs = [None] * len(jobs)
-    if len(outs) != len(jobs):
-        raise ValueError(f"{who}: one output (or None) per image")
-    bufs = []
-    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
-        if o is None:
-            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
-            o = torch.empty(min(inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks), dtype=torch.uint8,
-                            device=dev)
-        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
-                or not o.is_contiguous() or o.numel() < 1:
-            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
-        bufs.append(o)
-    length = torch.empty(len(jobs), dtype=torch.int64, device=dev)
-    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    bufs = _encode_outs(outs, images, per, dev, lambda i, inf, blocks: min(
+        inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks), who, torch)
+    length, status = _len_status(len(jobs), dev, torch)
     hip.encode_batch(jobs, None if stop is None else stop.data_ptr(), [o.data_ptr() for o in bufs],
                      [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(), workspace.buf.data_ptr(),
                      workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
@@ -647,27 +699,15 @@ def huffman_of_tables(record) -> dict:
 
 
 def _file_frames(images, result, opts, optimize, huffman, who):
-    """per image and geometry variant the (head, mid) bytes of jpeg_file.compose_parts: variant 0 is what the device codes
-    when stop reads 0 (the replacement chroma at 1x1 when the smoothing made one), variant 1 the original sampling"""
+    """per image and geometry variant (_image_variants) the (head, mid) bytes of jpeg_file.compose_parts"""
     from . import jpeg_file
     hip = _hip()
     n = len(images)
     per = huffman if isinstance(huffman, (list, tuple)) else [huffman] * n
     std = None
     parts = []
-    for i, im in enumerate(images):
-        res = None if result is None else result["images"][i]
-        ncomp = len(im["coefs"])
-        hs, vs = list(im.get("hsamp") or [1] * ncomp), list(im.get("vsamp") or [1] * ncomp)
-        quants = res["quants"] if res is not None else im.get("quants")
-        if quants is None:
-            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
-        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
+    for i, (im, (variants, quants, cs)) in enumerate(zip(images, _image_variants(images, result, who))):
         size = tuple(im["image_size"])
-        variants = [(hs, vs)]
-        if res is not None and res.get("coef_up") is not None:
-            variants = [([int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)),
-                        (hs, vs)]
         dc = ac = None
         if not optimize:
             if std is None:
@@ -738,18 +778,7 @@ def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts,
              for i, script in enumerate(per_image)]
     per, total, scratch_bytes = hip.encode_progressive_info(jobs, popts)
     heads = []                                                          # per image and geometry variant: SOI .. SOF2
-    for i, im in enumerate(images):
-        res = None if result is None else result["images"][i]
-        ncomp = len(im["coefs"])
-        hs, vs = list(im.get("hsamp") or [1] * ncomp), list(im.get("vsamp") or [1] * ncomp)
-        quants = res["quants"] if res is not None else im.get("quants")
-        cs = im.get("colorspace") if im.get("colorspace") is not None else (3 if ncomp == 3 else 1)
-        variants = [(hs, vs)]
-        if res is not None and res.get("coef_up") is not None:
-            variants = [([int(res.get("hsamp0") or 1)] + [1] * (ncomp - 1), [int(res.get("vsamp0") or 1)] + [1] * (ncomp - 1)),
-                        (hs, vs)]
-        if quants is None:
-            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
+    for im, (variants, quants, cs) in zip(images, _image_variants(images, result, who)):
         heads.append([jpeg_file.compose_parts(quants, vh, vv, cs, tuple(im["image_size"]), progressive=True)[0] for vh, vv in variants])
     key = ("progressive", refinement, tuple(tuple(map(tuple, s)) for s in per_image), tuple(opts or ()),
            tuple(_key(job, 0, 0) for job in jobs), tuple(tuple(h) for h in heads), str(dev))
@@ -763,38 +792,14 @@ def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts,
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
         hip.encode_progressive_prepare(jobs, popts, workspace.buf.data_ptr(), workspace.nbytes,
                                        torch.cuda.current_stream(dev).cuda_stream)
-        blob, frames_at = bytearray(), []
-        for variants in heads:
-            frames_at.append([])
-            for head in variants:
-                frames_at[-1].append((len(blob), len(head)))
-                blob += head
-        buf = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
-        base = buf.data_ptr()
-        frames = []
-        for variants in frames_at:
-            v = variants + [None] * (2 - len(variants))
-            frames.append(hip.encode_frame(head=[None if e is None else (base + e[0], e[1]) for e in v]))
+        buf, frames, fixed = _marker_blob(hip, [[(head,) for head in variants] for variants in heads], dev, torch)
         workspace.files = dict(key=key, buf=buf, frames=frames, scratch=torch.empty(max(1, scratch_bytes), dtype=torch.uint8, device=dev),
-                               fixed=[max(e[1] for e in variants) for variants in frames_at])
+                               fixed=fixed)
         workspace.key = key
     fs = workspace.files
-    if outs is None:
-        outs = [None] * n
-    if len(outs) != n:
-        raise ValueError(f"{who}: one output (or None) per image")
-    bufs = []
-    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
-        if o is None:
-            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
-            o = torch.empty(fs["fixed"][i] + min(inf["max_body_bytes"], 4096 + 600 * inf["nscans"] + 40 * blocks), dtype=torch.uint8,
-                            device=dev)
-        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
-                or not o.is_contiguous() or o.numel() < 1:
-            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
-        bufs.append(o)
-    length = torch.empty(n, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
+    bufs = _encode_outs(outs, images, per, dev, lambda i, inf, blocks: fs["fixed"][i] + min(
+        inf["max_body_bytes"], 4096 + 600 * inf["nscans"] + 40 * blocks), who, torch)
+    length, status = _len_status(n, dev, torch)
     hip.encode_progressive_files(jobs, fs["frames"], None if stop is None else stop.data_ptr(), [o.data_ptr() for o in bufs],
                                  [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(), fs["scratch"].data_ptr(),
                                  int(fs["scratch"].numel()), workspace.buf.data_ptr(), workspace.nbytes,
@@ -817,39 +822,14 @@ def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, 
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call with the same "
                                f"markers (workspace=...): uploading them copies from the host")
-        blob, at = bytearray(), []
-        for variants in parts:
-            at.append([])
-            for head, mid in variants:
-                at[-1].append((len(blob), len(head), len(blob) + len(head), len(mid)))
-                blob += head + mid
-        buf = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
-        base = buf.data_ptr()
-        frames = []
-        for variants in at:
-            v = variants + [None] * (2 - len(variants))
-            frames.append(hip.encode_frame(head=[None if e is None else (base + e[0], e[1]) for e in v],
-                                           mid=[None if e is None else (base + e[2], e[3]) for e in v]))
+        buf, frames, fixed = _marker_blob(hip, parts, dev, torch)
         nbytes = hip.encode_files_scratch_bytes(n)
         workspace.files = dict(key=fkey, buf=buf, frames=frames, scratch=torch.empty(nbytes, dtype=torch.uint8, device=dev),
-                               fixed=[max(e[1] + e[3] for e in variants) for variants in at])
+                               fixed=fixed)
     fs = workspace.files
-    if outs is None:
-        outs = [None] * n
-    if len(outs) != n:
-        raise ValueError(f"{who}: one output (or None) per image")
-    bufs = []
-    for i, (inf, o, im) in enumerate(zip(per, outs, images)):
-        if o is None:
-            blocks = sum(int(t.shape[0]) * int(t.shape[1]) for t in im["coefs"])
-            o = torch.empty(fs["fixed"][i] + 4 * 277 + 2 + min(inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks),
-                            dtype=torch.uint8, device=dev)
-        elif not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or o.dim() != 1 \
-                or not o.is_contiguous() or o.numel() < 1:
-            raise ValueError(f"{who}: output {i} must be a contiguous one-dimensional uint8 tensor on {dev}")
-        bufs.append(o)
-    length = torch.empty(n, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
+    bufs = _encode_outs(outs, images, per, dev, lambda i, inf, blocks: fs["fixed"][i] + 4 * 277 + 2 + min(
+        inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks), who, torch)
+    length, status = _len_status(n, dev, torch)
     tables = torch.empty((n, TABLES_BYTES), dtype=torch.uint8, device=dev) if optimize else None
     hip.encode_batch_files(jobs, fs["frames"], optimize, None if stop is None else stop.data_ptr(),
                            [o.data_ptr() for o in bufs], [int(o.numel()) for o in bufs], length.data_ptr(), status.data_ptr(),
