@@ -592,6 +592,68 @@ int qs_hip_read_split_device_batch_prepare(qs_hip_job *const *jobs, int njobs, c
 		void *d_workspace, size_t bytes, void *stream);
 int qs_hip_read_split_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_scan,
 		const uint64_t *scan_bytes, int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
+/* The progressive route of the scan reader: the bytes of a whole PROGRESSIVE Huffman file (SOF2, 8 bits) in device memory
+ * -> the coefficient arrays libjpeg 9's jpeg_read_coefficients leaves (jdhuff.c decode_mcu_DC_first / _AC_first /
+ * _DC_refine / _AC_refine, jdcoefct.c consume_data).  The jobs are the ones of the calls above; the options carry what a
+ * host-side walk over the file's markers found (jpeg_file.parse_progressive): per scan the jpeg_scan_info record, Td / Ta
+ * of its components, the DHT tables and the DRI value in effect at its SOS, and the offset of the first byte behind its
+ * SOS header.  The unit of work is a (job, scan) pair, and one lane decodes one restart interval of one scan.
+ * A scan depends on every earlier scan of the file that shares a component with it and whose band [Ss, Se] overlaps its
+ * own; its level is 0 if it depends on nothing, else 1 + the largest level it depends on, and the run makes one decode
+ * launch per level (libjpeg's ten-scan YCbCr script: three).  Parallelism comes from restart intervals, independent scans
+ * and the batch and from nothing else: a file without DRI is read by one lane per scan.  No self-synchronisation inside
+ * an interval (an AC refinement scan cannot have it).
+ * Rules: DC first -- the prediction runs as int from 0 in every interval, per scan component, the store is (JCOEF)(pred
+ * << Al); AC first -- HUFF_EXTEND << Al at zz[k], EOB runs (r < 15, s = 0: (1 << r) + r more bits; this block and the next
+ * run - 1 blocks are done), cleared at every interval start; DC refinement -- one bit per block, coef[0] |= 1 << Al, no
+ * table; AC refinement -- decode_mcu_AC_refine: a new coefficient has s = 1 and a sign bit, every already non-zero
+ * coefficient passed over takes one correction bit, applied only if (coef & (1 << Al)) == 0 and away from zero.  An
+ * interleaved scan keeps the frame's MCU grid and writes the dummy blocks of edge MCUs where the array has room for
+ * them; a one-component scan runs raster over width_in_blocks x height_in_blocks.  Every block no scan codes is 0.
+ * Refusals, from info, before anything is enqueued: a script libjpeg's validate_script refuses QS_HIP_EINVAL naming the
+ * scan; one it takes as sequential multi-scan, more than QS_HIP_MAX_SCANS scans, more than 10 blocks in an MCU of an
+ * interleaved scan, or an interval of more than QS_HIP_READ_MAX_INTERVAL_BLOCKS blocks in any scan -- counted in that
+ * scan's own MCUs, one block per MCU in a one-component scan -- QS_HIP_ENOTSUP; a scan that uses a table its record does
+ * not hold QS_HIP_EINVAL (a DC scan uses Td of each component, an AC scan Ta of its one, a DC refinement none).
+ *   info     per job nscans, levels and per scan mcus / intervals; *workspace_bytes; no device touched;
+ *   prepare  the pairs' descriptors (geometry, derived code tables, offsets) and the level lists into the workspace, and
+ *            the plan under the workspace's address; may synchronise `stream`, never inside a capture;
+ *   run      ENQUEUES launches only (graph-capturable, a linear graph): per chunk of QS_HIP_READ_CHUNK jobs 1 (arrays
+ *            zeroed), 4 per 32 pairs (the scans' ends and RSTn markers), 1 (checks) and one decode launch per level.
+ *            A workspace never prepared, or prepared for another number of jobs: QS_HIP_EINVAL.
+ * d_file[i]: device memory (any alignment) holding the whole file; file_bytes[i]: how many bytes may be read there --
+ * every read is bounded by it.  The scans' offsets are fixed at prepare, like the tables of the calls above: a run (or a
+ * graph replay) on another file of the same header layout reads that file; on a file whose scans do not start at the
+ * prepared offsets it ends with a non-zero status (the SOS header in front of every prepared offset is compared with
+ * the scan's record: status 1), never with an access outside the file or the arrays.
+ * d_status[i] (device int32), the largest over all scans and lanes of the job: 0 ok; 1 the RSTn count or order of a scan
+ * does not fit its interval, or a scan does not start at its prepared offset (no scan of such a job is decoded); 2 an
+ * interval ran short or has a whole byte left over, or no marker ends a scan (the file stops inside it); 3 a bit pattern
+ * without a code, a run passing Se, s != 1 in an AC refinement, or an EOB run longer than the blocks left in its
+ * interval.  libjpeg only warns on, or silently accepts, some of these.  With a non-zero status the arrays' content is
+ * unspecified, every store lies inside them, and other jobs are unaffected. */
+typedef struct {
+	qs_hip_encode_scan scan;                             /* comps_in_scan, component_index[] (frame order), Ss, Se, Ah, Al */
+	int32_t dc_tbl[QS_HIP_MAXC], ac_tbl[QS_HIP_MAXC];    /* Td / Ta of each scan component */
+	qs_hip_huff_table dc[4], ac[4];                      /* the DHT tables in effect at this SOS, by id */
+	uint8_t has_dc[4], has_ac[4];
+	int32_t restart_interval;                            /* the DRI in effect, in this scan's MCUs; 0: none */
+	uint64_t offset;                                     /* of the first byte behind the SOS header, in the file */
+} qs_hip_read_prog_scan;
+typedef struct {
+	const qs_hip_read_prog_scan *scans;
+	int32_t nscans;
+} qs_hip_read_prog_opts;
+typedef struct {
+	int32_t nscans, levels;
+	int32_t mcus[QS_HIP_MAX_SCANS], intervals[QS_HIP_MAX_SCANS];
+} qs_hip_read_prog_info;
+int qs_hip_read_prog_device_batch_info(qs_hip_job *const *jobs, int njobs, const qs_hip_read_prog_opts *const *opts,
+		qs_hip_read_prog_info *per_job, size_t *workspace_bytes);
+int qs_hip_read_prog_device_batch_prepare(qs_hip_job *const *jobs, int njobs, const qs_hip_read_prog_opts *const *opts,
+		void *d_workspace, size_t bytes, void *stream);
+int qs_hip_read_prog_device_batch(qs_hip_job *const *jobs, int njobs, const uint8_t *const *d_file,
+		const uint64_t *file_bytes, int32_t *d_status, void *d_workspace, size_t bytes, void *stream);
 /* Host only.  The optimal table for symbol counts freq[0..255] (freq[256] is ignored: the reserved symbol always counts
  * 1) by the procedure of JPEG Annex K.2 as libjpeg 9 carries it out: what optimize_coding writes into its DHT.  Counts
  * that are all zero: bits all 0, no symbols, success.  A code length above 32: QS_HIP_EINVAL.  (csrc/qs_huff.h: the
@@ -682,7 +744,8 @@ const char *qs_hip_last_error(void);
  * additions only: qs_hip_set_shard_schedule, the RCCL band entry points; 7: additions only -- the device-resident job,
  * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
  * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress,
- * the split route of the scan reader qs_hip_read_split_device_batch and its two calls, the _opts calls of the decode).
+ * the split route of the scan reader qs_hip_read_split_device_batch and its two calls, the _opts calls of the decode,
+ * the progressive route of the scan reader qs_hip_read_prog_device_batch and its two calls).
  * A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */
 #define QS_HIP_ABI_VERSION 7

@@ -72,13 +72,16 @@ DECODE_KERNELS = ("qs_decode_kernel",)
 # whose bounds are run-time values -- it stays in registers only as long as every index is a constant
 PROG_KERNELS = ("qp_begin", "qp_nofile", "qp_flags", "qp_headscan", "qp_runs", "qp_size", "qp_emit", "qp_frame",
                 "qr_flags", "qr_wsum", "qr_wscan", "qr_next", "qr_hop")      # qr_: the refinement scans' own
+# the scan reader's progressive route (qs_kernels_read_prog.hip): as for the split route; the job's arrays are reached
+# through the kernel arguments, not through a local copy a lane would index
+READ_PROG_KERNELS = ("qrp_init", "qrp_check", "qrp_decode")
 INSTANCES = {"qp_size": 4, "qp_emit": 2}     # template instantiations of one name (every other kernel: one)
 
 
 def main_no_scratch(prefix, path):
-    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS, DECODE_KERNELS and PROG_KERNELS that starts
-    with the prefix is there (in all its instantiations) and has no scratch"""
-    want = [k for k in SPLIT_READ_KERNELS + DECODE_KERNELS + PROG_KERNELS if k.startswith(prefix)]
+    """--no-scratch <prefix> <device.s>: every kernel of SPLIT_READ_KERNELS, DECODE_KERNELS, PROG_KERNELS and
+    READ_PROG_KERNELS that starts with the prefix is there (in all its instantiations) and has no scratch"""
+    want = [k for k in SPLIT_READ_KERNELS + DECODE_KERNELS + PROG_KERNELS + READ_PROG_KERNELS if k.startswith(prefix)]
     recs = kernel_records(open(path).read())
     bad = 0
     for k in want:

@@ -174,6 +174,25 @@ class ReadSplitInfo(C.Structure):
     _fields_ = ReadInfo._fields_ + [("max_segments", C.c_int64)]
 
 
+class ReadProgScan(C.Structure):
+    """qs_hip_read_prog_scan: one scan of a progressive file -- its jpeg_scan_info record, Td / Ta of its components, the
+    DHT tables and the DRI value in effect at its SOS, the offset of the first byte behind its SOS header"""
+    _fields_ = [("scan", EncodeScan), ("dc_tbl", C.c_int32 * MAXC), ("ac_tbl", C.c_int32 * MAXC), ("dc", HuffTable * 4),
+                ("ac", HuffTable * 4), ("has_dc", C.c_uint8 * 4), ("has_ac", C.c_uint8 * 4), ("restart_interval", C.c_int32),
+                ("offset", C.c_uint64)]
+
+
+class ReadProgOpts(C.Structure):
+    """qs_hip_read_prog_opts: the scans of one progressive file (jpeg_file.parse_progressive)"""
+    _fields_ = [("scans", C.POINTER(ReadProgScan)), ("nscans", C.c_int32)]
+
+
+class ReadProgInfo(C.Structure):
+    """qs_hip_read_prog_info: one job of the scan reader's progressive route (qs_hip_read_prog_device_batch_info)"""
+    _fields_ = [("nscans", C.c_int32), ("levels", C.c_int32), ("mcus", C.c_int32 * MAX_SCANS),
+                ("intervals", C.c_int32 * MAX_SCANS)]
+
+
 READ_SPLIT_BYTES = 256           # QS_HIP_READ_SPLIT_BYTES: stuffed bytes of a restart interval one lane decodes
 READ_SPLIT_ROUNDS = 17           # QS_HIP_READ_SPLIT_ROUNDS: synchronisation launches of the split route
 
@@ -270,6 +289,14 @@ ABI = {
                                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_read_split_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "qs_hip_read_prog_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                      C.POINTER(C.POINTER(ReadProgOpts)), C.POINTER(ReadProgInfo),
+                                                      C.POINTER(C.c_size_t)]),
+    "qs_hip_read_prog_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                         C.POINTER(C.POINTER(ReadProgOpts)), C.c_void_p, C.c_size_t,
+                                                         C.c_void_p]),
+    "qs_hip_read_prog_device_batch": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "qs_hip_compress_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.POINTER(CompressInfo),
                                                      C.POINTER(C.c_size_t)]),
     "qs_hip_compress_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
@@ -916,6 +943,67 @@ class HipQS:
         lens = (C.c_uint64 * max(1, len(scan_bytes)))(*[int(v) for v in scan_bytes])
         call = self.lib.qs_hip_read_split_device_batch if split else self.lib.qs_hip_read_device_batch
         self._check(call(self._job_ptrs(jobs), len(jobs), scans, lens, d_status, d_workspace, nbytes, stream))
+
+    # -- its progressive route (whole SOF2 files) ----------------------------------------
+    @staticmethod
+    def read_prog_opts(scans) -> ReadProgOpts:
+        """a qs_hip_read_prog_opts from jpeg_file.parse_progressive(...)["scans"]: per scan dict(comps, ss, se, ah, al,
+        dc_tbl, ac_tbl, dc, ac ({DHT id: (bits[17], huffval)} in effect), restart_interval, offset)"""
+        scans = list(scans)
+        arr = (ReadProgScan * max(1, len(scans)))()
+        for r, s in zip(arr, scans):
+            comps = list(s["comps"])
+            r.scan.ncomp = len(comps)
+            for k, c in enumerate(comps[:4]):
+                r.scan.comp[k] = int(c)
+            r.scan.Ss, r.scan.Se, r.scan.Ah, r.scan.Al = int(s["ss"]), int(s["se"]), int(s["ah"]), int(s["al"])
+            for k, (td, ta) in enumerate(list(zip(s["dc_tbl"], s["ac_tbl"]))[:4]):
+                r.dc_tbl[k], r.ac_tbl[k] = int(td), int(ta)
+            for tabs, dst, has in ((s.get("dc") or {}, r.dc, r.has_dc), (s.get("ac") or {}, r.ac, r.has_ac)):
+                for k, (bits, vals) in tabs.items():
+                    if k not in (0, 1, 2, 3) or len(bits) != 17 or len(vals) > 256:
+                        raise ValueError("read_prog_opts: table 0..3, bits[17], at most 256 symbols")
+                    dst[k].bits[:] = [int(b) for b in bits]
+                    for i, v in enumerate(vals):
+                        dst[k].huffval[i] = int(v)
+                    has[k] = 1
+            r.restart_interval = int(s["restart_interval"])
+            r.offset = int(s["offset"])
+        o = ReadProgOpts(C.cast(arr, C.POINTER(ReadProgScan)), len(scans))
+        o._scans = arr                                                  # (kept alive with the record)
+        return o
+
+    @staticmethod
+    def _read_prog_opt_ptrs(opts, n):
+        if len(opts) != n:
+            raise ValueError("one ReadProgOpts per job")
+        return (C.POINTER(ReadProgOpts) * max(1, n))(*[None if o is None else C.pointer(o) for o in opts])
+
+    def read_prog_batch_info(self, jobs, opts):
+        """qs_hip_read_prog_device_batch_info (no device needed) -> (list of dict(nscans, levels, mcus, intervals), the
+        batch's workspace bytes)"""
+        per = (ReadProgInfo * max(1, len(jobs)))()
+        total = C.c_size_t(0)
+        self._check(self.lib.qs_hip_read_prog_device_batch_info(self._job_ptrs(jobs), len(jobs),
+                                                                self._read_prog_opt_ptrs(opts, len(jobs)), per,
+                                                                C.byref(total)))
+        return [dict(nscans=int(p.nscans), levels=int(p.levels), mcus=list(p.mcus[:p.nscans]),
+                     intervals=list(p.intervals[:p.nscans])) for p in per[:len(jobs)]], int(total.value)
+
+    def read_prog_batch_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_read_prog_device_batch_prepare: the (job, scan) pairs' descriptors and the level lists into the
+        workspace (synchronises `stream`; not inside a capture)"""
+        self._check(self.lib.qs_hip_read_prog_device_batch_prepare(self._job_ptrs(jobs), len(jobs),
+                                                                   self._read_prog_opt_ptrs(opts, len(jobs)), d_workspace,
+                                                                   nbytes, stream))
+
+    def read_prog_batch(self, jobs, d_file, file_bytes, d_status: int, d_workspace: int, nbytes: int, stream=None) -> None:
+        """qs_hip_read_prog_device_batch: enqueue the progressive reader of every job; d_file[i] = device address of job
+        i's whole file, file_bytes[i] = how many bytes may be read there, d_status = device int32[njobs]"""
+        files = (C.c_void_p * max(1, len(d_file)))(*d_file)
+        lens = (C.c_uint64 * max(1, len(file_bytes)))(*[int(v) for v in file_bytes])
+        self._check(self.lib.qs_hip_read_prog_device_batch(self._job_ptrs(jobs), len(jobs), files, lens, d_status,
+                                                           d_workspace, nbytes, stream))
 
     def huff_optimal(self, freq):
         """qs_hip_huff_optimal (host only): symbol counts (256 or 257) -> (bits[17], huffval) as libjpeg's

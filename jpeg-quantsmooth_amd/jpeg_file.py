@@ -340,3 +340,149 @@ def parse(data, header_only: bool = False) -> dict:
                 vsamp=[c[2] for c in comps], quants=[qt[c[3]].copy() for c in comps], dc=dc, ac=ac,
                 dc_tbl=[d for _c, d, _a in sel], ac_tbl=[a for _c, _d, a in sel], restart_interval=int(dri),
                 scan_offset=pos, sof=frame["sof"], component_ids=ids)
+
+
+# ---- the markers of a progressive file, scan by scan ------------------------------------------------------------------------
+
+def parse_progressive(data) -> dict:
+    """The markers of a whole progressive Huffman file (SOF2, 8 bits) -> parse()'s frame fields (image_size, colorspace,
+    hsamp, vsamp, quants, component_ids, sof = 0xC2) and
+      scans   one dict per scan: comps (frame indices), ss, se, ah, al, dc_tbl / ac_tbl (Td / Ta per scan component),
+              dc / ac (the DHT tables in effect at that SOS: DHT and DRI persist until redefined), restart_interval,
+              offset (the first byte behind the SOS header), length (up to the next marker that is not RSTn)
+      script  [(comps, ss, se, ah, al)]
+    for the progressive route of the device scan reader (qs_hip_read_prog_device_batch).  Looks at markers only.
+
+    Accepted: exactly the files whose script passes validate_script (with either return value).  Everything else raises
+    ValueError naming what it met: SOF0 / SOF1 (parse()'s files), arithmetic, lossless and differential frames, 12 bits,
+    a DQT behind the first SOS, DNL, a scan that names an undefined table (a DC refinement names none), a script
+    validate_script refuses (with its scan index), no EOI behind the last scan."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("parse_progressive: no SOI at the start")
+    pos, qt, dc, ac, dri, frame, jfif, adobe, scans = 2, {}, {}, {}, 0, None, False, None, []
+    while True:
+        while pos + 1 < len(data) and data[pos] == 0xFF and data[pos + 1] == 0xFF:
+            pos += 1                                                   # fill bytes
+        if pos + 2 > len(data):
+            raise ValueError("parse_progressive: the data ends without EOI" + (" behind the last scan" if scans else ""))
+        if data[pos] != 0xFF:
+            raise ValueError(f"parse_progressive: marker expected at byte {pos}")
+        code = data[pos + 1]
+        if code == 0xD9:
+            if not scans:
+                raise ValueError("parse_progressive: EOI in front of any scan")
+            break
+        if code == 0x01 or 0xD0 <= code <= 0xD7:
+            pos += 2
+            continue
+        if pos + 4 > len(data):
+            raise ValueError("parse_progressive: the data ends without EOI")
+        n = struct.unpack_from(">H", data, pos + 2)[0]
+        if n < 2 or pos + 2 + n > len(data):
+            raise ValueError(f"parse_progressive: marker FF{code:02X} at byte {pos} runs past the data")
+        body = data[pos + 4:pos + 2 + n]
+        pos += 2 + n
+        if code in (0xC0, 0xC1):
+            raise ValueError(f"parse_progressive: a sequential frame (SOF{code - 0xC0}): parse() reads it")
+        if code in _SOF_NAMES and code != 0xC2:
+            raise ValueError(f"parse_progressive: {_SOF_NAMES[code]}: only progressive Huffman (SOF2)")
+        if code == 0xCC:
+            raise ValueError("parse_progressive: arithmetic coding (DAC)")
+        if code == 0xDC:
+            raise ValueError("parse_progressive: DNL")
+        if code == 0xC2:
+            if frame is not None:
+                raise ValueError("parse_progressive: a second SOF")
+            if len(body) < 6:
+                raise ValueError("parse_progressive: bad SOF")
+            prec, h, w, nc = struct.unpack_from(">BHHB", body, 0)
+            if prec != 8:
+                raise ValueError(f"parse_progressive: {prec}-bit samples: only 8")
+            if h == 0:
+                raise ValueError("parse_progressive: height 0 (DNL)")
+            if not 1 <= nc <= 4 or len(body) != 6 + 3 * nc:
+                raise ValueError(f"parse_progressive: {nc} components in the frame")
+            frame = dict(image_size=(w, h), comps=[(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15,
+                                                    body[8 + 3 * i]) for i in range(nc)])
+        elif code == 0xDB:
+            if scans:
+                raise ValueError("parse_progressive: DQT behind the first SOS")
+            p = 0
+            while p < len(body):
+                prec, idx = body[p] >> 4, body[p] & 15
+                if prec > 1 or idx > 3 or p + 1 + 64 * (prec + 1) > len(body):
+                    raise ValueError("parse_progressive: bad DQT")
+                vals = struct.unpack_from(">64H" if prec else "64B", body, p + 1)
+                q = np.zeros(64, np.uint16)
+                q[ZIGZAG] = vals
+                qt[idx] = q
+                p += 1 + 64 * (prec + 1)
+        elif code == 0xC4:
+            p = 0
+            while p < len(body):
+                if p + 17 > len(body):
+                    raise ValueError("parse_progressive: bad DHT")
+                idx = body[p]
+                bits = [0] + list(body[p + 1:p + 17])
+                cnt = sum(bits)
+                if (idx & 0xEF) > 3 or cnt > 256 or p + 17 + cnt > len(body):
+                    raise ValueError("parse_progressive: bad DHT")
+                (ac if idx & 0x10 else dc)[idx & 15] = (bits, list(body[p + 17:p + 17 + cnt]))
+                p += 17 + cnt
+        elif code == 0xDD:
+            if len(body) != 2:
+                raise ValueError("parse_progressive: bad DRI")
+            dri = struct.unpack(">H", body)[0]
+        elif code == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif code == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif code == 0xDA:
+            if frame is None:
+                raise ValueError("parse_progressive: SOS in front of SOF")
+            ids = [c[0] for c in frame["comps"]]
+            ns = body[0] if body else 0
+            if not 1 <= ns <= 4 or len(body) != 4 + 2 * ns:
+                raise ValueError(f"parse_progressive: scan {len(scans)}: bad SOS")
+            comps, td, ta = [], [], []
+            for i in range(ns):
+                cid = body[1 + 2 * i]
+                if cid not in ids:
+                    raise ValueError(f"parse_progressive: scan {len(scans)} names component id {cid}, not of the frame")
+                comps.append(ids.index(cid))
+                td.append(body[2 + 2 * i] >> 4)
+                ta.append(body[2 + 2 * i] & 15)
+            ss, se, ahal = body[1 + 2 * ns:4 + 2 * ns]
+            ah, al = ahal >> 4, ahal & 15
+            for i in range(ns):
+                if ss == 0 and ah == 0 and td[i] not in dc:
+                    raise ValueError(f"parse_progressive: scan {len(scans)}: Huffman table DC {td[i]} is used but not defined")
+                if ss != 0 and ta[i] not in ac:
+                    raise ValueError(f"parse_progressive: scan {len(scans)}: Huffman table AC {ta[i]} is used but not defined")
+            # behind the header: up to the next marker that is not RSTn (markers only: the bytes between are not decoded)
+            end = pos
+            while end + 1 < len(data) and not (data[end] == 0xFF and data[end + 1] != 0 and not 0xD0 <= data[end + 1] <= 0xD7):
+                end = data.find(b"\xff", end + 1)
+                if end < 0:
+                    end = len(data)
+            if end + 1 >= len(data):
+                raise ValueError(f"parse_progressive: the data ends inside scan {len(scans)}: no EOI behind the last scan")
+            scans.append(dict(comps=comps, ss=ss, se=se, ah=ah, al=al, dc_tbl=td, ac_tbl=ta, dc=dict(dc), ac=dict(ac),
+                              restart_interval=int(dri), offset=pos, length=end - pos))
+            pos = end
+    if frame is None:
+        raise ValueError("parse_progressive: no frame header")
+    comps = frame["comps"]
+    for _c, _h, _v, tq in comps:
+        if tq not in qt:
+            raise ValueError(f"parse_progressive: quantisation table {tq} is used but not defined")
+    script = [scan(s["comps"], s["ss"], s["se"], s["ah"], s["al"]) for s in scans]
+    try:
+        validate_script(script, len(comps))
+    except ScriptError as e:
+        raise ValueError(f"parse_progressive: {e}") from None
+    ids = [c[0] for c in comps]
+    return dict(image_size=frame["image_size"], colorspace=_colorspace(ids, jfif, adobe), hsamp=[c[1] for c in comps],
+                vsamp=[c[2] for c in comps], quants=[qt[c[3]].copy() for c in comps], component_ids=ids, sof=0xC2,
+                scans=scans, script=script)

@@ -33,7 +33,8 @@ builds the optimal Huffman tables and the whole file on the device (qs_hip_encod
     im = torch_qs.read(data)          # data: the bytes of a JPEG file with restart intervals, on the host or the device
 
 reads a file's scan into device coefficient tensors (qs_hip_read_device_batch, one lane per restart interval): the image
-dict the three calls above take.
+dict the three calls above take.  A progressive file (SOF2) goes to read_progressive (qs_hip_read_prog_device_batch: one
+lane per restart interval of one scan, one decode launch per level of the script), also through read / read_batch.
 
     im = torch_qs.compress(pixels, quality=85, hsamp=[2, 1, 1], vsamp=[2, 1, 1])   # pixels: uint8 (H, W, 3) on the device
 
@@ -916,7 +917,11 @@ def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=N
     by a prefix sum.  There is no interval cap; the images and the capture rules are the same, the workspace is one of
     its own (a workspace prepared for one route is prepared again for the other), and status may also be 4: the
     segments did not synchronise, read the file with split=False.  The default stays False until the crossover
-    between the routes is measured."""
+    between the routes is measured.
+
+    A batch in which EVERY file's frame is progressive (SOF2) is handed to read_progressive_batch (split=True is then a
+    ValueError); a batch that mixes progressive and sequential files raises ValueError naming the first file of the other
+    kind.  Sequential files take exactly the path they took before that route existed."""
     return _read_batch(datas, outs, workspace, device, "read_batch", split)
 
 
@@ -934,8 +939,30 @@ def _read_batch(datas, outs, workspace, device, who, split=False):
         if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
             raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
         headers = workspace.headers
+        if headers[0].get("sof") == 0xC2:                               # a workspace of the progressive route
+            if split:
+                raise ValueError(f"{who}: split=True reads sequential files; these are progressive (SOF2)")
+            return _read_progressive_batch(datas, outs, workspace, device, who)
     else:
-        headers = [_read_header(d, torch, f"{who}: file {i}") for i, d in enumerate(datas)]
+        # a sequential file takes the path below; a batch in which every frame is SOF2 goes to the progressive route
+        headers, prog = [], []
+        for i, d in enumerate(datas):
+            try:
+                headers.append(_read_header(d, torch, f"{who}: file {i}"))
+                prog.append(False)
+            except ValueError as e:
+                if "(SOF2)" not in str(e):
+                    raise
+                headers.append(None)
+                prog.append(True)
+        if any(prog):
+            if not all(prog):
+                other = prog.index(not prog[0])
+                raise ValueError(f"{who}: file 0 is {'progressive (SOF2)' if prog[0] else 'sequential'} and file {other} is "
+                                 f"{'progressive (SOF2)' if prog[other] else 'sequential'}: a batch is read by one route")
+            if split:
+                raise ValueError(f"{who}: split=True reads sequential files; these are progressive (SOF2)")
+            return _read_progressive_batch(datas, outs, workspace, device, who)
     dev = next((d.device for d in datas if isinstance(d, torch.Tensor) and d.is_cuda), None)
     if dev is None:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -997,6 +1024,110 @@ def read(data, *, out=None, workspace: Workspace | None = None, device=None, spl
     """read_batch on one file -> its image dict (coefs, quants, hsamp, vsamp, colorspace, image_size, huffman,
     restart_interval, status) with the workspace used under `workspace`; split as read_batch takes it"""
     r = _read_batch([data], None if out is None else [out], workspace, device, "read", split)
+    return dict(r["images"][0], workspace=r["workspace"])
+
+
+# ---- reading a progressive file into coefficient tensors (qs_hip_read_prog_device_batch) -----------------------------------
+
+def read_progressive_batch(datas, *, outs=None, workspace: Workspace | None = None, device=None) -> dict:
+    """Read PROGRESSIVE JPEG files (SOF2, Huffman, 8 bits: cjpeg -progressive, jpegtran -progressive, this package's
+    encode_file(scans=...)) into device coefficient tensors on the current stream: what libjpeg 9's
+    jpeg_read_coefficients leaves in its arrays.  One lane reads one restart interval of one scan, and scans that
+    depend on each other -- a refinement on the scans it refines -- run in successive launches, one per level of the
+    script (three for libjpeg's ten-scan script).  Files with restart intervals and batches are the workload; a file
+    without DRI is read by one lane per scan, and refused when a scan has more than 32 768 blocks in an interval.
+
+    datas, outs, workspace, device and the result are read_batch's.  The whole file is parsed on the host
+    (jpeg_file.parse_progressive: markers only), so a device tensor is copied to the host once -- never inside a graph
+    capture, where the workspace's stored headers are used: the files must then be device tensors with the header layout
+    of the files the workspace was prepared with (the same tables, scans and offsets; a file whose scans start elsewhere
+    ends with status 1).  images[i] holds read_batch's fields with huffman=None (the tables are per scan), scans (the
+    script, as encode_file(scans=...) takes it) and restart_interval (the first scan's DRI value).  status: 0 ok; 1 the
+    RSTn markers of a scan do not fit its interval, or a scan does not start at its prepared offset; 2 an interval with
+    too few or too many bytes, or a file that stops inside a scan; 3 bits without a code, a run past the band's end or
+    past the interval's blocks; the arrays are then unspecified."""
+    return _read_progressive_batch(datas, outs, workspace, device, "read_progressive_batch")
+
+
+def _read_progressive_batch(datas, outs, workspace, device, who):
+    import torch
+    from . import jpeg_file
+    if not isinstance(datas, (list, tuple)) or not datas:
+        raise ValueError(f"{who}: datas must be a non-empty list of files")
+    if outs is not None and len(outs) != len(datas):
+        raise ValueError(f"{who}: one output list (or None) per file")
+    for i, d in enumerate(datas):
+        if isinstance(d, torch.Tensor):
+            if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_contiguous():
+                raise TypeError(f"{who}: file {i} must be a contiguous one-dimensional uint8 tensor")
+        elif not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError(f"{who}: a file is bytes or a contiguous one-dimensional uint8 tensor")
+    capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        if workspace is None or getattr(workspace, "headers", None) is None or len(workspace.headers) != len(datas) \
+                or workspace.headers[0].get("sof") != 0xC2:
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on files with "
+                               f"the same headers (workspace=...): parsing a file copies it to the host")
+        if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
+            raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
+        headers = workspace.headers
+    else:
+        headers = [jpeg_file.parse_progressive(d.cpu().numpy().tobytes() if isinstance(d, torch.Tensor) else bytes(d))
+                   for d in datas]
+    dev = next((d.device for d in datas if isinstance(d, torch.Tensor) and d.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    hip = _hip()
+    bufs, jobs, opts, images = [], [], [], []
+    for i, (d, p) in enumerate(zip(datas, headers)):
+        if isinstance(d, torch.Tensor):
+            if d.is_cuda and d.device != dev:
+                raise ValueError(f"{who}: file {i} is on {d.device}, the batch on {dev}")
+            buf = d if d.is_cuda else d.to(dev, non_blocking=True)
+        else:
+            buf = torch.frombuffer(bytearray(d), dtype=torch.uint8).to(dev)
+        bufs.append(buf)
+        n = len(p["hsamp"])
+        w, h = p["image_size"]
+        mh, mv = max(p["hsamp"]), max(p["vsamp"])
+        shapes = [(-(-h * p["vsamp"][ci] // (8 * mv)), -(-w * p["hsamp"][ci] // (8 * mh))) for ci in range(n)]
+        if outs is None or outs[i] is None:
+            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
+        else:
+            coefs = list(outs[i])
+            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
+                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
+        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], [None] * n,
+                                   hsamp=p["hsamp"], vsamp=p["vsamp"], colorspace=p["colorspace"] or 1, image_size=(w, h)))
+        opts.append(hip.read_prog_opts(p["scans"]))
+        images.append(dict(coefs=coefs, quants=[q.copy() for q in p["quants"]], hsamp=list(p["hsamp"]),
+                           vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), huffman=None,
+                           scans=list(p["script"]), restart_interval=p["scans"][0]["restart_interval"]))
+    _per, total = hip.read_prog_batch_info(jobs, opts)
+    key = ("read-prog",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o._scans) for o in opts)
+    if workspace is None:
+        workspace = Workspace()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if workspace.key != key:
+        if capturing:
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
+                               f"geometry, scans and tables (workspace=...): preparing one synchronises")
+        if workspace.nbytes < total or workspace.buf.device != dev:
+            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        hip.read_prog_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream)
+        workspace.key = key
+    workspace.headers = headers
+    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+    hip.read_prog_batch(jobs, [b.data_ptr() for b in bufs], [b.numel() for b in bufs], status.data_ptr(),
+                        workspace.buf.data_ptr(), workspace.nbytes, stream)
+    for i, im in enumerate(images):
+        im["status"] = status[i:i + 1]
+    return dict(images=images, status=status, workspace=workspace)
+
+
+def read_progressive(data, *, out=None, workspace: Workspace | None = None, device=None) -> dict:
+    """read_progressive_batch on one file -> its image dict with the workspace used under `workspace`"""
+    r = _read_progressive_batch([data], None if out is None else [out], workspace, device, "read_progressive")
     return dict(r["images"][0], workspace=r["workspace"])
 
 

@@ -49,6 +49,15 @@ restart option; where the interval route accepts the same file its time on it is
 (interval_route_read_ms, null where it refuses the file), and both must give the arrays encoded.  --no-host leaves
 libjpeg's read out.
 
+--read --progressive [--script simple] times the progressive route of the scan reader (torch_qs.read_progressive_batch:
+one lane per restart interval of one scan, one decode launch per level of the script) on the same three cases, on
+progressive files the device progressive coder wrote with --restart N / --restart-rows N or without either (then one
+lane reads each scan: the case the route is expected to lose): the upload of the file plus the read, and the read
+alone, next to the host route on the same file -- libjpeg 9's jpeg_read_coefficients on one core plus the pinned upload
+of the coefficient arrays.  A file the route refuses (an interval over the cap) is reported as refused; --batch-only --width 1280 --height 720
+runs the batch case alone at a size the route reads without DRI.  Exits non-zero
+unless the arrays read are the arrays encoded.
+
 --compress times the device compress of pixels (torch_qs.compress_batch, one launch per batch, quality 50 tables) on the
 same three cases, as time per call and GB/s of pixels read plus coefficients written, next to the decode of the arrays
 it wrote (the same bytes the other way) and the host route it replaces: libjpeg 9's jpeg_write_scanlines on one core
@@ -59,7 +68,7 @@ route and the comparison, tests/libjpeg9_compress_fancy.c) and reports whether e
 mode's: the gray case must.
 
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
-                                       [--decode | --encode [--optimize-files | --progressive [--script simple]] | --read [--split] [--no-host] | --compress]
+                                       [--decode | --encode [--optimize-files | --progressive [--script simple]] | --read [--split | --progressive [--script simple]] [--no-host] | --compress]
                                        [--restart N | --restart-rows N]
                                        [--downsampling box|dct] [--upsampling dct|triangle]"""
 import argparse
@@ -100,12 +109,17 @@ def main():
     ap.add_argument("--upsampling", choices=["dct", "triangle"], default="dct",
                     help="--decode: dct (libjpeg 9's DCT-scaled chroma) or triangle (libjpeg-turbo's triangle filters)")
     ap.add_argument("--no-host", action="store_true", help="--read: do not time libjpeg's read of the file")
+    ap.add_argument("--batch-only", action="store_true",
+                    help="--read --progressive: only the batch of --images files of --width x --height (a size under the "
+                         "interval cap shows the file without DRI: 1280 x 720)")
     ap.add_argument("--compress", action="store_true", help="time the device compress of pixels instead")
     ap.add_argument("--downsampling", choices=["box", "dct"], default="box",
                     help="--compress: box (do_fancy_downsampling = FALSE) or dct (libjpeg 9's default)")
     a = ap.parse_args()
     if a.compress:
         return bench_compress(a)
+    if a.read and a.progressive:
+        return bench_read_progressive(a)
     if a.read:
         return bench_read(a)
     if a.decode:
@@ -715,6 +729,123 @@ def bench_read(a):
     bad = [r["case"] for r in out["results"] if not r["identical"]]
     if bad:
         raise SystemExit(f"bench_device_batch --read: {bad}: the arrays read are not the arrays encoded")
+
+
+def bench_read_progressive(a):
+    import tempfile
+    import numpy as np
+    import torch
+    import jpegqs_pkg
+    sys.path.insert(0, str(ROOT / "tests"))
+    from decode_oracle import LibJpeg9, synth_image
+    rst = dict(restart_interval=a.restart, restart_in_rows=a.restart_rows) if a.restart or a.restart_rows else {}
+    pkg = jpegqs_pkg.load()
+    torch_qs, jpeg_file = pkg.torch_qs, pkg.jpeg_file
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_batch: no GPU visible (this tool measures the device only)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(1)
+    cases = [("8192x8192_gray", [synth_image(rng, (8192, 8192), [1], [1], 1, amp=30)]),
+             ("8192x8192_420", [synth_image(rng, (8192, 8192), [2, 1, 1], [2, 1, 1], 3, amp=30)]),
+             (f"{a.images}x{a.width}x{a.height}_420",
+              [synth_image(rng, (a.width, a.height), [2, 1, 1], [2, 1, 1], 3, amp=30)] * a.images)]
+    if a.batch_only:
+        cases = cases[2:]
+    out = dict(tool="bench_device_batch", leg="read_progressive", script=a.script, device=torch.cuda.get_device_name(dev),
+               restart=rst, results=[])
+    for name, ims in cases:
+        im = ims[0]
+        n = len(im["coefs"])
+        script = jpeg_file.simple_progression(n, im["colorspace"]) if a.script == "simple" else jpeg_file.spectral_script(n)
+        coefs = [torch.from_numpy(c).to(dev) for c in im["coefs"]]
+        w = torch_qs.encode_file(coefs, im["quants"], hsamp=im["hsamp"], vsamp=im["vsamp"], colorspace=im["colorspace"],
+                                 image_size=im["image_size"], scans=script, refinement=True, **rst)
+        torch.cuda.synchronize()
+        if int(w["status"][0]) != 0:
+            raise SystemExit(f"bench_device_batch --read --progressive: {name}: the coder ended with status {int(w['status'][0])}")
+        data = w["file"][:int(w["len"][0])].cpu().numpy().tobytes()
+        del w
+        header = jpeg_file.parse_progressive(data)
+        row = dict(case=name, images=len(ims), file_bytes=len(data) * len(ims), scans=len(script),
+                   coef_mbytes=round(sum(c.numel() * 2 for c in coefs) * len(ims) / 1e6, 1))
+        info_job = [pkg.HipQS.device_job([1] * n, [tuple(c.shape[:2]) for c in coefs], [None] * n, hsamp=im["hsamp"],
+                                         vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"])]
+        try:
+            per, _ = pkg.HipQS().read_prog_batch_info(info_job, [pkg.HipQS.read_prog_opts(header["scans"])])
+        except pkg.hipqs.QsHipError as e:
+            row.update(refused=str(e), identical=True)
+            out["results"].append(row)
+            continue
+        pinned = [torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory() for _ in ims]
+        on_dev = [p.to(dev) for p in pinned]
+        ws = torch_qs.Workspace()
+        r = torch_qs.read_progressive_batch(on_dev, workspace=ws)
+        outs = [x["coefs"] for x in r["images"]]
+        status = r["status"].cpu().tolist()
+        identical = status == [0] * len(ims) and all(torch.equal(g, c) for o in outs for g, c in zip(o, coefs))
+        g = torch.cuda.CUDAGraph()                                      # the read alone: no host work per call
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g):
+            torch_qs.read_progressive_batch(on_dev, outs=outs, workspace=ws)
+
+        def device_route():
+            for p, d in zip(pinned, on_dev):
+                d.copy_(p, non_blocking=True)
+            g.replay()
+            torch.cuda.synchronize()
+
+        def kernels_only():
+            g.replay()
+            torch.cuda.synchronize()
+
+        host_pinned = [[torch.from_numpy(c).pin_memory() for c in im["coefs"]] for _ in ims]
+        dst = [[torch.empty_like(c) for c in coefs] for _ in ims]
+
+        def coef_upload():
+            for hp, d in zip(host_pinned, dst):
+                for h, t in zip(hp, d):
+                    t.copy_(h, non_blocking=True)
+            torch.cuda.synchronize()
+
+        def med(fn, calls):
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                ms.append((time.perf_counter() - t0) * 1e3 / calls)
+            return round(float(np.median(ms)), 3), [round(m, 3) for m in ms]
+
+        k_ms, k_all = med(kernels_only, 1)
+        dev_ms, dev_all = med(device_route, 1 if k_ms > 50 else 3)
+        up_ms, _ = med(coef_upload, 3)
+        row.update(levels=per[0]["levels"], lanes_per_scan=per[0]["intervals"], restart_interval=header["scans"][0]["restart_interval"],
+                   device_upload_plus_read_ms=dev_ms, device_windows=dev_all, device_read_ms=k_ms, device_read_windows=k_all,
+                   host_coef_upload_ms=up_ms, identical=bool(identical))
+        del g
+        if not a.no_host:
+            with tempfile.TemporaryDirectory() as td:
+                lj9 = LibJpeg9(Path(td))
+                f = Path(td) / "in.jpg"
+                f.write_bytes(data)
+                arrays = Path(td) / "out.bin"
+                lj9._run("read", f, arrays)                             # the helper alone: it writes the arrays to a file
+                ts = []
+                for _ in range(min(a.repeats, 3)):
+                    t0 = time.perf_counter()
+                    lj9._run("read", f, arrays)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                row["host_libjpeg9_read_ms_per_image"] = round(float(np.median(ts)), 1)
+            row["host_route_ms"] = round(up_ms + row["host_libjpeg9_read_ms_per_image"] * len(ims), 1)
+            row["device_over_host_route"] = round(dev_ms / row["host_route_ms"], 2)
+        out["results"].append(row)
+    print(json.dumps(out), flush=True)
+    bad = [r["case"] for r in out["results"] if not r["identical"]]
+    if bad:
+        raise SystemExit(f"bench_device_batch --read --progressive: {bad}: the arrays read are not the arrays encoded")
 
 
 def bench_compress(a):
