@@ -306,6 +306,33 @@ int qs_hip_decode_device_batch_info_opts(qs_hip_job *const *jobs, int njobs, con
 		qs_hip_decode_info *per_job, size_t *workspace_bytes);
 int qs_hip_decode_device_batch_prepare_opts(qs_hip_job *const *jobs, int njobs, const qs_hip_decode_opts *const *opts,
 		void *d_workspace, size_t bytes, void *stream);
+/* Reduced sizes, chosen per job through info / prepare with a second options record: what libjpeg 9 hands out with
+ * scale_num = 1, scale_denom = 2, 4 or 8 (JDCT_ISLOW, defaults), bit for bit.  The output is
+ * ceil(image_width * M / 8) x ceil(image_height * M / 8) samples with M = 8 / scale_denom, and libjpeg 9 sizes each
+ * component's IDCT so that no chroma upsampling is left (widths x heights, as in jidctint.c's names):
+ *   luma, grayscale, 1x1 chroma   M x M     jpeg_idct_4x4, _2x2, _1x1
+ *   chroma under 2x2 luma         2M x 2M   jpeg_idct_islow, _4x4, _2x2
+ *   chroma under 2x1 luma         2M x M    jpeg_idct_8x4, _4x2, _2x1
+ *   chroma under 1x2 luma         M x 2M    jpeg_idct_4x8, _2x4, _1x2
+ *   chroma under 4x1 luma         2M x M, then each column twice
+ * Only the top-left coefficients those IDCTs take are read.  Layouts, arrays, d_stop and the two geometries of a job
+ * with replacement chroma are those of the full-size decode.  per_job[i].width / height report the scaled output, so
+ * buffers are sized from info as before.  opts NULL or opts[i] NULL: full size, QS_HIP_UPSAMPLE_DCT.  scale_denom
+ * outside {1, 2, 4, 8}: QS_HIP_EINVAL.  QS_HIP_UPSAMPLE_TRIANGLE with scale_denom != 1: QS_HIP_ENOTSUP (a limit: at
+ * reduced sizes libjpeg-turbo runs jidctred.c's own kernels before its filters, a contract this library does not
+ * carry); libjpeg 9's other denominators (scale_num / scale_denom = k / 8 for k = 3, 5, 6, 7, 9 .. 16) are not offered
+ * either.  One batch may mix denominators and, at denominator 1, both upsampling modes.  The run call is unchanged and
+ * still makes launches only: at most two per QS_HIP_DECODE_CHUNK jobs (the chunk's full-size jobs, its reduced ones).
+ * It takes the scales of the last prepare of d_workspace made through this library instance (the 256 most recently
+ * prepared workspaces are remembered; any other runs at full size) and checks out_pitch against the scaled width. */
+typedef struct {
+	int32_t upsampling;   /* QS_HIP_UPSAMPLE_* */
+	int32_t scale_denom;  /* 1, 2, 4 or 8 */
+} qs_hip_decode_scale_opts;
+int qs_hip_decode_device_batch_info_scaled(qs_hip_job *const *jobs, int njobs,
+		const qs_hip_decode_scale_opts *const *opts, qs_hip_decode_info *per_job, size_t *workspace_bytes);
+int qs_hip_decode_device_batch_prepare_scaled(qs_hip_job *const *jobs, int njobs,
+		const qs_hip_decode_scale_opts *const *opts, void *d_workspace, size_t bytes, void *stream);
 
 /* ---- device entropy coder (the coefficient arrays of device-resident jobs -> the bytes of a baseline JPEG scan) ----
  * What libjpeg 9 writes between the SOS header and EOI when jpeg_write_coefficients gets the same arrays (jchuff.c:
@@ -745,6 +772,7 @@ const char *qs_hip_last_error(void);
  * qs_hip_device_info and its three calls, the device batch calls, qs_hip_decode_info and the device decode, the device entropy coder, the device scan reader, the device compress,
  * qs_hip_huff_optimal_device and the whole-file run qs_hip_encode_device_batch_files, the _opts calls of the compress,
  * the split route of the scan reader qs_hip_read_split_device_batch and its two calls, the _opts calls of the decode,
+ * its _scaled calls with qs_hip_decode_scale_opts,
  * the progressive route of the scan reader qs_hip_read_prog_device_batch and its two calls).
  * A caller built against
  * this header can compare QS_HIP_ABI_VERSION with what the loaded library reports. */

@@ -67,7 +67,7 @@ def main(path):
 SPLIT_READ_KERNELS = ("qrs_map", "qrs_decode", "qrs_count", "qrs_tile_scan", "qrs_write", "qrs_dc_tiles", "qrs_dc_write")
 # the decode to pixels (qs_kernels_decode.hip): a lane's block, its IDCT workspace and the rows of the triangle filter
 # are arrays indexed by unrolled loops -- they stay in registers only as long as every index is a constant
-DECODE_KERNELS = ("qs_decode_kernel",)
+DECODE_KERNELS = ("qs_decode_kernel", "qs_decode_scaled_kernel")     # (the second: the reduced sizes' kernel)
 # the progressive run (qs_kernels_encode_prog.inc): a lane's block is an array indexed by an unrolled walk over the band,
 # whose bounds are run-time values -- it stays in registers only as long as every index is a constant
 PROG_KERNELS = ("qp_begin", "qp_nofile", "qp_flags", "qp_headscan", "qp_runs", "qp_size", "qp_emit", "qp_frame",

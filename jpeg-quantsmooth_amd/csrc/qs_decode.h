@@ -16,9 +16,11 @@
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define QS_DEC_HD __host__ __device__ inline
+#define QS_DEC_HDF __host__ __device__ __forceinline__   // (the scaled kernel's functions: no calls, no stack)
 #define QD_UNROLL _Pragma("unroll")
 #else
 #define QS_DEC_HD static inline
+#define QS_DEC_HDF static inline
 #define QD_UNROLL
 #endif
 
@@ -51,6 +53,10 @@ struct QsDecJob {
   int32_t tile0, tiles;          // first workgroup of this job in its chunk's launch, and how many it has
   uint16_t q[3][64];             // the components' tables (natural order)
 };
+// The reduced sizes (section 12.2) keep the record's size: a job at scale_denom 2, 4 or 8 carries the denominator in the
+// high byte of `upsampling` (QS_DEC_UP_DCT + 256 * scale_denom), width x height are its scaled output, and tiles == 0 --
+// the full-size kernel, which reads `upsampling` only for a job with tiles, steps over it.  The scaled kernel derives the
+// job's tiles from width x height and takes the job's first workgroup from the kernel arguments (QsDecPtrs::stile0).
 
 // What addresses caller memory travels in the kernel arguments of the run call, one chunk of jobs per launch, so the
 // kernel bounds every access by them (a workspace that does not match the run gives wrong pixels, never a stray
@@ -62,7 +68,7 @@ struct QsDecPtrs {
   int64_t pitch;
   int32_t width, height;         // the output extent the caller gave
   int32_t nblk[5];               // blocks in each array
-  int32_t pad;
+  int32_t stile0;                // first workgroup of this job in the chunk's scaled launch (the full-size kernel ignores it)
 };
 struct QsDecArgs {
   const QsDecJob* jobs;          // the chunk's descriptors (workspace)
@@ -336,4 +342,255 @@ QS_DEC_HD void qd_tri_column_any(int hs, int vs, const uint8_t* c, int stride, i
 // least one sample inside the downsampled size (every clamped index falls into such a block).
 QS_DEC_HD bool qd_tri_block_needed(int bx, int by, int Wc, int Hc) {
   return bx >= 0 && by >= 0 && bx * 8 < Wc && by * 8 < Hc;
+}
+
+// ---- libjpeg 9's reduced sizes: scale_denom 2, 4, 8 ------------------------------------------
+// With scale 1/N a luma block gives M x M samples (M = 8 / N) and libjpeg 9 picks each component's IDCT so that no
+// upsampling is left (jdmaster.c: DCT_h_scaled_size x DCT_v_scaled_size; 4x1 keeps its 2x replication):
+//   luma / gray / 1x1 chroma  M x M          jpeg_idct_4x4, _2x2, _1x1
+//   2x2 chroma                2M x 2M        jpeg_idct_islow (8x8), _4x4, _2x2
+//   2x1 chroma                2M x M         jpeg_idct_8x4, _4x2, _2x1      (names are width x height)
+//   1x2 chroma                M x 2M         jpeg_idct_4x8, _2x4, _1x2
+//   4x1 chroma                2M x M, each column twice
+// A PW x PH IDCT reads the block's top-left PW columns x PH rows and nothing else.
+//
+// Numerical contract, function by function (INT32 is long, DEQUANTIZE an int product):
+//   4x4, 8x4  pass 1 (4-point columns): ws = (int)(((a +- b) << 2) + ((odd + 2^10) >> 11)), odd the c2 / c6 rotation of
+//             rows 1 and 3.  The even term is linear, so its low 32 bits are those of the wrapping form; the odd term
+//             needs bits 11..42 of its sum: wrapping 32 bits when the sum fits int32, else 64 bits.  Its matrix rows
+//             are (10703, 4433) and (4433, -10704) [FIX(0.541196100) + FIX(0.765366865), FIX(0.541196100),
+//             FIX(0.541196100) - FIX(1.847759065)]: L1 norm 15137, and 15137 * x + 2^10 <= 2^31 - 1 holds up to
+//             x = 141869 = QS_DEC_FAST_BOUND4 on |dq| of rows 1 and 3 (tests/decode_scaled_host.cpp prints the norm).
+//             pass 2 (4-point or 8-point rows, >> 18, & 1023): the sum modulo 2^28, wrapping 32 bits always.
+//   4x8       pass 1 is jpeg_idct_islow's 8-point column: QS_DEC_FAST_BOUND as at full size; pass 2 as above.
+//   4x2, 2x4  the workspace is INT32 and nothing is shifted before the end: ((...) >> 16) & 1023 takes the sum modulo
+//             2^26, wrapping 32 bits in both passes.
+//   2x2, 2x1, 1x2, 1x1  sums of dequantised values plus (RANGE_CENTER << 3) + 4, then (>> 3) & 1023: modulo 2^13.
+#define QS_DEC_FAST_BOUND4 141869
+
+// the 4-point kernels' odd part: z1 = (z2 + z3) * c6 + bias; o[0] = z1 + z2 * (c2 - c6), o[1] = z1 - z3 * (c2 + c6)
+template <class T>
+QS_DEC_HDF void qd_idct4_odd(T z2, T z3, T bias, T* o) {
+  const T z1 = (z2 + z3) * (T)QD_FIX(0.541196100) + bias;
+  o[0] = z1 + z2 * (T)QD_FIX(0.765366865);
+  o[1] = z1 - z3 * (T)QD_FIX(1.847759065);
+}
+
+// One 4-point row / column whose even part is shifted by CONST_BITS (pass 2 of 4x4, 4x8, 4x2; pass 1 of 2x4).  dc_bias
+// is added to in[0] before the shift.  Wrapping arithmetic.
+QS_DEC_HDF void qd_idct4(const uint32_t* in, uint32_t dc_bias, uint32_t* out) {
+  const uint32_t t0 = in[0] + dc_bias, t2 = in[2];
+  const uint32_t t10 = (t0 + t2) << 13, t12 = (t0 - t2) << 13;
+  uint32_t o[2];
+  qd_idct4_odd<uint32_t>(in[1], in[3], 0u, o);
+  out[0] = t10 + o[0]; out[3] = t10 - o[0];
+  out[1] = t12 + o[1]; out[2] = t12 - o[1];
+}
+
+// One 4-point column of pass 1 of jpeg_idct_4x4 / _8x4: the even part << PASS1_BITS, the odd part descaled on its own.
+QS_DEC_HDF void qd_idct4_pass1(const int32_t* in, bool fast, int32_t* ws) {
+  const uint32_t e0 = ((uint32_t)in[0] + (uint32_t)in[2]) << 2, e1 = ((uint32_t)in[0] - (uint32_t)in[2]) << 2;
+  uint32_t o0, o1;
+  if (fast) {
+    uint32_t o[2];
+    qd_idct4_odd<uint32_t>((uint32_t)in[1], (uint32_t)in[3], 1u << 10, o);
+    o0 = (uint32_t)((int32_t)o[0] >> 11); o1 = (uint32_t)((int32_t)o[1] >> 11);
+  } else {
+    int64_t o[2];
+    qd_idct4_odd<int64_t>(in[1], in[3], (int64_t)1 << 10, o);
+    o0 = (uint32_t)(o[0] >> 11); o1 = (uint32_t)(o[1] >> 11);      // (int) of libjpeg's INT32 sum: its low 32 bits
+  }
+  ws[0] = (int32_t)(e0 + o0); ws[3] = (int32_t)(e0 - o0);
+  ws[1] = (int32_t)(e1 + o1); ws[2] = (int32_t)(e1 - o1);
+}
+
+// pass-2 bias of the kernels whose pass 1 scales by PASS1_BITS, added to in[0] before the shift (qd_idct4)
+#define QD_PASS2_BIAS4 ((512u << 5) + (1u << 4))
+// (RANGE_CENTER << 3) + (1 << 2): the 2- and 1-point forms and 4x2, whose pass 1 does not scale
+#define QD_BIAS3 ((512u << 3) + (1u << 2))
+
+// The block's top-left PW columns x PH rows, dequantised: dq[r * PW + c].  One load of PW * 2 bytes per row (src is a
+// block of a 16-byte aligned array: row r lies 16 * r bytes in).
+template <int PW, int PH>
+QS_DEC_HDF void qd_load_sub(const int16_t* src, const uint16_t* q, int32_t* dq) {
+  QD_UNROLL
+  for (int r = 0; r < PH; ++r) {
+    struct alignas(PW * 2) Row { int16_t v[PW]; };
+    const Row row = *reinterpret_cast<const Row*>(src + r * 8);
+    QD_UNROLL
+    for (int c = 0; c < PW; ++c) dq[r * PW + c] = (int32_t)row.v[c] * (int32_t)q[r * 8 + c];
+  }
+}
+
+// jpeg_idct_<PW>x<PH> on qd_load_sub's values: PH rows of PW samples into dst (row stride `stride`), each column
+// written XREP times.  (8x8 is qd_idct_block<false, false>.)
+template <int PW, int PH, int XREP = 1>
+QS_DEC_HDF void qd_idct_scaled(const int32_t* dq, uint8_t* dst, int stride) {
+  auto put = [&](int r, int c, uint8_t s) {
+    QD_UNROLL
+    for (int k = 0; k < XREP; ++k) dst[r * stride + c * XREP + k] = s;
+  };
+  if constexpr (PW <= 2 && PH <= 2) {
+    const uint32_t a = (uint32_t)dq[0] + QD_BIAS3;
+    if constexpr (PW == 1 && PH == 1) {
+      put(0, 0, qd_limit(a >> 3));
+    } else if constexpr (PW * PH == 2) {                   // 2x1: dq[1] is column 1; 1x2: dq[1] is row 1
+      put(0, 0, qd_limit((a + (uint32_t)dq[1]) >> 3));
+      put(PW == 2 ? 0 : 1, PW == 2 ? 1 : 0, qd_limit((a - (uint32_t)dq[1]) >> 3));
+    } else {
+      const uint32_t t0 = a + (uint32_t)dq[2], t2 = a - (uint32_t)dq[2];
+      const uint32_t t1 = (uint32_t)dq[1] + (uint32_t)dq[3], t3 = (uint32_t)dq[1] - (uint32_t)dq[3];
+      put(0, 0, qd_limit((t0 + t1) >> 3)); put(0, 1, qd_limit((t0 - t1) >> 3));
+      put(1, 0, qd_limit((t2 + t3) >> 3)); put(1, 1, qd_limit((t2 - t3) >> 3));
+    }
+  } else if constexpr (PW == 4 && PH == 2) {
+    QD_UNROLL
+    for (int r = 0; r < 2; ++r) {
+      uint32_t in[4], o[4];
+      QD_UNROLL
+      for (int c = 0; c < 4; ++c) in[c] = r ? (uint32_t)dq[c] - (uint32_t)dq[4 + c] : (uint32_t)dq[c] + (uint32_t)dq[4 + c];
+      qd_idct4(in, QD_BIAS3, o);
+      QD_UNROLL
+      for (int c = 0; c < 4; ++c) put(r, c, qd_limit(o[c] >> 16));
+    }
+  } else if constexpr (PW == 2 && PH == 4) {
+    uint32_t ws[4][2];
+    QD_UNROLL
+    for (int c = 0; c < 2; ++c) {
+      uint32_t in[4], o[4];
+      QD_UNROLL
+      for (int k = 0; k < 4; ++k) in[k] = (uint32_t)dq[k * 2 + c];
+      qd_idct4(in, 0u, o);
+      QD_UNROLL
+      for (int r = 0; r < 4; ++r) ws[r][c] = o[r];
+    }
+    QD_UNROLL
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t t = ws[r][0] + ((512u << 16) + (1u << 15));
+      put(r, 0, qd_limit((t + ws[r][1]) >> 16));
+      put(r, 1, qd_limit((t - ws[r][1]) >> 16));
+    }
+  } else {
+    static_assert((PH == 4 && (PW == 4 || PW == 8)) || (PH == 8 && PW == 4), "4x4, 8x4, 4x8");
+    int32_t ws[PH][PW];
+    int32_t mx = 0;
+    QD_UNROLL
+    for (int i = 0; i < PW * PH; ++i) {
+      if (PH == 4 && !((i / PW) & 1)) continue;            // (4-point pass 1: rows 1 and 3 alone bear on the choice)
+      const int32_t a = dq[i] < 0 ? -dq[i] : dq[i];
+      mx = a > mx ? a : mx;
+    }
+    const bool fast = mx <= (PH == 4 ? QS_DEC_FAST_BOUND4 : QS_DEC_FAST_BOUND);
+    QD_UNROLL
+    for (int c = 0; c < PW; ++c) {                         // pass 1: columns
+      if constexpr (PH == 4) {
+        int32_t in[4], o[4];
+        QD_UNROLL
+        for (int k = 0; k < 4; ++k) in[k] = dq[k * PW + c];
+        qd_idct4_pass1(in, fast, o);
+        QD_UNROLL
+        for (int r = 0; r < 4; ++r) ws[r][c] = o[r];
+      } else if (fast) {
+        uint32_t in[8], o[8];
+        QD_UNROLL
+        for (int k = 0; k < 8; ++k) in[k] = (uint32_t)dq[k * PW + c];
+        qd_idct8<uint32_t>(in, 1u << 10, o);
+        QD_UNROLL
+        for (int r = 0; r < 8; ++r) ws[r][c] = (int32_t)o[r] >> 11;
+      } else {
+        int64_t in[8], o[8];
+        QD_UNROLL
+        for (int k = 0; k < 8; ++k) in[k] = dq[k * PW + c];
+        qd_idct8<int64_t>(in, (int64_t)1 << 10, o);
+        QD_UNROLL
+        for (int r = 0; r < 8; ++r) ws[r][c] = (int32_t)(o[r] >> 11);
+      }
+    }
+    QD_UNROLL
+    for (int r = 0; r < PH; ++r) {                         // pass 2: rows, modulo 2^32
+      uint32_t in[PW], o[PW];
+      QD_UNROLL
+      for (int k = 0; k < PW; ++k) in[k] = (uint32_t)ws[r][k];
+      if constexpr (PW == 8) qd_idct8<uint32_t>(in, QD_PASS2_BIAS, o); else qd_idct4(in, QD_PASS2_BIAS4, o);
+      QD_UNROLL
+      for (int c = 0; c < PW; ++c) put(r, c, qd_limit(o[c] >> 18));
+    }
+  }
+}
+
+template <int PW, int PH, int XREP = 1>
+QS_DEC_HDF void qd_scaled_block(const int16_t* src, const uint16_t* q, uint8_t* dst, int stride) {
+  int32_t dq[PW * PH];
+  qd_load_sub<PW, PH>(src, q, dq);
+  if constexpr (PW == 8 && PH == 8) qd_idct_block<false, false>(dq, dst, stride);
+  else qd_idct_scaled<PW, PH, XREP>(dq, dst, stride);
+}
+
+// The scaled kernel's tile: QS_DEC_TW x QS_DEC_TH output samples, a whole number of MCUs at every scale and layout.
+// Component ci's blocks cover bw x bh output samples each (luma m x m, chroma m * hs x m * vs); the tile's work items
+// are its luma blocks, then chroma 1's, then chroma 2's, in raster order: 64 / 256 / 1,024 luma blocks at m = 4 / 2 / 1.
+// output samples per luma block edge of a job: 8 / scale_denom; 0 for a record that is not one of prepare's
+QS_DEC_HDF int qd_job_m(const QsDecJob& job) {
+  const int d = job.upsampling >> 8;
+  return d == 0 ? 8 : d == 2 ? 4 : d == 4 ? 2 : d == 8 ? 1 : 0;
+}
+
+QS_DEC_HDF int qd_scaled_items(const QsDecJob& job, const QsDecGeom& g, int m) {
+  const int nl = (QS_DEC_TW / m) * (QS_DEC_TH / m);
+  return job.layout == QS_DEC_GRAY ? nl : nl + 2 * (QS_DEC_TW / (m * g.hs)) * (QS_DEC_TH / (m * g.vs));
+}
+
+// Work item `it` of the tile at (X0, Y0): one block of one component into its plane px[ci] (QS_DEC_TH rows of QS_DEC_TW).
+// width x height: the output crop (never more than the caller's extent).  A block outside the crop, the component's
+// grid or the caller's array is not read and leaves its samples unwritten (no pixel of the crop takes them).
+QS_DEC_HDF void qd_scaled_item(const QsDecJob& job, const QsDecPtrs& P, const QsDecGeom& g, int variant, int m, int width,
+                              int height, int X0, int Y0, int it, uint8_t* px) {
+  const int nl = (QS_DEC_TW / m) * (QS_DEC_TH / m);
+  const int ci = it < nl ? 0 : 1 + (it - nl) / ((QS_DEC_TW / (m * g.hs)) * (QS_DEC_TH / (m * g.vs)));
+  const int hs = ci ? g.hs : 1, vs = ci ? g.vs : 1;
+  const int bw = m * hs, bh = m * vs, nbx = QS_DEC_TW / bw;
+  const int k = ci ? (it - nl) % (nbx * (QS_DEC_TH / bh)) : it;
+  const int kx = k % nbx, ky = k / nbx;
+  const int bx = X0 / bw + kx, by = Y0 / bh + ky, x0 = kx * bw, y0 = ky * bh;
+  const int slot = variant && ci ? 2 + ci : ci;
+  if (!(X0 + x0 < width && Y0 + y0 < height && bx < g.wblk[ci] && by < g.hblk[ci] &&
+        (long long)by * g.wblk[ci] + bx < P.nblk[slot])) return;
+  const int16_t* src = P.coef[slot] + ((size_t)by * g.wblk[ci] + bx) * 64;
+  const uint16_t* q = job.q[ci];
+  uint8_t* dst = px + ((size_t)ci * QS_DEC_TH + y0) * QS_DEC_TW + x0;
+  const int pw = hs == 4 ? bw / 2 : bw;                    // 4x1: a 2m x m IDCT, each column twice
+  switch (pw * 16 + bh) {
+    case 8 * 16 + 8: qd_scaled_block<8, 8>(src, q, dst, QS_DEC_TW); break;
+    case 4 * 16 + 4: qd_scaled_block<4, 4>(src, q, dst, QS_DEC_TW); break;
+    case 2 * 16 + 2: qd_scaled_block<2, 2>(src, q, dst, QS_DEC_TW); break;
+    case 1 * 16 + 1: qd_scaled_block<1, 1>(src, q, dst, QS_DEC_TW); break;
+    case 8 * 16 + 4:
+      if (hs == 4) qd_scaled_block<8, 4, 2>(src, q, dst, QS_DEC_TW); else qd_scaled_block<8, 4>(src, q, dst, QS_DEC_TW);
+      break;
+    case 4 * 16 + 2:
+      if (hs == 4) qd_scaled_block<4, 2, 2>(src, q, dst, QS_DEC_TW); else qd_scaled_block<4, 2>(src, q, dst, QS_DEC_TW);
+      break;
+    case 2 * 16 + 1:
+      if (hs == 4) qd_scaled_block<2, 1, 2>(src, q, dst, QS_DEC_TW); else qd_scaled_block<2, 1>(src, q, dst, QS_DEC_TW);
+      break;
+    case 4 * 16 + 8: qd_scaled_block<4, 8>(src, q, dst, QS_DEC_TW); break;
+    case 2 * 16 + 4: qd_scaled_block<2, 4>(src, q, dst, QS_DEC_TW); break;
+    case 1 * 16 + 2: qd_scaled_block<1, 2>(src, q, dst, QS_DEC_TW); break;
+    default: break;                                        // (never prepared)
+  }
+}
+
+// Pixel (x, r) of the tile: its component samples -> its output samples in rows (QS_DEC_TH rows of QS_DEC_TW * 3).
+QS_DEC_HDF void qd_scaled_convert(const QsDecJob& job, const uint8_t* px, int r, int x, uint8_t* rows) {
+  const uint8_t* p = px + (size_t)r * QS_DEC_TW + x;
+  uint8_t* o = rows + (size_t)r * QS_DEC_TW * 3;
+  if (job.layout == QS_DEC_YCC) {
+    qd_ycc_rgb(p[0], p[QS_DEC_TH * QS_DEC_TW], p[2 * QS_DEC_TH * QS_DEC_TW], o + x * 3);
+  } else if (job.layout == QS_DEC_RGB) {
+    o[x * 3] = p[0];
+    o[x * 3 + 1] = p[QS_DEC_TH * QS_DEC_TW];
+    o[x * 3 + 2] = p[2 * QS_DEC_TH * QS_DEC_TW];
+  } else {
+    o[x] = p[0];
+  }
 }

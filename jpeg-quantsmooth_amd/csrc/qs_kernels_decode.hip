@@ -20,6 +20,9 @@
 //
 // Geometry and tables live in the caller's workspace (written by the prepare call); the arrays, the outputs and the
 // output extent travel in the kernel arguments (QsDecArgs), one chunk of up to QS_DEC_CHUNK jobs per launch.
+//
+// Jobs at libjpeg 9's reduced sizes (scale_denom 2, 4, 8) have no tiles in this kernel's launch: they are decoded by
+// qs_decode_scaled_kernel at the end of this file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "qs_decode.h"
@@ -149,4 +152,56 @@ qs_decode_kernel(const QsDecArgs a) {
 
 void qs_launch_decode(const QsDecArgs& a, int tiles, hipStream_t s) {
   if (tiles > 0) hipLaunchKernelGGL(qs_decode_kernel, dim3(tiles), dim3(QS_DEC_LANES), 0, s, a);
+}
+
+// The reduced sizes (scale_denom 2, 4, 8): a kernel of its own, so the full-size one keeps its
+// instructions.  A workgroup (one wave) owns QS_DEC_TW x QS_DEC_TH OUTPUT samples of one job with m < 8, i.e. 64 / m x
+// 16 / m luma blocks and the chroma blocks over them; libjpeg 9 sizes each component's IDCT so that none is upsampled
+// (qs_decode.h).  Phase 1: the lanes walk the tile's blocks (qd_scaled_item), consecutive lanes on consecutive blocks
+// of a block row; each reads the top-left PW x PH coefficients of its block and nothing else.  Phases 2 and 3 as above.
+__global__ void __launch_bounds__(QS_DEC_LANES) __attribute__((amdgpu_waves_per_eu(3)))
+qs_decode_scaled_kernel(const QsDecArgs a) {
+  __shared__ uint8_t px[3 * QS_DEC_TH * QS_DEC_TW];        // component samples of the tile
+  __shared__ uint8_t rows[QS_DEC_TH * QS_DEC_TW * 3];       // the tile's output rows
+  const QsDecJob* J = a.jobs;
+  const int tile = (int)blockIdx.x;
+  int lo = 0, hi = a.n - 1;                                // the job whose tiles hold this workgroup
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.p[mid].stile0 <= tile) lo = mid; else hi = mid - 1;
+  }
+  const QsDecJob& job = J[lo];
+  const QsDecPtrs& P = a.p[lo];
+  const int m = qd_job_m(job);
+  if (m != 1 && m != 2 && m != 4) return;                  // a full-size job (the other kernel's), or never prepared
+  if (job.width < 1 || job.height < 1 || job.width > 65500 || job.height > 65500) return;
+  const int stiles_x = (job.width + QS_DEC_TW - 1) / QS_DEC_TW, stiles = stiles_x * ((job.height + QS_DEC_TH - 1) / QS_DEC_TH);
+  const int t = tile - P.stile0;
+  if (t < 0 || t >= stiles) return;
+  const int X0 = (t % stiles_x) * QS_DEC_TW, Y0 = (t / stiles_x) * QS_DEC_TH;
+  const int variant = job.two && a.d_stop && a.d_stop[a.job0 + lo] != 0 ? 1 : 0;
+  const QsDecGeom& g = job.g[variant];
+  if ((g.hs != 1 && g.hs != 2 && g.hs != 4) || (g.vs != 1 && g.vs != 2) || g.hs * g.vs > 4) return;
+  const int width = min(job.width, P.width), height = min(job.height, P.height);
+  if ((job.nout != 1 && job.nout != 3) || P.pitch < (int64_t)width * job.nout) return;   // (a run that does not match the prepare)
+  const int lane = (int)threadIdx.x;
+
+  const int items = qd_scaled_items(job, g, m);
+  for (int it = lane; it < items; it += QS_DEC_LANES) qd_scaled_item(job, P, g, variant, m, width, height, X0, Y0, it, px);
+  __syncthreads();
+
+  const int w = min(QS_DEC_TW, width - X0), h = min(QS_DEC_TH, height - Y0);
+  if (lane < w)
+    for (int r = 0; r < h; ++r) qd_scaled_convert(job, px, r, lane, rows);
+  __syncthreads();
+
+  const int nb = w * job.nout;
+  for (int r = 0; r < h; ++r) {
+    uint8_t* out = P.out + (size_t)(Y0 + r) * P.pitch + (size_t)X0 * job.nout;
+    for (int b = lane; b < nb; b += QS_DEC_LANES) out[b] = rows[r * QS_DEC_TW * 3 + b];
+  }
+}
+
+void qs_launch_decode_scaled(const QsDecArgs& a, int tiles, hipStream_t s) {
+  if (tiles > 0) hipLaunchKernelGGL(qs_decode_scaled_kernel, dim3(tiles), dim3(QS_DEC_LANES), 0, s, a);
 }

@@ -107,6 +107,12 @@ class DecodeOpts(C.Structure):
     _fields_ = [("upsampling", C.c_int32)]
 
 
+class DecodeScaleOpts(C.Structure):
+    """qs_hip_decode_scale_opts: the chroma upsampling and the reduced size (scale_denom 1, 2, 4 or 8) of one job of the
+    device decode"""
+    _fields_ = [("upsampling", C.c_int32), ("scale_denom", C.c_int32)]
+
+
 class HuffTable(C.Structure):
     """qs_hip_huff_table: bits[l] = codes of length l, huffval = the symbols by increasing code length"""
     _fields_ = [("bits", C.c_uint8 * 17), ("huffval", C.c_uint8 * 256)]
@@ -244,6 +250,12 @@ ABI = {
     "qs_hip_decode_device_batch_prepare_opts": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
                                                            C.POINTER(C.POINTER(DecodeOpts)), C.c_void_p, C.c_size_t,
                                                            C.c_void_p]),
+    "qs_hip_decode_device_batch_info_scaled": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                          C.POINTER(C.POINTER(DecodeScaleOpts)), C.POINTER(DecodeInfo),
+                                                          C.POINTER(C.c_size_t)]),
+    "qs_hip_decode_device_batch_prepare_scaled": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int,
+                                                             C.POINTER(C.POINTER(DecodeScaleOpts)), C.c_void_p, C.c_size_t,
+                                                             C.c_void_p]),
     "qs_hip_encode_device_batch_info": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(EncodeInfo),
                                                    C.POINTER(C.c_size_t)]),
     "qs_hip_encode_device_batch_prepare": (C.c_int, [C.POINTER(C.POINTER(Job)), C.c_int, C.POINTER(C.POINTER(HuffTables)),
@@ -630,13 +642,37 @@ class HipQS:
         arr = (C.POINTER(DecodeOpts) * max(1, n))(*[C.pointer(o) if o is not None else None for o in keep])
         return arr, keep
 
-    def decode_batch_info(self, jobs, opts=None):
-        """qs_hip_decode_device_batch_info[_opts] (no device needed) -> (list of dict(width, height, channels, layout),
-        the batch's workspace bytes).  opts: None (the call without opts: every job in the dct mode), or one entry per
-        job: None, "dct", "triangle" (libjpeg-turbo's triangle-filter chroma upsampling) or a DecodeOpts"""
+    @classmethod
+    def _decode_scale_ptrs(cls, opts, scales, n):
+        """scales: one scale_denom per job (None: full size); opts as _decode_opt_ptrs takes them or None -> (the pointer
+        array of DecodeScaleOpts, what it points to)"""
+        if len(scales) != n:
+            raise ValueError(f"decode scales: {len(scales)} entries for {n} jobs")
+        _arr, modes = cls._decode_opt_ptrs([None] * n if opts is None else opts, n)
+        keep = []
+        for mode, d in zip(modes, scales):
+            if isinstance(d, DecodeScaleOpts):
+                keep.append(d)
+                continue
+            rec = DecodeScaleOpts()
+            rec.upsampling = UPSAMPLE_DCT if mode is None else mode.upsampling
+            rec.scale_denom = 1 if d is None else int(d)
+            keep.append(rec)
+        return (C.POINTER(DecodeScaleOpts) * max(1, n))(*[C.pointer(o) for o in keep]), keep
+
+    def decode_batch_info(self, jobs, opts=None, scales=None):
+        """qs_hip_decode_device_batch_info[_opts / _scaled] (no device needed) -> (list of dict(width, height, channels,
+        layout), the batch's workspace bytes).  opts: None (the call without opts: every job in the dct mode), or one
+        entry per job: None, "dct", "triangle" (libjpeg-turbo's triangle-filter chroma upsampling) or a DecodeOpts.
+        scales: None, or one scale_denom per job (1, 2, 4, 8; None = 1): libjpeg 9's reduced sizes, through the _scaled
+        call; width and height are then the scaled output's"""
         per = (DecodeInfo * max(1, len(jobs)))()
         total = C.c_size_t(0)
-        if opts is None:
+        if scales is not None:
+            arr, _keep = self._decode_scale_ptrs(opts, scales, len(jobs))
+            self._check(self.lib.qs_hip_decode_device_batch_info_scaled(self._job_ptrs(jobs), len(jobs), arr, per,
+                                                                        C.byref(total)))
+        elif opts is None:
             self._check(self.lib.qs_hip_decode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
         else:
             arr, _keep = self._decode_opt_ptrs(opts, len(jobs))
@@ -648,10 +684,14 @@ class HipQS:
     def _outs(d_out, pitch):
         return (C.c_void_p * max(1, len(d_out)))(*d_out), (C.c_size_t * max(1, len(pitch)))(*pitch)
 
-    def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, opts=None) -> None:
-        """qs_hip_decode_device_batch_prepare[_opts]: geometry, modes and tables into the workspace (synchronises
-        `stream`; not inside a capture); opts as decode_batch_info takes them"""
-        if opts is None:
+    def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, opts=None, scales=None) -> None:
+        """qs_hip_decode_device_batch_prepare[_opts / _scaled]: geometry, modes, scales and tables into the workspace
+        (synchronises `stream`; not inside a capture); opts and scales as decode_batch_info takes them"""
+        if scales is not None:
+            arr, _keep = self._decode_scale_ptrs(opts, scales, len(jobs))
+            self._check(self.lib.qs_hip_decode_device_batch_prepare_scaled(self._job_ptrs(jobs), len(jobs), arr,
+                                                                           d_workspace, nbytes, stream))
+        elif opts is None:
             self._check(self.lib.qs_hip_decode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), d_workspace, nbytes,
                                                                     stream))
         else:

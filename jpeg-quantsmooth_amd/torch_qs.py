@@ -242,13 +242,21 @@ def _upsampling(value, who):
     return value
 
 
-def _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes=None):
-    """the decode's workspace (prepared outside any capture when the geometry, tables or modes changed), the outputs,
-    the run.  modes: None (the calls without opts) or one "dct" / "triangle" per job"""
+def _scale_denom(value, who):
+    if isinstance(value, bool) or not isinstance(value, int) or value not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: scale_denom {value!r}: 1, 2, 4 or 8 (libjpeg 9's scale_num / scale_denom = 1 / N)")
+    return value
+
+
+def _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes=None, scales=None):
+    """the decode's workspace (prepared outside any capture when the geometry, tables, modes or scales changed), the
+    outputs, the run.  modes: None (the calls without opts) or one "dct" / "triangle" per job; scales: None (full size)
+    or one scale_denom per job"""
     import torch
     hip = _hip()
-    per, total = hip.decode_batch_info(jobs, modes)
-    key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs) + (() if modes is None else ("upsampling", tuple(modes)))
+    per, total = hip.decode_batch_info(jobs, modes, scales)
+    key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs) + (() if modes is None else ("upsampling", tuple(modes))) \
+        + (() if scales is None else ("scale_denom", tuple(scales)))
     if workspace is None:
         workspace = Workspace()
     if workspace.key != key:
@@ -258,7 +266,7 @@ def _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes=None):
         if workspace.nbytes < total or workspace.buf.device != dev:      # (filled in place: decode() returns no dict)
             workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
         hip.decode_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream,
-                                 modes)
+                                 modes, scales)
         workspace.key = key
     if outs is None:
         outs = [None] * len(jobs)
@@ -286,7 +294,7 @@ def _check_stop(stop, n, dev, who, torch):
 
 
 def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image_size=None, result=None, out=None,
-           workspace: Workspace | None = None, upsampling="dct"):
+           workspace: Workspace | None = None, upsampling="dct", scale_denom=1):
     """Decode coefficient tensors to pixels on the current stream, exactly as libjpeg 9 does (JDCT_ISLOW, its default
     upsampling -- 2x chroma by DCT scaling -- and default output colour space).  Returns a uint8 CUDA tensor
     (image_height, image_width, C): C = 1 for grayscale, 3 (RGB) for YCbCr and RGB images.
@@ -295,6 +303,11 @@ def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
     libjpeg 6b (what Pillow, OpenCV and torchvision decode with) -- the 8x8 IDCT at chroma resolution, then jdsample.c's
     triangle filters, and turbo's colour tables (its green is one lower than libjpeg 9's on a few (Cb, Cr) pairs).
     Grayscale and RGB-kept images without subsampling come out the same in both.  Anything else raises ValueError.
+
+    scale_denom=2, 4 or 8: what libjpeg 9 hands out with scale_num / scale_denom = 1 / N -- an image of
+    ceil(width * M / 8) x ceil(height * M / 8) samples, M = 8 / N, from IDCTs of reduced size that read only the block's
+    top-left coefficients (no full-size decode, no second pass).  Only with upsampling="dct"; any other value, or
+    "triangle" with a reduced size, raises ValueError.
 
     coefs, quants, hsamp, vsamp, colorspace: as quantsmooth_ takes them; image_size = (width, height) is required.
     result: what quantsmooth_ returned for these coefs -- its output tables and replacement chroma are used, and for
@@ -305,18 +318,21 @@ def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
     r = decode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                            image_size=image_size)],
                      result=None if result is None else dict(stop=result["stop"], images=[result]),
-                     outs=None if out is None else [out], workspace=workspace, upsampling=upsampling, _who="decode")
+                     outs=None if out is None else [out], workspace=workspace, upsampling=upsampling,
+                     scale_denom=scale_denom, _who="decode")
     return r["images"][0]
 
 
 def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None = None, upsampling="dct",
-                 _who="decode_batch") -> dict:
+                 scale_denom=1, _who="decode_batch") -> dict:
     """decode on many images in one call (one kernel launch for up to 44 images).  images[i]: a dict with decode's
     per-image arguments (coefs, quants, hsamp, vsamp, colorspace, image_size, and optionally upsampling, which overrides
     this call's upsampling= for that image: one batch may mix modes).  result: what quantsmooth_batch_ returned
     for these images, in the same order.  outs: optional preallocated outputs.  Returns dict(images=[uint8 tensors],
     workspace=Workspace).  A change of mode prepares the workspace again (outside a capture), as a change of geometry
-    does."""
+    does.  scale_denom: one value for every image or a list with one per image, and the key "scale_denom" of an image's
+    dict overrides it: one batch may mix 1, 2, 4 and 8.  outs[i] has the scaled shape, and a change of scales prepares
+    the workspace again as a change of mode does."""
     import torch
     who = _who
     _upsampling(upsampling, who)
@@ -324,8 +340,22 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
         raise ValueError(f"{who}: images must be a non-empty list of dicts")
     modes = [upsampling if not isinstance(im, dict) or im.get("upsampling") is None
              else _upsampling(im["upsampling"], f"{who}: image {i}") for i, im in enumerate(images)]
+    if isinstance(scale_denom, (list, tuple)):
+        if len(scale_denom) != len(images):
+            raise ValueError(f"{who}: scale_denom has {len(scale_denom)} entries for {len(images)} images")
+        per_image = list(scale_denom)
+    else:
+        per_image = [scale_denom] * len(images)
+    scales = [_scale_denom(d if not isinstance(im, dict) or im.get("scale_denom") is None else im["scale_denom"],
+                           f"{who}: image {i}") for i, (im, d) in enumerate(zip(images, per_image))]
+    for i, (m, d) in enumerate(zip(modes, scales)):
+        if m == "triangle" and d != 1:
+            raise ValueError(f"{who}: image {i}: upsampling \"triangle\" decodes at full size only (scale_denom {d}): at "
+                             f"reduced sizes libjpeg-turbo runs other IDCTs, which this decode does not carry")
     if all(m == "dct" for m in modes):
         modes = None                                                    # (the calls without opts)
+    if all(d == 1 for d in scales):
+        scales = None                                                   # (the calls of the full-size decode)
     for i, im in enumerate(images):
         if isinstance(im, dict) and im.get("image_size") is None:
             raise ValueError(f"{who}: image {i} has no image_size: the decode needs (width, height)")
@@ -351,7 +381,7 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
     if result is not None:
         stop = result["stop"]
         _check_stop(stop, len(images), dev, who, torch)
-    px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes)
+    px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes, scales)
     return dict(images=px, workspace=workspace)
 
 

@@ -15,7 +15,10 @@ Prints one JSON line.
 written; and, for 8192^2 4:2:0, the host alternative it replaces: the copy of the coefficients to the host plus
 libjpeg 9's single-thread decode (tests/libjpeg9_decode.c, whose time includes writing the coefficients to an in-memory
 JPEG first).  --upsampling triangle runs the same three cases in the decode's triangle mode (libjpeg-turbo's chroma
-upsampling; no host alternative is timed).
+upsampling; no host alternative is timed).  --scale-denom 2|4|8 runs them at libjpeg 9's reduced sizes (DESIGN.md
+section 12.2) and reports, per case, the full-size decode of the same arrays timed in the same session and the bytes
+the scaled decode must move (the coefficients its IDCTs take -- exact, and as the 64-byte lines holding them -- plus
+the samples out).
 
 --encode times the device entropy coder (torch_qs.encode_scan_batch with the standard tables) on the same three cases:
 the encode plus the device-to-host copy of `len` bytes, next to the host alternative it replaces -- the copy of the
@@ -70,7 +73,7 @@ mode's: the gray case must.
     python tools/bench_device_batch.py [--images 32] [--qualities 3,6] [--niter 3] [--window 1.0] [--repeats 5]
                                        [--decode | --encode [--optimize-files | --progressive [--script simple]] | --read [--split | --progressive [--script simple]] [--no-host] | --compress]
                                        [--restart N | --restart-rows N]
-                                       [--downsampling box|dct] [--upsampling dct|triangle]"""
+                                       [--downsampling box|dct] [--upsampling dct|triangle] [--scale-denom 1|2|4|8]"""
 import argparse
 import json
 import sys
@@ -108,6 +111,9 @@ def main():
                     help="--read: the split route (segments of an interval in parallel); works without a restart option")
     ap.add_argument("--upsampling", choices=["dct", "triangle"], default="dct",
                     help="--decode: dct (libjpeg 9's DCT-scaled chroma) or triangle (libjpeg-turbo's triangle filters)")
+    ap.add_argument("--scale-denom", type=int, choices=[1, 2, 4, 8], default=1,
+                    help="--decode: libjpeg 9's reduced sizes (scale_num / scale_denom = 1 / N); the full-size decode of "
+                         "the same arrays is timed in the same session, and the bytes the scaled decode must move are reported")
     ap.add_argument("--no-host", action="store_true", help="--read: do not time libjpeg's read of the file")
     ap.add_argument("--batch-only", action="store_true",
                     help="--read --progressive: only the batch of --images files of --width x --height (a size under the "
@@ -248,6 +254,38 @@ def bench_decode(a):
     out = dict(tool="bench_device_batch", leg="decode", upsampling=a.upsampling, device=torch.cuda.get_device_name(dev),
                results=[])
     mode = dict(upsampling=a.upsampling) if a.upsampling != "dct" else {}      # (dct: the call as it always was)
+    if a.scale_denom != 1:
+        mode["scale_denom"] = a.scale_denom
+        out["scale_denom"] = a.scale_denom
+
+    def windows(call):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(20):
+                call()
+            e1.record(stream)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / 20)
+        return float(np.median(ms)), [round(m, 4) for m in ms]
+
+    def scaled_traffic(im, outs_bytes):
+        """what the scaled decode must move: the coefficients its IDCTs take (exact, and as the 64-byte lines that hold
+        them: a block is two lines, rows 0..3 and 4..7) plus the samples out"""
+        m = 8 // a.scale_denom
+        hs, vs = (im["hsamp"][0], im["vsamp"][0]) if len(im["coefs"]) > 1 else (1, 1)
+        exact = lines = 0
+        for ci, c in enumerate(im["coefs"]):
+            pw, ph = (m * min(hs, 2), m * vs) if ci else (m, m)
+            nblk = c.shape[0] * c.shape[1]
+            exact += nblk * pw * ph * 2
+            lines += nblk * 64 * (2 if ph > 4 else 1)
+        return exact + outs_bytes, lines + outs_bytes
+
     for name, ims in cases:
         images = [dict(coefs=[torch.from_numpy(c).to(dev) for c in im["coefs"]], quants=im["quants"], hsamp=im["hsamp"],
                        vsamp=im["vsamp"], colorspace=im["colorspace"], image_size=im["image_size"]) for im in ims]
@@ -270,7 +308,21 @@ def bench_decode(a):
         med = float(np.median(ms))
         row = dict(case=name, images=len(images), mbytes=round(nbytes / 1e6, 1), ms=[round(m, 4) for m in ms],
                    median_ms=round(med, 4), gb_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
-        if name == "8192x8192_420" and a.upsampling == "dct":       # (libjpeg 9 is the host alternative of the dct mode)
+        if a.scale_denom != 1:
+            exact = lines = 0
+            for im, o in zip(images, outs):
+                e, l = scaled_traffic(im, o.numel())
+                exact += e
+                lines += l
+            fouts = torch_qs.decode_batch(images, workspace=torch_qs.Workspace())["images"]
+            fws = torch_qs.Workspace()
+            fmed, fms = windows(lambda: torch_qs.decode_batch(images, outs=fouts, workspace=fws))
+            row.update(must_move_mbytes=round(exact / 1e6, 1), must_move_64B_lines_mbytes=round(lines / 1e6, 1),
+                       gb_per_s_must_move=round(exact / (med * 1e-3) / 1e9, 1),
+                       gb_per_s_64B_lines=round(lines / (med * 1e-3) / 1e9, 1),
+                       full_size_ms=fms, full_size_median_ms=round(fmed, 4), full_over_scaled=round(fmed / med, 2))
+            del fouts
+        if name == "8192x8192_420" and a.upsampling == "dct" and a.scale_denom == 1:   # (libjpeg 9 is the host alternative of the dct mode)
             with tempfile.TemporaryDirectory() as td:
                 lj9 = LibJpeg9(Path(td))
                 torch.cuda.synchronize()
