@@ -232,8 +232,10 @@ def parse(data, header_only: bool = False) -> dict:
 
     Accepted: SOF0 or SOF1, 8 bits, Huffman, exactly one scan that carries all components of the frame in frame order
     with Ss = 0, Se = 63, Ah = Al = 0.  Everything else raises ValueError naming what it met: SOF2 and up, arithmetic
-    coding, 12 bits, more than one scan, a DHT or DQT between scans, a DNL.  header_only: `data` may end anywhere behind
-    the SOS header (what follows the scan is then not looked at)."""
+    coding, 12 bits, more than one scan, a DHT or DQT between scans, a DNL, fill bytes in front of an RSTn (T.81 B.1.1.2
+    allows them; the device readers do not skip them).  Fill bytes in front of the EOI behind the scan are skipped, as
+    the readers skip them.  header_only: `data` may end anywhere behind the SOS header (what follows the scan is then not
+    looked at)."""
     data = bytes(data)
     if data[:2] != b"\xff\xd8":
         raise ValueError("parse: no SOI at the start")
@@ -331,6 +333,11 @@ def parse(data, header_only: bool = False) -> dict:
             end = data.find(b"\xff", end + 1)
             if end < 0:
                 end = len(data)
+        while end + 2 < len(data) and data[end + 1] == 0xFF:
+            end += 1                                                   # fill bytes in front of the marker behind the scan
+        if end + 1 < len(data) and 0xD0 <= data[end + 1] <= 0xD7:
+            raise ValueError(f"parse: fill bytes inside a scan (FF FF in front of RST{data[end + 1] - 0xD0} at byte {end + 1}) "
+                             f"are not supported: the device readers take an RSTn marker as two bytes")
         if end + 1 < len(data) and data[end + 1] != 0xD9:
             code = data[end + 1]
             raise ValueError(f"parse: {_MARKER_NAMES.get(code, f'marker FF{code:02X}')} behind the first scan: more than "
@@ -356,7 +363,8 @@ def parse_progressive(data) -> dict:
     Accepted: exactly the files whose script passes validate_script (with either return value).  Everything else raises
     ValueError naming what it met: SOF0 / SOF1 (parse()'s files), arithmetic, lossless and differential frames, 12 bits,
     a DQT behind the first SOS, DNL, a scan that names an undefined table (a DC refinement names none), a script
-    validate_script refuses (with its scan index), no EOI behind the last scan."""
+    validate_script refuses (with its scan index), no EOI behind the last scan, fill bytes in front of an RSTn (with the
+    scan's index; fill bytes in front of any other marker are skipped)."""
     data = bytes(data)
     if data[:2] != b"\xff\xd8":
         raise ValueError("parse_progressive: no SOI at the start")
@@ -468,6 +476,13 @@ def parse_progressive(data) -> dict:
                     end = len(data)
             if end + 1 >= len(data):
                 raise ValueError(f"parse_progressive: the data ends inside scan {len(scans)}: no EOI behind the last scan")
+            fill = end
+            while fill + 2 < len(data) and data[fill + 1] == 0xFF:
+                fill += 1                                              # fill bytes in front of the marker behind the scan
+            if 0xD0 <= data[fill + 1] <= 0xD7:
+                raise ValueError(f"parse_progressive: scan {len(scans)}: fill bytes inside a scan (FF FF in front of "
+                                 f"RST{data[fill + 1] - 0xD0} at byte {fill + 1}) are not supported: the device readers "
+                                 f"take an RSTn marker as two bytes")
             scans.append(dict(comps=comps, ss=ss, se=se, ah=ah, al=al, dc_tbl=td, ac_tbl=ta, dc=dict(dc), ac=dict(ac),
                               restart_interval=int(dri), offset=pos, length=end - pos))
             pos = end
