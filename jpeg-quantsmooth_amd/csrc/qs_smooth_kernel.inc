@@ -165,6 +165,13 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
   const bool big_wave = !DIAG && __builtin_amdgcn_ballot_w64((bigacc & 0xC000C000u) != 0) != 0;   // (wave-uniform)
   // sum c*orig, sum orig*orig over the 63 AC coefficients (rebalance step); the luma walk keeps them in LDS (xreb)
   long long reb_m0 = 0, reb_m1 = 0;
+  // (luma walk) Each anti-diagonal's share of the two sums is collected in a register first and added to the 64-bit LDS
+  // sum once, behind the anti-diagonal: 14 LDS additions per sum instead of 63, and no widening per coefficient.
+  // Exact: in a wave without out-of-range coefficients |v| and |orig| stay below 9216 (|c| < 0x2000 plus less than a
+  // quantiser < 0x800, half of one more for orig), so a product is non-negative and below 2^27, and the at most 8
+  // products of an anti-diagonal add up to less than 2^30 -- no wrap in 32 bits, while the 63-term sum can pass 2^32
+  // and stays 64 bits wide.  A wave WITH such a coefficient (big_wave) ignores the walk's sums altogether.
+  uint32_t reb_a0 = 0, reb_a1 = 0;
   // Scalar operands.  Everything about coefficient k comes from its 16-byte record (QsConsts::rec); the weights
   // stream through two 16-SGPR buffers (WA / WB), one 16-float chunk per pipeline step (QS_ISSUE / QS_LAND below).
   const float* tabp = cst->tab;
@@ -353,9 +360,9 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
             reb_m0 += (long long)(c0 * c0);
             reb_m1 += (long long)(c0 * c0);
           } else {
-            qs_lds_u64* const xreb = qs_xreb(col, lds, 0);
-            qs_lds_add64(xreb, (long long)(c0 * c0));
-            qs_lds_add64(xreb + 64, (long long)(c0 * c0));
+            const uint32_t sq = (uint32_t)__mul24(c0, c0);
+            reb_a0 += sq;
+            reb_a1 += sq;
           }
         }
         asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx4 %1, %4, %5\n\ts_waitcnt lgkmcnt(0)"
@@ -527,10 +534,9 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
           if (__builtin_expect(big_wave, 0)) { asm volatile("" : "+v"(v)); v = r ? v : c0; }
           *cptr = (lds_i16)v;
           chg_any |= __builtin_amdgcn_ballot_w64(v != c0);   // v_cmp + s_or_b64: no register per lane
-          if (rebalance) {                            // wave-uniform; integer sums, exact in any order, added in LDS
-            qs_lds_u64* const xreb = qs_xreb(col, lds, 0);
-            qs_lds_add64(xreb, (long long)(v * orig));
-            qs_lds_add64(xreb + 64, (long long)(orig * orig));
+          if (rebalance) {                            // wave-uniform; integer sums, exact in any order (24-bit operands)
+            reb_a0 += (uint32_t)__mul24(v, orig);
+            reb_a1 += (uint32_t)__mul24(orig, orig);
           }
         }
       }
@@ -538,6 +544,12 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
       }             // (the branch of a coefficient that is not skipped)
     }
     kfirst = klast - 1;
+    if (!DIAG && rebalance) {   // the anti-diagonal's partial sums go to LDS (wave-uniform)
+      qs_lds_u64* const xreb = qs_xreb(col, lds, 0);
+      qs_lds_add64(xreb, (long long)(unsigned long long)reb_a0);
+      qs_lds_add64(xreb + 64, (long long)(unsigned long long)reb_a1);
+      reb_a0 = 0; reb_a1 = 0;
+    }
   }
   QS_SWAIT(WA);  // drain the last (unused) prefetch before the wave moves on
 
@@ -562,6 +574,27 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
     }
     if (m1 > m0) {
       const int mul = (int)(((m1 << 13) + (m0 >> 1)) / m0);
+      // (luma walk) The hand-shaped form: one dword -- two coefficients -- per LDS read and write at an immediate offset
+      // from the column pointer, the quantiser scalars through the scalar cache, 24-bit multiplies, and only the bound
+      // that can bind (qs_rebalance_outward, qs_devfn.h: 13 VALU instructions per coefficient where the loop below
+      // executes 20 and waits for three loads of its own; its listing shows 27, both forms of the bounds).  The
+      // proof needs a wave without out-of-range coefficients and mul < 2^15.  Every such wave has mul <= 16384 -- each
+      // term of m0 is v * orig >= orig^2 / 2, because |orig| >= div and |v - orig| <= div / 2 -- but the bound is
+      // checked, not assumed: a wave with a larger mul in any rebalancing lane takes the loop below.
+      bool outward = false;
+      if constexpr (!DIAG) outward = !big && __builtin_amdgcn_ballot_w64((uint32_t)mul > (uint32_t)QS_REB_MUL_MAX) == 0;
+      if (outward) {                                      // wave-uniform
+        typedef const __attribute__((address_space(4))) int32_t* qs_cptr;   // wave-uniform, read-only: scalar loads
+        const qs_cptr qn = (qs_cptr)(uintptr_t)cst->qn, x1n = (qs_cptr)(uintptr_t)cst->x1n, x2n = (qs_cptr)(uintptr_t)cst->x2n;
+#pragma unroll
+        for (int r = 0; r < 32; ++r) {
+          const uint32_t d = col[r * QS_LDS_PITCH];
+          const int c0 = (int16_t)(d & 0xffffu), c1 = (int32_t)d >> 16;
+          const int v0 = r ? qs_rebalance_outward(c0, mul, qn[2 * r], x1n[2 * r], x2n[2 * r]) : c0;   // (DC stays)
+          const int v1 = qs_rebalance_outward(c1, mul, qn[2 * r + 1], x1n[2 * r + 1], x2n[2 * r + 1]);
+          col[r * QS_LDS_PITCH] = ((uint32_t)v0 & 0xffffu) | ((uint32_t)v1 << 16);
+        }
+      } else {
 #pragma unroll 9
       for (int n = 1; n < 64; ++n) {
         const int c = lds_coef(col, n);
@@ -575,6 +608,7 @@ QS_SMOOTH_KERNEL_NAME(const QsConsts* __restrict__ cst, int16_t* __restrict__ co
         int v = (c * mul + 0x1000) >> 13;
         v = min(max(v, lo), hi);
         lds_set_coef(col, n, v);
+      }
       }
     }
   }
