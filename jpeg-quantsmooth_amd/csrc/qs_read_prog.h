@@ -239,7 +239,7 @@ QS_RD_HD void qrp_correct(QrBits& b, int p1, int16_t* c) {
   if (b.left < 32) qr_fill(b);
   const uint32_t bit = qr_peek(b, 1);
   b.left -= 1;
-  if (bit && (*c & p1) == 0) *c = (int16_t)(*c >= 0 ? *c + p1 : *c - p1);
+  if (bit && (*c & p1) == 0) *c = (int16_t)(*c >= 0 ? *c + p1 : *c - p1);   // (the guard: no accepted script gets here with the bit set -- a coefficient is refined only at Ah = its last Al, Al = Ah - 1, so every non-zero value is a multiple of 2 * p1)
 }
 
 // decode_mcu_AC_refine

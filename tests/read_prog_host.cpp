@@ -6,6 +6,11 @@
  * between guard margins that are checked after the run.
  *
  *   read_prog_host run in.bin out.bin
+ *   read_prog_host correct p1 coef byte [p1 coef byte ...]
+ *
+ * correct: qrp_correct on one coefficient with the one-byte stream `byte`, per triple a line "coef bits": the coefficient
+ * behind the call and the bits the call took.  No file validate_script accepts hands the function a coefficient whose bit
+ * Al is set, so its guard is pinned here, at block level.
  *
  * in.bin:  int32 ncases, then per case
  *            int32 ncomp, width, height, hsamp[4], vsamp[4], stride[4] (blocks per array row), rows[4], nscans
@@ -133,8 +138,26 @@ static int run(const char* src, const char* dst) {
   return fclose(out) != 0;
 }
 
+static int correct(int n, char** v) {
+  for (int i = 0; i + 2 < n; i += 3) {
+    const uint8_t byte = (uint8_t)atoi(v[i + 2]);
+    int16_t c = (int16_t)atoi(v[i + 1]);
+    QrSrc s;
+    s.p = &byte;
+    s.n = 1;
+    QrBits b;
+    qr_bits_init(b, s, 0, 1);
+    qr_fill(b);
+    const int before = b.left;
+    qrp_correct(b, atoi(v[i]), &c);
+    printf("%d %d\n", (int)c, before - b.left);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "run")) return run(argv[2], argv[3]);
-  fprintf(stderr, "usage: read_prog_host run in.bin out.bin\n");
+  if (argc >= 5 && (argc - 2) % 3 == 0 && !strcmp(argv[1], "correct")) return correct(argc - 2, argv + 2);
+  fprintf(stderr, "usage: read_prog_host run in.bin out.bin | correct p1 coef byte ...\n");
   return 2;
 }
