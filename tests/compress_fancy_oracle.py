@@ -3,15 +3,12 @@
 do_fancy_downsampling TRUE, and its exported jpeg_fdct_16x16 / _16x8 / _8x16 on single blocks.  Also the host build of
 both modes' arithmetic (tests/compress_fancy_host.cpp over csrc/qs_compress.h) and the cases the CPU and the GPU tests
 share.  The grid, the pixels, the tables and the comparison are those of compress_oracle.py."""
-import os
-import shutil
 import struct
 
 import numpy as np
 
-from compress_oracle import (CSRC, HERE, LAYOUTS, SIZES, Compress9, _cc, assert_same_arrays, pack, pixels,  # noqa: F401
-                             tables)
-from decode_oracle import JPEGINC, JPEGLIB
+from compress_oracle import LAYOUTS, SIZES, Compress9, assert_same_arrays, pack, pixels, tables  # noqa: F401
+from host_tools import build
 
 FANCY_SIZES = SIZES + [(31, 15), (17, 31), (63, 33)]
 KINDS = ["ones", "q50", "edge"]
@@ -60,18 +57,11 @@ class CompressFancy9(Compress9):
     def __init__(self, workdir):
         super().__init__(workdir)
         self.box_exe = self.exe
-        self.exe = self.dir / "libjpeg9_compress_fancy"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or "gcc"
-        _cc([cc, "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe), str(HERE / "libjpeg9_compress_fancy.c"),
-             str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"], "the libjpeg 9 oracle (tests/libjpeg9_compress_fancy.c)")
+        self.exe = build("libjpeg9_compress_fancy.c", libjpeg=True)
         self.fancy_host_exe = self.build_fancy_host("compress_fancy_host", [])
 
     def build_fancy_host(self, name, extra):
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or "g++"
-        exe = self.dir / name
-        _cc([cxx, "-O2", "-g", "-std=c++17", "-Wall", *extra, f"-I{CSRC}", "-o", str(exe),
-             str(HERE / "compress_fancy_host.cpp")], f"tests/compress_fancy_host.cpp ({' '.join(extra) or 'plain'})")
-        return exe
+        return self.build_host(name, extra, "compress_fancy_host.cpp")
 
     def libjpeg_box(self, px, quants, hsamp, vsamp, colorspace):
         """libjpeg 9 with do_fancy_downsampling FALSE on the same input"""
@@ -82,29 +72,14 @@ class CompressFancy9(Compress9):
             self.exe = fancy
 
     def host(self, px, quants, hsamp, vsamp, colorspace, exe=None, mode="dct"):
-        src, out = self._tmp(".bin"), self._tmp(".out")
-        src.write_bytes(pack(px, quants, hsamp, vsamp, colorspace))
-        self._run(exe or self.fancy_host_exe, "image", mode, src, out)
-        b = out.read_bytes()
-        src.unlink()
-        out.unlink()
-        _, n, w, h, cs = struct.unpack_from("<5i", b, 0)
-        off, geo = 20, []
-        for _c in range(n):
-            geo.append(struct.unpack_from("<5i", b, off))
-            off += 20 + 128
-        coefs = []
-        for wb, hb, _hs, _vs, _hq in geo:
-            coefs.append(np.frombuffer(b, np.int16, wb * hb * 64, off).reshape(hb, wb, 64).copy())
-            off += wb * hb * 128
-        return dict(coefs=coefs, hsamp=[g[2] for g in geo], vsamp=[g[3] for g in geo], colorspace=cs, image_size=(w, h))
+        return self._image(exe or self.fancy_host_exe, px, quants, hsamp, vsamp, colorspace, mode)
 
     def fdct16(self, which, shape, blocks, exe=None):
         """jpeg_fdct_<shape> ('libjpeg') or the host build's block function ('host') on blocks (n, H * W) uint8 ->
         (n, 64) int32"""
         w, h = SHAPES[shape]
         blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, w * h)
-        src, out = self._tmp(".bin"), self._tmp(".out")
+        src, out = self.tmp(".bin"), self.tmp(".out")
         src.write_bytes(struct.pack("<i", len(blocks)) + blocks.tobytes())
         self._run(self.exe if which == "libjpeg" else (exe or self.fancy_host_exe), "block", shape, src, out)
         r = np.fromfile(out, np.int32).reshape(len(blocks), 64)

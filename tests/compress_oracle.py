@@ -4,19 +4,13 @@ do_fancy_downsampling FALSE, one given table per component), read back with `lib
 jpeg_fdct_islow on single blocks.  Also the host build of the compress's own arithmetic (tests/compress_host.cpp over
 csrc/qs_compress.h) and the case grid the CPU and the GPU tests share.  If a helper cannot be built, the tests that
 need it fail."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_oracle import JPEGINC, JPEGLIB, MAGIC, LibJpeg9
-
-HERE = Path(__file__).resolve().parent
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
+from decode_oracle import LibJpeg9
+from host_tools import Tool, build, run
+from wire import header, parse_image
 
 # (name, hsamp, vsamp, colour space): every supported layout
 LAYOUTS = [("gray", [1], [1], 1)] + \
@@ -54,7 +48,7 @@ def all_colours():
 
 def pack(px, quants, hsamp, vsamp, colorspace):
     h, w, n = px.shape
-    parts = [struct.pack("<5i", MAGIC, n, w, h, colorspace)]
+    parts = [header(n, w, h, colorspace)]
     for ci in range(n):
         parts.append(struct.pack("<2i", hsamp[ci], vsamp[ci]))
         parts.append(np.asarray(quants[ci], np.uint16).tobytes())
@@ -62,45 +56,35 @@ def pack(px, quants, hsamp, vsamp, colorspace):
     return b"".join(parts)
 
 
-def _cc(cmd, what):
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode:
-        pytest.fail(f"{what} did not build:\n{r.stderr}")
-
-
-class Compress9:
-    def __init__(self, workdir: Path):
-        self.dir = Path(workdir)
+class Compress9(Tool):
+    def __init__(self, workdir):
+        super().__init__(build("libjpeg9_compress.c", libjpeg=True), workdir)
         self.lj9 = LibJpeg9(self.dir)
-        self.exe = self.dir / "libjpeg9_compress"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or "gcc"
-        _cc([cc, "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe), str(HERE / "libjpeg9_compress.c"), str(JPEGLIB),
-             f"-Wl,-rpath,{JPEGLIB.parent}"], "the libjpeg 9 oracle (tests/libjpeg9_compress.c)")
         self.host_exe = self.build_host("compress_host", [])
-        self.n = 0
 
-    def build_host(self, name, extra):
-        """tests/compress_host.cpp as a stand-alone program (extra: e.g. the sanitizer flags)"""
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or "g++"
-        exe = self.dir / name
-        _cc([cxx, "-O2", "-g", "-std=c++17", "-Wall", *extra, f"-I{CSRC}", "-o", str(exe), str(HERE / "compress_host.cpp")],
-            f"tests/compress_host.cpp ({' '.join(extra) or 'plain'})")
-        return exe
-
-    def _tmp(self, ext):
-        self.n += 1
-        return self.dir / f"c{os.getpid()}_{self.n}{ext}"
+    def build_host(self, name, extra, source="compress_host.cpp"):
+        """tests/compress_host.cpp as a stand-alone program (extra: e.g. the sanitizer flags; name: what the caller
+        calls the variant)"""
+        return build(source, flags=["-g", *extra])
 
     @staticmethod
     def _run(exe, *args):
-        r = subprocess.run([str(exe), *map(str, args)], capture_output=True, text=True)
-        if r.returncode:
-            pytest.fail(f"{Path(exe).name} {args[0]} failed ({r.returncode}): {r.stderr}")
-        return r.stdout
+        """(the program is an argument here: an object of this class runs two or four of them)"""
+        return run(exe, *args).stdout
+
+    def _image(self, exe, px, quants, hsamp, vsamp, colorspace, *mode):
+        """`image [mode] in out` of a host build -> the image dict its output holds"""
+        src, out = self.tmp(".bin"), self.tmp(".out")
+        src.write_bytes(pack(px, quants, hsamp, vsamp, colorspace))
+        self._run(exe, "image", *mode, src, out)
+        b = out.read_bytes()
+        src.unlink()
+        out.unlink()
+        return parse_image(b, with_quants=False)
 
     def libjpeg(self, px, quants, hsamp, vsamp, colorspace, keep_file=False):
         """libjpeg 9's arrays for these pixels -> the image dict of LibJpeg9.read (with 'file': the JPEG's path)"""
-        src, jpg = self._tmp(".bin"), self._tmp(".jpg")
+        src, jpg = self.tmp(".bin"), self.tmp(".jpg")
         src.write_bytes(pack(px, quants, hsamp, vsamp, colorspace))
         self._run(self.exe, "image", src, jpg)
         im = self.lj9.read(jpg)
@@ -113,27 +97,12 @@ class Compress9:
 
     def host(self, px, quants, hsamp, vsamp, colorspace, exe=None):
         """the host build of csrc/qs_compress.h on the same input -> the same dict"""
-        src, out = self._tmp(".bin"), self._tmp(".out")
-        src.write_bytes(pack(px, quants, hsamp, vsamp, colorspace))
-        self._run(exe or self.host_exe, "image", src, out)
-        b = out.read_bytes()
-        src.unlink()
-        out.unlink()
-        _, n, w, h, cs = struct.unpack_from("<5i", b, 0)
-        off, geo = 20, []
-        for _c in range(n):
-            geo.append(struct.unpack_from("<5i", b, off))
-            off += 20 + 128
-        coefs = []
-        for wb, hb, _hs, _vs, _hq in geo:
-            coefs.append(np.frombuffer(b, np.int16, wb * hb * 64, off).reshape(hb, wb, 64).copy())
-            off += wb * hb * 128
-        return dict(coefs=coefs, hsamp=[g[2] for g in geo], vsamp=[g[3] for g in geo], colorspace=cs, image_size=(w, h))
+        return self._image(exe or self.host_exe, px, quants, hsamp, vsamp, colorspace)
 
     def fdct(self, which, blocks, exe=None):
         """jpeg_fdct_islow ('libjpeg') or qc_fdct_row + qc_fdct_col ('host') on blocks (n, 64) uint8 -> (n, 64) int32"""
         blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 64)
-        src, out = self._tmp(".bin"), self._tmp(".out")
+        src, out = self.tmp(".bin"), self.tmp(".out")
         src.write_bytes(struct.pack("<i", len(blocks)) + blocks.tobytes())
         self._run(self.exe if which == "libjpeg" else (exe or self.host_exe), "block", src, out)
         return np.fromfile(out, np.int32).reshape(len(blocks), 64)

@@ -1,76 +1,31 @@
 """libjpeg 9 as the oracle of the device decode (tests/libjpeg9_decode.c, compiled on demand against the libjpeg 9 the
 rest of the suite links): whole-image decodes of coefficient arrays, and its exported IDCTs on single blocks.  No code of
 this project or of the reference is involved.  If the helper cannot be built, the tests that need it fail."""
-import os
-import shutil
-import struct
-import subprocess
-from pathlib import Path
-
 import numpy as np
-import pytest
 
-HERE = Path(__file__).resolve().parent
+from host_tools import HERE, JPEGINC, JPEGLIB, Tool, build  # noqa: F401
+from wire import MAGIC, pack_blocks, pack_image, parse_image  # noqa: F401
+
 GOLD = HERE / "golden" / "cli"
-JPEGINC = Path("/opt/conda/include")
-JPEGLIB = Path("/opt/conda/lib/libjpeg.so.9")
-MAGIC = 0x51534A43
 KIND_SHAPE = {"islow": (8, 8), "16x16": (16, 16), "16x8": (8, 16), "8x16": (16, 8)}   # (rows, cols) out
 
 
-class LibJpeg9:
-    def __init__(self, workdir: Path):
-        self.dir = Path(workdir)
-        self.exe = self.dir / "libjpeg9_decode"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        r = subprocess.run([cc or "gcc", "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe), str(HERE / "libjpeg9_decode.c"),
-                            str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"the libjpeg 9 oracle (tests/libjpeg9_decode.c) did not build:\n{r.stderr}")
-        self.n = 0
-
-    def _tmp(self, ext):
-        self.n += 1
-        return self.dir / f"t{os.getpid()}_{self.n}{ext}"
-
-    def _run(self, *args):
-        r = subprocess.run([str(self.exe), *map(str, args)], capture_output=True, text=True)
-        if r.returncode:
-            pytest.fail(f"libjpeg9_decode {args[0]} failed: {r.stderr}")
+class LibJpeg9(Tool):
+    def __init__(self, workdir):
+        super().__init__(build("libjpeg9_decode.c", libjpeg=True), workdir)
 
     def read(self, jpeg_path):
         """-> dict(coefs, quants, hsamp, vsamp, colorspace, image_size) of a JPEG file (jpeg_read_coefficients)"""
-        out = self._tmp(".bin")
+        out = self.tmp(".bin")
         self._run("read", jpeg_path, out)
-        b = out.read_bytes()
-        _, n, w, h, cs = struct.unpack_from("<5i", b, 0)
-        off, geo = 20, []
-        for _c in range(n):
-            g = struct.unpack_from("<5i", b, off)
-            q = np.frombuffer(b, np.uint16, 64, off + 20).copy()
-            geo.append((g, q))
-            off += 20 + 128
-        coefs = []
-        for (wb, hb, _hs, _vs, _hq), _q in geo:
-            coefs.append(np.frombuffer(b, np.int16, wb * hb * 64, off).reshape(hb, wb, 64).copy())
-            off += wb * hb * 128
-        return dict(coefs=coefs, quants=[q if g[4] else None for g, q in geo], hsamp=[g[2] for g, _ in geo],
-                    vsamp=[g[3] for g, _ in geo], colorspace=cs, image_size=(w, h))
+        return parse_image(out.read_bytes())
 
     def decode(self, coefs, quants, hsamp, vsamp, colorspace, image_size):
         """libjpeg 9's pixels for these arrays: written with jpeg_write_coefficients, read back with jpeg_read_scanlines
         (JDCT_ISLOW, defaults) -> uint8 (H, W, C)"""
-        n = len(coefs)
-        parts = [struct.pack("<5i", MAGIC, n, image_size[0], image_size[1], colorspace)]
-        for ci in range(n):
-            c = coefs[ci]
-            q = np.ones(64, np.uint16) if quants[ci] is None else np.asarray(quants[ci], np.uint16)
-            parts.append(struct.pack("<5i", c.shape[1], c.shape[0], hsamp[ci], vsamp[ci], 1))
-            parts.append(q.tobytes())
-        for c in coefs:
-            parts.append(np.ascontiguousarray(c, np.int16).tobytes())
-        src, out = self._tmp(".bin"), self._tmp(".raw")
-        src.write_bytes(b"".join(parts))
+        src, out = self.tmp(".bin"), self.tmp(".raw")
+        src.write_bytes(pack_image(dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
+                                        image_size=image_size)))
         self._run("decode", src, out)
         px = np.fromfile(out, np.uint8)
         w, h = image_size
@@ -78,14 +33,12 @@ class LibJpeg9:
 
     def blocks(self, kind, coefs, tables):
         """jpeg_idct_<kind> on each block: coefs (n, 64) int16, tables (n, 64) uint16 -> (n, rows, cols) uint8"""
-        coefs = np.asarray(coefs, np.int16).reshape(-1, 64)
-        tables = np.asarray(tables, np.uint16).reshape(-1, 64)
-        src, out = self._tmp(".bin"), self._tmp(".out")
-        rec = np.concatenate([coefs.view(np.uint16), tables], axis=1)
-        src.write_bytes(struct.pack("<i", len(coefs)) + rec.astype(np.uint16).tobytes())
+        n, data = pack_blocks(coefs, tables)
+        src, out = self.tmp(".bin"), self.tmp(".out")
+        src.write_bytes(data)
         self._run("block", kind, src, out)
         r, c = KIND_SHAPE[kind]
-        return np.fromfile(out, np.uint8).reshape(len(coefs), r, c)
+        return np.fromfile(out, np.uint8).reshape(n, r, c)
 
 
 def blocks_needed(image_size, hsamp, vsamp, ci):

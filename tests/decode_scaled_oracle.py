@@ -2,19 +2,13 @@
 against the libjpeg 9 the rest of the suite links): whole-image decodes with scale_num / scale_denom = 1 / N, and its
 exported reduced IDCTs on single blocks; the host build of the product's arithmetic (tests/decode_scaled_host.cpp); and
 the seeded case builders the CPU and GPU tests share.  If a helper cannot be built, the tests that need it fail."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_cases import DECODE_H, padded, small_image
-from decode_oracle import JPEGINC, JPEGLIB, MAGIC
-
-HERE = Path(__file__).resolve().parent
+from decode_cases import DECODE_H, padded, small_image  # noqa: F401
+from host_tools import Tool, build
+from wire import pack_blocks, pack_image
 KINDS = ("4x4", "2x2", "1x1", "8x4", "4x2", "2x1", "4x8", "2x4", "1x2")        # width x height
 DENOMS = (2, 4, 8)
 TILE_W, TILE_H = 64, 16
@@ -35,64 +29,25 @@ def kind_of(hs, vs, denom):
     return f"{m * min(hs, 2)}x{m * vs}", 2 if hs == 4 else 1
 
 
-def _image_bytes(im):
-    n = len(im["coefs"])
-    w, h = im["image_size"]
-    parts = [struct.pack("<5i", MAGIC, n, w, h, im["colorspace"])]
-    for ci in range(n):
-        c = im["coefs"][ci]
-        q = np.ones(64, np.uint16) if im["quants"][ci] is None else np.asarray(im["quants"][ci], np.uint16)
-        parts.append(struct.pack("<5i", c.shape[1], c.shape[0], im["hsamp"][ci], im["vsamp"][ci], 1))
-        parts.append(q.tobytes())
-    parts += [np.ascontiguousarray(c, np.int16).tobytes() for c in im["coefs"]]
-    return b"".join(parts)
-
-
-def _block_bytes(coefs, tables):
-    coefs = np.asarray(coefs, np.int16).reshape(-1, 64)
-    tables = np.broadcast_to(np.asarray(tables, np.uint16).reshape(-1, 64), coefs.shape)
-    rec = np.concatenate([coefs.view(np.uint16), tables], axis=1)
-    return len(coefs), struct.pack("<i", len(coefs)) + rec.astype(np.uint16).tobytes()
-
-
-class _Helper:
-    """a program built on demand that takes `decode in out DENOM` and `block KIND in out`"""
-    name = src = what = None
-
-    def __init__(self, workdir, cmd):
-        self.dir = Path(workdir)
-        self.exe = self.dir / self.name
-        r = subprocess.run(cmd + ["-o", str(self.exe)], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"{self.what} (tests/{self.src}) did not build:\n{r.stderr}")
-        self.n = 0
-
-    def _tmp(self, ext):
-        self.n += 1
-        return self.dir / f"s{os.getpid()}_{self.n}{ext}"
-
-    def _run(self, *args):
-        r = subprocess.run([str(self.exe), *map(str, args)], capture_output=True, text=True)
-        if r.returncode:
-            pytest.fail(f"{self.name} {' '.join(map(str, args[:2]))} failed ({r.returncode}): {r.stderr[-3000:]}")
-        return r.stdout
+class _Helper(Tool):
+    """a program that takes `decode in out DENOM` and `block KIND in out`"""
 
     def decode(self, im, denom):
         """the image's samples at 1 / denom -> uint8 (H', W', C); the size is asserted to be ceil(W * M / 8) x ceil(H * M / 8)"""
-        src, out = self._tmp(".bin"), self._tmp(".raw")
-        src.write_bytes(_image_bytes(im))
+        src, out = self.tmp(".bin"), self.tmp(".raw")
+        src.write_bytes(pack_image(im))
         self._run("decode", src, out, denom)
         b = out.read_bytes()
         w, h, c = struct.unpack_from("<3i", b, 0)
-        assert (w, h) == scaled_size(im["image_size"], denom), (self.name, (w, h), im["image_size"], denom)
+        assert (w, h) == scaled_size(im["image_size"], denom), (self.exe.name, (w, h), im["image_size"], denom)
         src.unlink()
         out.unlink()
         return np.frombuffer(b, np.uint8, w * h * c, 12).reshape(h, w, c).copy()
 
     def blocks(self, kind, coefs, tables):
         """jpeg_idct_<kind> on each block: coefs (n, 64) int16, tables (n, 64) or (64,) uint16 -> (n, height, width) uint8"""
-        n, data = _block_bytes(coefs, tables)
-        src, out = self._tmp(".bin"), self._tmp(".out")
+        n, data = pack_blocks(coefs, tables)
+        src, out = self.tmp(".bin"), self.tmp(".out")
         src.write_bytes(data)
         self._run("block", kind, src, out)
         w, h = int(kind[0]), int(kind[2])
@@ -100,30 +55,24 @@ class _Helper:
 
 
 class LibJpeg9Scaled(_Helper):
-    name, src, what = "libjpeg9_decode_scaled", "libjpeg9_decode_scaled.c", "the libjpeg 9 oracle of the reduced sizes"
+    """tests/libjpeg9_decode_scaled.c: the libjpeg 9 oracle of the reduced sizes"""
 
     def __init__(self, workdir):
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or "gcc"
-        super().__init__(workdir, [cc, "-O2", "-Wall", f"-I{JPEGINC}", str(HERE / self.src), str(JPEGLIB),
-                                   f"-Wl,-rpath,{JPEGLIB.parent}"])
+        super().__init__(build("libjpeg9_decode_scaled.c", libjpeg=True), workdir)
 
 
 class ScaledHost(_Helper):
-    """csrc/qs_decode.h's reduced sizes compiled for the host; sanitize=True: with -fsanitize=address,undefined (a
-    stand-alone program: nothing is loaded into Python)"""
-    name, src, what = "decode_scaled_host", "decode_scaled_host.cpp", "the host build of csrc/qs_decode.h"
+    """csrc/qs_decode.h's reduced sizes compiled for the host (tests/decode_scaled_host.cpp); sanitize=True: with
+    -fsanitize=address,undefined (a stand-alone program: nothing is loaded into Python)"""
 
     def __init__(self, workdir, sanitize=False):
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or "g++"
         # (C++20 under the sanitizers: the 64-bit pass 1 shared with the full size shifts negative values left, which
         # every compiler of this code defines as two's complement and the language does from C++20 on)
-        flags = ["-std=c++20", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else ["-std=c++17"]
-        if sanitize:
-            self.name = "decode_scaled_host_asan"
-        super().__init__(workdir, [cxx, "-O1", "-Wall", *flags, f"-I{DECODE_H.parent}", str(HERE / self.src)])
+        super().__init__(build("decode_scaled_host.cpp", flags=["-std=c++20"] if sanitize else ["-O1"], sanitize=sanitize),
+                         workdir)
 
     def info(self):
-        return {k: int(v) for k, v in (line.split("=") for line in self._run("info").split())}
+        return {k: int(v) for k, v in (line.split("=") for line in self._run("info").stdout.split())}
 
 
 # ---- blocks -----------------------------------------------------------------------------------------------------------

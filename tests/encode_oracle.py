@@ -1,16 +1,13 @@
 """libjpeg 9 as the oracle of the device entropy coder (tests/libjpeg9_encode.c, compiled on demand like the decode
 oracle's helper), a parser of the files it writes, and a plain Python restatement of the baseline scan coder (test only:
 it pins the scan-order rules of DESIGN.md section 13 against libjpeg before any GPU is involved)."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_oracle import HERE, JPEGINC, JPEGLIB, MAGIC, blocks_needed
+from decode_oracle import blocks_needed
+from host_tools import Tool, build
+from wire import pack_image
 
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
@@ -21,44 +18,33 @@ class LibjpegError(Exception):
     """libjpeg stopped with an error (exit status 3 of the helper)"""
 
 
-class LibJpeg9Enc:
-    def __init__(self, workdir: Path):
-        self.dir = Path(workdir)
-        self.exe = self.dir / "libjpeg9_encode"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        r = subprocess.run([cc or "gcc", "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe), str(HERE / "libjpeg9_encode.c"),
-                            str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"the libjpeg 9 oracle (tests/libjpeg9_encode.c) did not build:\n{r.stderr}")
-        self.n = 0
+class LibJpeg9Enc(Tool):
+    """tests/libjpeg9_encode.c; its subclasses in encode_rst_oracle.py and encode_prog_oracle.py run the same program
+    with restart intervals and with a scan script"""
 
-    def stage(self, im, quants=None) -> Path:
+    def __init__(self, workdir):
+        super().__init__(build("libjpeg9_encode.c", libjpeg=True), workdir)
+
+    def stage(self, im, quants=None):
         """the image dict as the helper's input file"""
-        self.n += 1
-        src = self.dir / f"e{os.getpid()}_{self.n}.bin"
-        quants = im["quants"] if quants is None else quants
-        parts = [struct.pack("<5i", MAGIC, len(im["coefs"]), im["image_size"][0], im["image_size"][1], im["colorspace"])]
-        for ci, c in enumerate(im["coefs"]):
-            q = np.ones(64, np.uint16) if quants[ci] is None else np.asarray(quants[ci], np.uint16)
-            parts.append(struct.pack("<5i", c.shape[1], c.shape[0], im["hsamp"][ci], im["vsamp"][ci], 1))
-            parts.append(q.tobytes())
-        for c in im["coefs"]:
-            parts.append(np.ascontiguousarray(c, np.int16).tobytes())
-        src.write_bytes(b"".join(parts))
+        src = self.tmp(".bin")
+        src.write_bytes(pack_image(im, quants))
         return src
 
-    def run(self, src: Path, optimize=False) -> bytes:
-        """the helper on a staged input: the file jpeg_write_coefficients makes; LibjpegError when libjpeg refuses"""
+    def _write(self, src, *args) -> bytes:
+        """the program on a staged input, which stays: the file it makes, or LibjpegError when libjpeg refuses"""
         out = src.with_suffix(".jpg")
-        r = subprocess.run([str(self.exe), "write", str(src), str(out)] + (["optimize"] if optimize else []),
-                           capture_output=True, text=True)
-        if r.returncode == 3:
-            raise LibjpegError(r.stderr.strip())
-        if r.returncode:
-            pytest.fail(f"libjpeg9_encode failed ({r.returncode}): {r.stderr}")
-        data = out.read_bytes()
-        out.unlink()
-        return data
+        try:
+            r = self._run("write", src, out, *args, ok=(0, 3))
+            if r.returncode == 3:
+                raise LibjpegError(r.stderr.strip())
+            return out.read_bytes()
+        finally:
+            out.unlink(missing_ok=True)
+
+    def run(self, src, optimize=False) -> bytes:
+        """the helper on a staged input: the file jpeg_write_coefficients makes; LibjpegError when libjpeg refuses"""
+        return self._write(src, *(["optimize"] if optimize else []))
 
     def write(self, im, optimize=False, quants=None) -> bytes:
         """the file jpeg_write_coefficients makes of the image dict (coefs, quants, hsamp, vsamp, colorspace,

@@ -1,22 +1,19 @@
 """Progressive files (spectral selection) of the device entropy coder: libjpeg 9 as the oracle
-(tests/libjpeg9_encode_prog.c, compiled on demand), a plain Python restatement of jchuff.c's encode_mcu_DC_first /
+(tests/libjpeg9_encode.c, compiled on demand), a plain Python restatement of jchuff.c's encode_mcu_DC_first /
 encode_mcu_AC_first / emit_eobrun, jcmaster.c's per_scan_setup and jcmarker.c's write_scan_header on top of
 tests/encode_oracle.py and tests/huff_oracle.py (test only: it pins the rules of DESIGN.md section 17 against libjpeg
 before any GPU is involved), the host build of csrc/qs_encode_prog.h (tests/encode_prog_host.cpp), and the builders of the
 cases the test modules share."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_oracle import HERE, JPEGINC, JPEGLIB, blocks_needed
-from encode_oracle import LAYOUTS, ZIGZAG, BadCoef, LibJpeg9Enc, LibjpegError, derive, nbits, synth_scan_image
+from decode_oracle import blocks_needed
+from encode_oracle import LAYOUTS, ZIGZAG, BadCoef, LibJpeg9Enc, derive, nbits, synth_scan_image
 from encode_rst_oracle import RST_LAYOUTS, stuff
-from huff_oracle import CSRC, libjpeg_optimal
+from host_tools import Tool, build
+from huff_oracle import libjpeg_optimal
+from wire import pack_image
 
 PROG_SIZES = [(1, 1), (7, 9), (8, 8), (16, 17), (33, 18), (65, 66), (141, 93)]
 EOB_MAX = 0x7FFF
@@ -28,91 +25,56 @@ def script_text(script) -> str:
 
 
 class LibJpeg9EncProg(LibJpeg9Enc):
-    """tests/libjpeg9_encode_prog.c: jpeg_write_coefficients with cinfo.scan_info set"""
-
-    def __init__(self, workdir: Path):
-        self.dir = Path(workdir) / "prog"
-        self.dir.mkdir(exist_ok=True)
-        self.exe = self.dir / "libjpeg9_encode_prog"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        r = subprocess.run([cc or "gcc", "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe),
-                            str(HERE / "libjpeg9_encode_prog.c"), str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"],
-                           capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"the libjpeg 9 oracle (tests/libjpeg9_encode_prog.c) did not build:\n{r.stderr}")
-        self.n = 0
+    """LibJpeg9Enc with cinfo.scan_info set"""
 
     def write(self, im, script, ri=0, rows=0) -> bytes:
         """the file libjpeg makes of the image dict with the script; LibjpegError when libjpeg refuses"""
         src = self.stage(im)
-        out, txt = src.with_suffix(".jpg"), src.with_suffix(".txt")
+        txt = src.with_suffix(".txt")
         txt.write_text(script_text(script))
         try:
-            r = subprocess.run([str(self.exe), "write", str(src), str(out), str(int(ri)), str(int(rows)), str(txt)],
-                               capture_output=True, text=True)
-            if r.returncode == 3:
-                raise LibjpegError(r.stderr.strip())
-            if r.returncode:
-                pytest.fail(f"libjpeg9_encode_prog failed ({r.returncode}): {r.stderr}")
-            return out.read_bytes()
+            return self._write(src, int(ri), int(rows), txt)
         finally:
-            for p in (src, out, txt):
-                if p.exists():
-                    p.unlink()
+            src.unlink()
+            txt.unlink()
 
 
-class ProgHost:
+class ProgHost(Tool):
     """tests/encode_prog_host.cpp: csrc/qs_encode_prog.h in its host form, as a process"""
+    SOURCE = "encode_prog_host.cpp"
 
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir) / ("prog_host_san" if sanitize else "prog_host")
-        self.dir.mkdir(exist_ok=True)
-        self.exe = self.dir / "encode_prog_host"
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "encode_prog_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/encode_prog_host.cpp did not build:\n{r.stderr}")
-        self.stager = LibJpeg9Enc.__new__(LibJpeg9Enc)
-        self.stager.dir, self.stager.n = self.dir, 0
-
-    def _run(self, *args):
-        return subprocess.run([str(self.exe), *[str(a) for a in args]], capture_output=True, text=True)
+    def __init__(self, workdir, sanitize=False):
+        super().__init__(build(self.SOURCE, flags=["-Wno-unknown-pragmas"], sanitize=sanitize), workdir)
 
     def bounds(self) -> str:
-        r = self._run("bounds")
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r.stdout
+        return self._run("bounds").stdout
 
     def validate(self, script, ncomp):
         """-> (QP_SCRIPT_* code, scan)"""
-        txt = self.dir / f"v{os.getpid()}.txt"
+        txt = self.tmp(".txt")
         txt.write_text(script_text(script))
         r = self._run("validate", ncomp, txt)
         txt.unlink()
-        assert r.returncode == 0, r.stderr
         code, scan = r.stdout.split()[:2]
         return int(code), int(scan)
 
     def write(self, im, script, head: bytes, ri=0, rows=0):
         """-> the file, or the status (1 / 5) the header's coders end with"""
-        src = self.stager.stage(im)
+        src = self.tmp(".bin")
         out, txt, hd = src.with_suffix(".jpg"), src.with_suffix(".txt"), src.with_suffix(".head")
+        src.write_bytes(pack_image(im))
         txt.write_text(script_text(script))
         hd.write_bytes(head)
         try:
-            r = self._run("write", src, txt, hd, out, int(ri), int(rows))
+            r = self._run("write", src, txt, hd, out, int(ri), int(rows), ok=(0, 4, 5))
             if r.returncode == 4:
                 return int(r.stdout.split()[1])
             if r.returncode == 5:
                 return "mcu"
-            assert r.returncode == 0, f"encode_prog_host failed ({r.returncode}): {r.stdout}{r.stderr}"
             return out.read_bytes()
         finally:
             for p in (src, out, txt, hd):
-                if p.exists():
-                    p.unlink()
+                p.unlink(missing_ok=True)
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------

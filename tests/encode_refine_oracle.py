@@ -3,53 +3,28 @@ encode_mcu_DC_refine / encode_mcu_AC_refine / emit_eobrun / emit_buffered_bits i
 of tests/encode_prog_oracle.py (test only: it pins the rules of DESIGN.md section 17.1 against libjpeg's whole files
 before any GPU is involved), the host build of csrc/qs_encode_prog.h for such scripts (tests/encode_refine_host.cpp),
 libjpeg's own jpeg_simple_progression (tests/libjpeg9_simple_prog.c) and the crafted images the test modules share."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_oracle import HERE, JPEGINC, JPEGLIB
-from encode_oracle import ZIGZAG, LibJpeg9Enc, derive
+from encode_oracle import ZIGZAG, derive
 from encode_prog_oracle import (COMPONENT_IDS, EOB_MAX, TABLES, ProgHost, eob_symbol, scan_mcus, scan_order, scan_symbols_prog,
                                 sub_image)
 from encode_rst_oracle import gray_image, stuff
-from huff_oracle import CSRC, libjpeg_optimal
+from host_tools import build, run
+from huff_oracle import libjpeg_optimal
 
 CORR_MAX = 937                                                          # MAX_CORR_BITS - DCTSIZE2 + 1
 
 
 class RefineHost(ProgHost):
     """tests/encode_refine_host.cpp: csrc/qs_encode_prog.h in its host form for scripts with refinement scans"""
-
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir) / ("refine_host_san" if sanitize else "refine_host")
-        self.dir.mkdir(exist_ok=True)
-        self.exe = self.dir / "encode_refine_host"
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "encode_refine_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/encode_refine_host.cpp did not build:\n{r.stderr}")
-        self.stager = LibJpeg9Enc.__new__(LibJpeg9Enc)
-        self.stager.dir, self.stager.n = self.dir, 0
+    SOURCE = "encode_refine_host.cpp"
 
 
-def libjpeg_simple_progression(workdir: Path, ncomp: int, colorspace: int):
+def libjpeg_simple_progression(workdir, ncomp: int, colorspace: int):
     """tests/libjpeg9_simple_prog.c: cinfo.scan_info after jpeg_simple_progression -> the script"""
-    exe = Path(workdir) / "libjpeg9_simple_prog"
-    if not exe.exists():
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        r = subprocess.run([cc or "gcc", "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(exe), str(HERE / "libjpeg9_simple_prog.c"),
-                            str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"], capture_output=True, text=True)
-        if r.returncode or not exe.exists():
-            pytest.fail(f"tests/libjpeg9_simple_prog.c did not build:\n{r.stderr}")
-    r = subprocess.run([str(exe), str(ncomp), str(colorspace)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = run(build("libjpeg9_simple_prog.c", libjpeg=True), ncomp, colorspace)
     out = []
     for line in r.stdout.splitlines():
         v = [int(x) for x in line.split()]

@@ -1,54 +1,23 @@
-"""Restart intervals of the device entropy coder: libjpeg 9 as the oracle (tests/libjpeg9_encode_rst.c, compiled on
+"""Restart intervals of the device entropy coder: libjpeg 9 as the oracle (tests/libjpeg9_encode.c, compiled on
 demand), a plain Python restatement of the restart rules of jchuff.c / jcmaster.c / jcmarker.c on top of
 tests/encode_oracle.py (test only: it pins the rules of DESIGN.md section 13 against libjpeg before any GPU is involved),
 and the builders of the cases both test modules share."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from decode_oracle import HERE, JPEGINC, JPEGLIB
-from encode_oracle import (LAYOUTS, SIZES, LibJpeg9Enc, LibjpegError, block_symbols, derive, scan_blocks,
-                           synth_scan_image)
+from encode_oracle import LAYOUTS, SIZES, LibJpeg9Enc, block_symbols, derive, scan_blocks, synth_scan_image
+from host_tools import HERE  # noqa: F401
 
 SCHUNK = 4096                      # bytes of the unstuffed stream the stuffing stage takes per step (QS_ENC_SCHUNK)
 
 
 class LibJpeg9EncRst(LibJpeg9Enc):
-    """tests/libjpeg9_encode_rst.c: LibJpeg9Enc with cinfo.restart_interval / cinfo.restart_in_rows"""
+    """LibJpeg9Enc with cinfo.restart_interval / cinfo.restart_in_rows"""
 
-    def __init__(self, workdir: Path):
-        # a directory of its own: LibJpeg9Enc names its staged files by process and count, so two helpers in one
-        # directory would write, and remove, each other's inputs
-        self.dir = Path(workdir) / "rst"
-        self.dir.mkdir(exist_ok=True)
-        self.exe = self.dir / "libjpeg9_encode_rst"
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        r = subprocess.run([cc or "gcc", "-O2", "-Wall", f"-I{JPEGINC}", "-o", str(self.exe),
-                            str(HERE / "libjpeg9_encode_rst.c"), str(JPEGLIB), f"-Wl,-rpath,{JPEGLIB.parent}"],
-                           capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"the libjpeg 9 oracle (tests/libjpeg9_encode_rst.c) did not build:\n{r.stderr}")
-        self.n = 0
-
-    def run(self, src: Path, ri=0, rows=0, optimize=False) -> bytes:
+    def run(self, src, ri=0, rows=0, optimize=False) -> bytes:
         """the helper on a staged input (stage()), which stays; LibjpegError when libjpeg refuses"""
-        out = src.with_suffix(".jpg")
-        try:
-            r = subprocess.run([str(self.exe), "write", str(src), str(out), str(int(ri)), str(int(rows))]
-                               + (["optimize"] if optimize else []), capture_output=True, text=True)
-            if r.returncode == 3:
-                raise LibjpegError(r.stderr.strip())
-            if r.returncode:
-                pytest.fail(f"libjpeg9_encode_rst failed ({r.returncode}): {r.stderr}")
-            return out.read_bytes()
-        finally:
-            if out.exists():
-                out.unlink()
+        return self._write(src, int(ri), int(rows), *(["optimize"] if optimize else []))
 
     def write(self, im, ri=0, rows=0, optimize=False, quants=None) -> bytes:
         """the file jpeg_write_coefficients makes of the image dict with restart_interval = ri and restart_in_rows =

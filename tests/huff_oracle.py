@@ -1,17 +1,12 @@
 """What the tests of the optimal-table procedure (csrc/qs_huff.h) share: a restatement of libjpeg's
 jpeg_gen_optimal_table that walks the others[] chains as jchuff.c does, the histograms both the CPU and the GPU tests
 run, and the host build of the header (tests/huff_host.cpp)."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-HERE = Path(__file__).resolve().parent
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
+from host_tools import Tool, build
+
 MAX_CLEN = 32
 _BIG = np.int64(1) << 62
 
@@ -135,28 +130,19 @@ def seeded_histograms(n, seed):
     return out
 
 
-class HuffHost:
+class HuffHost(Tool):
     """tests/huff_host.cpp: the table procedure of csrc/qs_huff.h in its host form, as a process"""
+    SILENT = True
 
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir)
-        self.exe = self.dir / ("huff_host_san" if sanitize else "huff_host")
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "huff_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/huff_host.cpp did not build:\n{r.stderr}")
-        self.n = 0
+    def __init__(self, workdir, sanitize=False):
+        super().__init__(build("huff_host.cpp", sanitize=sanitize), workdir)
 
     def run(self, hists):
         """[counts[256]] -> [(status, bits[17], huffval: the first sum(bits) symbols, rest: the bytes behind them)];
         fails on a non-zero exit or anything on stderr (a sanitizer report)"""
-        self.n += 1
-        src, dst = self.dir / f"h{os.getpid()}_{self.n}.bin", self.dir / f"h{os.getpid()}_{self.n}.out"
+        src, dst = self.tmp(".bin"), self.tmp(".out")
         src.write_bytes(struct.pack("<i", len(hists)) + b"".join(np.asarray(h, np.uint32)[:256].tobytes() for h in hists))
-        r = subprocess.run([str(self.exe), "run", str(src), str(dst)], capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, f"huff_host exit {r.returncode}:\n{r.stderr[-4000:]}"
+        self._run("run", src, dst)
         b = dst.read_bytes()
         src.unlink()
         dst.unlink()

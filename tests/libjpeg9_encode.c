@@ -1,13 +1,17 @@
 /*
- * libjpeg9_encode.c -- TEST ORACLE for the device entropy coder (tests/test_encode_host.py, tests/test_gpu_encode.py):
- * libjpeg 9 itself, with no code of this project or of the reference in the loop.
+ * libjpeg9_encode.c -- TEST ORACLE for the device entropy coder, its restart intervals and its progressive files
+ * (tests/test_encode_host.py, tests/test_encode_rst_host.py, tests/test_encode_prog_host.py and their GPU twins): libjpeg 9
+ * itself, with no code of this project or of the reference in the loop.
  *
  *   libjpeg9_encode write in.bin out.jpg [optimize]
+ *   libjpeg9_encode write in.bin out.jpg restart_interval restart_in_rows [optimize | script.txt]
  *
  * writes the coefficient arrays of in.bin (the format of tests/libjpeg9_decode.c) with jpeg_write_coefficients on a
  * fresh compress object: jpeg_set_defaults + jpeg_set_colorspace, the sampling factors and one quant table per
- * component from the file, the standard Huffman tables or, with `optimize`, optimize_coding.
- * Exit status: 0 written; 3 libjpeg stopped with an error (its message on stderr); 1 anything else.
+ * component from the file, the standard Huffman tables or, with `optimize`, optimize_coding; cinfo.restart_interval
+ * and cinfo.restart_in_rows are the arguments (what jpegtran -restart sets; 0 where there are none), and with a script
+ * cinfo.scan_info / num_scans are its lines (one scan each: "ncomp c0 c1 c2 c3 Ss Se Ah Al", what jpegtran -scans sets).
+ * Exit status: 0 written; 3 libjpeg stopped with an error (its message on stderr); 2 bad arguments; 1 anything else.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,7 +35,10 @@ static void *xread(FILE *f, size_t n) {
 	return p;
 }
 
-static int do_write(const char *src, const char *dst, int optimize) {
+static jpeg_scan_info script[1024];
+static int nscans, have_script;
+
+static int do_write(const char *src, const char *dst, long ri, long rows, int optimize) {
 	struct jpeg_compress_struct co;
 	struct jpeg_error_mgr err;
 	jvirt_barray_ptr arrays[4];
@@ -67,11 +74,11 @@ static int do_write(const char *src, const char *dst, int optimize) {
 	co.in_color_space = (J_COLOR_SPACE)hdr[4];
 	jpeg_set_defaults(&co);
 	jpeg_set_colorspace(&co, (J_COLOR_SPACE)hdr[4]);
+	co.optimize_coding = optimize ? TRUE : FALSE;
 	/* what jpeg_copy_critical_parameters sets for a transcode */
 	co.min_DCT_h_scaled_size = co.min_DCT_v_scaled_size = DCTSIZE;
 	co.jpeg_width = co.image_width;
 	co.jpeg_height = co.image_height;
-	co.optimize_coding = optimize ? TRUE : FALSE;
 	for (c = 0; c < n; c++) {
 		JQUANT_TBL *t;
 		co.comp_info[c].h_samp_factor = g[c][2];
@@ -106,6 +113,12 @@ static int do_write(const char *src, const char *dst, int optimize) {
 			if (y < hb) memcpy(r[0], blk[c] + (size_t)y * g[c][0] * 64, (size_t)wb * sizeof(JBLOCK));
 		}
 	}
+	co.restart_interval = (unsigned int)ri;
+	co.restart_in_rows = (int)rows;
+	if (have_script) {
+		co.scan_info = script;
+		co.num_scans = nscans;
+	}
 	jpeg_write_coefficients(&co, arrays);
 	jpeg_finish_compress(&co);
 	jpeg_destroy_compress(&co);
@@ -114,8 +127,28 @@ static int do_write(const char *src, const char *dst, int optimize) {
 }
 
 int main(int argc, char **argv) {
-	if ((argc == 4 || (argc == 5 && !strcmp(argv[4], "optimize"))) && !strcmp(argv[1], "write"))
-		return do_write(argv[2], argv[3], argc == 5);
-	fprintf(stderr, "usage: libjpeg9_encode write in.bin out.jpg [optimize]\n");
+	const char *last = argc == 5 || argc == 7 ? argv[argc - 1] : NULL;     /* `optimize` or the script */
+	int optimize = last && !strcmp(last, "optimize");
+	if (argc >= 4 && argc <= 7 && !strcmp(argv[1], "write") && (argc != 5 || optimize)) {
+		long ri = argc >= 6 ? strtol(argv[4], NULL, 10) : 0, rows = argc >= 6 ? strtol(argv[5], NULL, 10) : 0;
+		FILE *f = last && !optimize ? fopen(last, "r") : NULL;
+		jpeg_scan_info *s = script;
+		if (ri < 0 || ri > 65535 || rows < 0 || rows > 65535 || (last && !optimize && !f)) {
+			fprintf(stderr, "libjpeg9_encode: bad argument\n");
+			return 2;
+		}
+		while (f && nscans < 1024 && fscanf(f, "%d %d %d %d %d %d %d %d %d", &s->comps_in_scan, &s->component_index[0],
+				&s->component_index[1], &s->component_index[2], &s->component_index[3], &s->Ss, &s->Se, &s->Ah, &s->Al) == 9) {
+			nscans++;
+			s++;
+		}
+		if (f) {
+			have_script = 1;
+			fclose(f);
+		}
+		return do_write(argv[2], argv[3], ri, rows, optimize);
+	}
+	fprintf(stderr, "usage: libjpeg9_encode write in.bin out.jpg [optimize]\n"
+			"       libjpeg9_encode write in.bin out.jpg restart_interval restart_in_rows [optimize | script.txt]\n");
 	return 2;
 }

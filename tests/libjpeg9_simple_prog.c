@@ -6,7 +6,7 @@
  *
  * sets up a compress object of ncomp components in the J_COLOR_SPACE `colorspace` (jpeg_set_defaults +
  * jpeg_set_colorspace), calls jpeg_simple_progression and prints cinfo.scan_info, one scan per line:
- * "ncomp c0 c1 c2 c3 Ss Se Ah Al" (the format of tests/libjpeg9_encode_prog.c's scripts).
+ * "ncomp c0 c1 c2 c3 Ss Se Ah Al" (the format of tests/libjpeg9_encode.c's scripts).
  * Exit status: 0 printed; 3 libjpeg stopped with an error; 1 anything else.
  */
 #include <stdio.h>

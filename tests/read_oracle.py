@@ -1,88 +1,57 @@
 """What the tests of the device scan reader share (tests/test_read_host.py, tests/test_gpu_read.py): the host build of
 csrc/qs_read.h (tests/read_host.cpp, compiled on demand, optionally with -fsanitize=address,undefined), libjpeg 9 at
-both ends of the oracle -- files written by tests/libjpeg9_encode_rst.c, expected arrays read by tests/libjpeg9_decode.c
+both ends of the oracle -- files written by tests/libjpeg9_encode.c, expected arrays read by tests/libjpeg9_decode.c
 -- the grid of valid cases and the seeded corrupt corpus."""
-import os
-import shutil
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
-import pytest
 
 import jpegqs_pkg
-from decode_oracle import HERE, LibJpeg9, blocks_needed
+from decode_oracle import LibJpeg9, blocks_needed
 from encode_oracle import LAYOUTS, SIZES, synth_scan_image
-from encode_rst_oracle import RST_LAYOUTS, LibJpeg9EncRst, dc_range_images, mcu_geometry, optimize_cases, padding_case
+from encode_rst_oracle import RST_LAYOUTS, dc_range_images, mcu_geometry, optimize_cases, padding_case
+from host_tools import CSRC, HERE, Tool, build  # noqa: F401
+from wire import frame_words, pack_tables, pad4, parse_image, parse_results
 
 pkg = jpegqs_pkg.load()
 from jpeg_quantsmooth_amd import jpeg_file  # noqa: E402
 
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
 CORPUS_SEED = 1           # the three valid files of the corrupt corpus (corpus_sources); 3.2 % of it decodes clean
 
 
-class ReadHost:
-    """tests/read_host.cpp: qs_read.h on the host"""
+class CaseHost(Tool):
+    """a host build of a scan reader that takes `run in.bin out.bin`: int32 ncases and the cases of PACK in, per case
+    WORDS int32 (the status first) and the arrays out.  A run fails on a non-zero exit or anything on stderr (a sanitizer
+    report)."""
+    SILENT = True
+    WORDS = 1
 
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir)
-        self.exe = self.dir / ("read_host_san" if sanitize else "read_host")
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "read_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/read_host.cpp did not build:\n{r.stderr}")
-        self.n = 0
-
-    def run(self, cases):
-        """cases: [dict(header: jpeg_file.parse's dict, scan: bytes, shapes: [(rows, stride)] per component)] ->
-        [(status, [int16 arrays (rows, stride, 64)] or None)]; fails on a non-zero exit or anything on stderr (a
-        sanitizer report)"""
-        self.n += 1
-        src, dst = self.dir / f"c{os.getpid()}_{self.n}.bin", self.dir / f"c{os.getpid()}_{self.n}.out"
-        src.write_bytes(struct.pack("<i", len(cases)) + b"".join(pack_case(c) for c in cases))
-        r = subprocess.run([str(self.exe), "run", str(src), str(dst)], capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, f"read_host exit {r.returncode}:\n{r.stderr[-4000:]}"
+    def run(self, cases, *args):
+        src, dst = self.tmp(".bin"), self.tmp(".out")
+        with open(src, "wb") as f:
+            f.write(struct.pack("<i", len(cases)))
+            for c in cases:
+                f.write(self.PACK(c))
+        self._run("run", src, dst, *args)
         b = dst.read_bytes()
         src.unlink()
         dst.unlink()
-        out, off = [], 0
-        for c in cases:
-            status = struct.unpack_from("<i", b, off)[0]
-            off += 4
-            arrs = None
-            if status >= 0:
-                arrs = []
-                for rows, stride in c["shapes"]:
-                    arrs.append(np.frombuffer(b, np.int16, rows * stride * 64, off).reshape(rows, stride, 64).copy())
-                    off += rows * stride * 128
-            out.append((status, arrs))
-        assert off == len(b)
-        return out
-
-
-def pad4(v):
-    return list(v) + [0] * (4 - len(v))
+        return parse_results(b, cases, self.WORDS)
 
 
 def pack_case(c) -> bytes:
-    p, shapes = c["header"], c["shapes"]
-    n = len(p["hsamp"])
-    head = struct.pack("<28i", n, p["image_size"][0], p["image_size"][1], *pad4(p["hsamp"]), *pad4(p["vsamp"]),
-                       *pad4([s[1] for s in shapes]), *pad4([s[0] for s in shapes]), *pad4(p["dc_tbl"]), *pad4(p["ac_tbl"]),
-                       p["restart_interval"])
-    tabs = []
-    for kind in ("dc", "ac"):
-        for t in range(4):
-            if t in p[kind]:
-                bits, vals = p[kind][t]
-                tabs.append(bytes([1]) + bytes(bits) + bytes(vals) + bytes(256 - len(vals)))
-            else:
-                tabs.append(bytes(1 + 17 + 256))
-    return head + b"".join(tabs) + struct.pack("<Q", len(c["scan"])) + bytes(c["scan"])
+    p = c["header"]
+    return struct.pack("<28i", *frame_words(p, c["shapes"]), *pad4(p["dc_tbl"]), *pad4(p["ac_tbl"]), p["restart_interval"]) \
+        + pack_tables(p) + struct.pack("<Q", len(c["scan"])) + bytes(c["scan"])
+
+
+class ReadHost(CaseHost):
+    """tests/read_host.cpp: qs_read.h on the host.  run(cases): [dict(header: jpeg_file.parse's dict, scan: bytes,
+    shapes: [(rows, stride)] per component)] -> [(status, [int16 arrays (rows, stride, 64)] or None)]"""
+    PACK = staticmethod(pack_case)
+
+    def __init__(self, workdir, sanitize=False):
+        super().__init__(build("read_host.cpp", sanitize=sanitize), workdir)
 
 
 def true_shapes(p):
@@ -96,20 +65,14 @@ class LibjpegReader(LibJpeg9):
     def read_bytes(self, data):
         """-> (image dict or None when libjpeg stopped with an error, clean: no warning and no error).  libjpeg's
         default error manager prints the first warning of a file to stderr and counts the rest in num_warnings."""
-        src, out = self._tmp(".jpg"), self._tmp(".bin")
-        src.write_bytes(data)
-        r = subprocess.run([str(self.exe), "read", str(src), str(out)], capture_output=True, text=True)
-        src.unlink()
-        if r.returncode:
-            if out.exists():
-                out.unlink()
-            return None, False
-        out.unlink()
+        src, out = self.tmp(".jpg"), self.tmp(".bin")
         src.write_bytes(data)
         try:
-            return self.read(src), not r.stderr.strip()
+            r = self._run("read", src, out, ok=None)
+            return (parse_image(out.read_bytes()), not r.stderr.strip()) if r.returncode == 0 else (None, False)
         finally:
             src.unlink()
+            out.unlink(missing_ok=True)
 
 
 def expected_arrays(ref, shapes):

@@ -21,16 +21,8 @@
  *          over the interval cap, -4 more than 10 blocks in an MCU, -5 the script is refused, -6 a store outside an
  *          array -- int32 levels and, for status >= 0, the arrays (stride x rows x 64 int16 per component)
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "qs_read_prog.h"
-
-static bool get(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
+#include "read_case.h"                    // get, rc_table
 
 static const int GUARD = 256;      // int16 on either side of every array
 
@@ -62,7 +54,7 @@ static int run(const char* src, const char* dst) {
       memset(&J[(size_t)s], 0, sizeof(QrJob));
       memset(&X[(size_t)s], 0, sizeof(QrpScan));
       memcpy(&recs[(size_t)s], r, sizeof(QpScanRec));
-      uint8_t tabs[8][1 + 17 + 256];
+      uint8_t tabs[8][RC_TABLE_REC];
       if (!get(in, tabs, sizeof tabs)) return 1;
       if (status) continue;
       const QpScanRec& rec = recs[(size_t)s];
@@ -85,7 +77,7 @@ static int run(const char* src, const char* dst) {
       for (int c = 0; c < rec.ncomp; ++c) {
         const int t = rec.Ss == 0 ? J[(size_t)s].dc_tbl[c] : 4 + J[(size_t)s].ac_tbl[c];
         if (rec.Ss == 0 && rec.Ah) continue;                           // a DC refinement has no symbols
-        if (!tabs[t][0] || qr_build_table(tabs[t] + 1, tabs[t] + 18, t < 4, &J[(size_t)s].tab[t])) status = -1;
+        if (!tabs[t][0] || rc_table(tabs[t], t, &J[(size_t)s].tab[t])) status = -1;
       }
     }
     uint64_t n = 0;

@@ -1,99 +1,47 @@
 """What the tests of the scan reader's progressive route share (tests/test_read_prog_host.py, tests/test_gpu_read_prog.py):
 the host build of csrc/qs_read_prog.h (tests/read_prog_host.cpp, compiled on demand, optionally with
--fsanitize=address,undefined), libjpeg 9 at both ends of the oracle -- files written by tests/libjpeg9_encode_prog.c,
+-fsanitize=address,undefined), libjpeg 9 at both ends of the oracle -- files written by tests/libjpeg9_encode.c,
 expected arrays read by tests/libjpeg9_decode.c -- the grid of valid cases and the seeded corrupt corpus."""
 import os
-import shutil
 import struct
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
-import pytest
 
 import jpegqs_pkg
-from decode_oracle import HERE
 from encode_oracle import LAYOUTS, synth_scan_image
 from encode_prog_oracle import PROG_SIZES
 from encode_refine_oracle import GRAY_REFINE, big_crafted_images, crafted_images, refine_scripts
 from encode_rst_oracle import RST_LAYOUTS, dc_range_images, mcu_geometry
-from read_oracle import CORPUS_SEED, LibjpegReader, pad4, padded_shapes
+from host_tools import HERE, build, run
+from read_oracle import CORPUS_SEED, CaseHost, LibjpegReader, padded_shapes
+from wire import frame_words, pack_tables, pad4
 
 pkg = jpegqs_pkg.load()
 from jpeg_quantsmooth_amd import jpeg_file  # noqa: E402
 
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
 GOLDEN_PROG = HERE / "golden" / "cli" / "rgb120x88_prog.jpg"
 
 
-class ReadProgHost:
-    """tests/read_prog_host.cpp: qs_read_prog.h on the host"""
-
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir)
-        self.exe = self.dir / ("read_prog_host_san" if sanitize else "read_prog_host")
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", *flags, f"-I{CSRC}", "-o",
-                            str(self.exe), str(HERE / "read_prog_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/read_prog_host.cpp did not build:\n{r.stderr}")
-        self.n = 0
-
-    def run(self, cases):
-        """cases: [dict(header: jpeg_file.parse_progressive's dict, data: the file, shapes: [(rows, stride)] per
-        component)] -> [(status, levels, [int16 arrays (rows, stride, 64)] or None)]; fails on a non-zero exit or anything
-        on stderr (a sanitizer report)"""
-        self.n += 1
-        src, dst = self.dir / f"p{os.getpid()}_{self.n}.bin", self.dir / f"p{os.getpid()}_{self.n}.out"
-        with open(src, "wb") as f:
-            f.write(struct.pack("<i", len(cases)))
-            for c in cases:
-                f.write(pack_case(c))
-        r = subprocess.run([str(self.exe), "run", str(src), str(dst)], capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, f"read_prog_host exit {r.returncode}:\n{r.stderr[-4000:]}"
-        b = dst.read_bytes()
-        src.unlink()
-        dst.unlink()
-        out, off = [], 0
-        for c in cases:
-            status, levels = struct.unpack_from("<2i", b, off)
-            off += 8
-            arrs = None
-            if status >= 0:
-                arrs = []
-                for rows, stride in c["shapes"]:
-                    arrs.append(np.frombuffer(b, np.int16, rows * stride * 64, off).reshape(rows, stride, 64).copy())
-                    off += rows * stride * 128
-            out.append((status, levels, arrs))
-        assert off == len(b)
-        return out
-
-
-def pack_tables(s) -> bytes:
-    tabs = []
-    for kind in ("dc", "ac"):
-        for t in range(4):
-            if t in s[kind]:
-                bits, vals = s[kind][t]
-                tabs.append(bytes([1]) + bytes(bits) + bytes(vals) + bytes(256 - len(vals)))
-            else:
-                tabs.append(bytes(1 + 17 + 256))
-    return b"".join(tabs)
-
-
 def pack_case(c) -> bytes:
-    p, shapes = c["header"], c["shapes"]
-    n = len(p["hsamp"])
-    out = [struct.pack("<20i", n, p["image_size"][0], p["image_size"][1], *pad4(p["hsamp"]), *pad4(p["vsamp"]),
-                       *pad4([s[1] for s in shapes]), *pad4([s[0] for s in shapes]), len(p["scans"]))]
+    p = c["header"]
+    out = [struct.pack("<20i", *frame_words(p, c["shapes"]), len(p["scans"]))]
     for s in p["scans"]:
         out.append(struct.pack("<18iQ", len(s["comps"]), *pad4(s["comps"]), s["ss"], s["se"], s["ah"], s["al"],
                                *pad4(s["dc_tbl"]), *pad4(s["ac_tbl"]), s["restart_interval"], s["offset"]))
         out.append(pack_tables(s))
     out.append(struct.pack("<Q", len(c["data"])) + bytes(c["data"]))
     return b"".join(out)
+
+
+class ReadProgHost(CaseHost):
+    """tests/read_prog_host.cpp: qs_read_prog.h on the host.  run(cases): [dict(header: jpeg_file.parse_progressive's
+    dict, data: the file, shapes: [(rows, stride)] per component)] -> [(status, levels, [int16 arrays (rows, stride, 64)]
+    or None)]"""
+    PACK, WORDS = staticmethod(pack_case), 2
+
+    def __init__(self, workdir, sanitize=False):
+        super().__init__(build("read_prog_host.cpp", flags=["-Wno-unknown-pragmas"], sanitize=sanitize), workdir)
 
 
 def expected_arrays(ref, shapes, script):
@@ -250,7 +198,7 @@ def libjpeg_reads(lj: LibjpegReader, corpus, threads=8):
         src, out = lj.dir / f"lr{os.getpid()}_{i}.jpg", lj.dir / f"lr{os.getpid()}_{i}.bin"
         src.write_bytes(data)
         try:
-            r = subprocess.run([str(lj.exe), "read", str(src), str(out)], capture_output=True, text=True)
+            r = run(lj.exe, "read", src, out, ok=None)
             if r.returncode or r.stderr.strip():
                 return None, False
             return src, True

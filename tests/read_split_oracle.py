@@ -3,70 +3,29 @@ tests/test_gpu_read_split.py): the host build of csrc/qs_read_split.h (tests/rea
 its variants) and the corpus of valid files the number of synchronisation rounds was measured on (DESIGN.md section
 14): the grid of tests/read_oracle.py, natural-statistics images at three qualities, RGB, CMYK and YCCK files, standard
 and optimized tables."""
-import os
-import shutil
-import struct
-import subprocess
-from pathlib import Path
-
 import numpy as np
-import pytest
 
 from crafted_scans import ZIGZAG
-from decode_oracle import HERE
-from read_oracle import CSRC, build_grid, make_case, pack_case, pkg
+from host_tools import build
+from read_oracle import CaseHost, build_grid, make_case, pack_case, pkg
 
 SPLIT_BYTES = 256                  # QS_RD_SPLIT_BYTES / QS_HIP_READ_SPLIT_BYTES
 SPLIT_ROUNDS = 17                  # QS_RD_SPLIT_ROUNDS / QS_HIP_READ_SPLIT_ROUNDS
 
 
-class SplitHost:
+class SplitHost(CaseHost):
     """tests/read_split_host.cpp: qr_split_serial on the host.  rounds / nbytes: built with -DQS_RD_SPLIT_ROUNDS /
     -DQS_RD_SPLIT_BYTES"""
+    PACK, WORDS = staticmethod(pack_case), 3
 
-    def __init__(self, workdir: Path, sanitize=False, rounds=None, nbytes=None):
-        self.dir = Path(workdir)
-        name = "read_split_host" + ("_san" if sanitize else "") + (f"_r{rounds}" if rounds is not None else "") \
-            + (f"_b{nbytes}" if nbytes is not None else "")
-        self.exe = self.dir / name
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        if rounds is not None:
-            flags.append(f"-DQS_RD_SPLIT_ROUNDS={rounds}")
-        if nbytes is not None:
-            flags.append(f"-DQS_RD_SPLIT_BYTES={nbytes}")
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "read_split_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            pytest.fail(f"tests/read_split_host.cpp did not build:\n{r.stderr}")
-        self.n = 0
+    def __init__(self, workdir, sanitize=False, rounds=None, nbytes=None):
+        defines = [f"{k}={v}" for k, v in (("QS_RD_SPLIT_ROUNDS", rounds), ("QS_RD_SPLIT_BYTES", nbytes)) if v is not None]
+        super().__init__(build("read_split_host.cpp", defines=defines, sanitize=sanitize), workdir)
 
     def run(self, cases, rounds=None):
         """cases as ReadHost.run takes them -> [(status, rounds needed or -1, segments, arrays or None)]; rounds: run
-        that many synchronisation rounds instead of the build's constant; fails on a non-zero exit or anything on
-        stderr (a sanitizer report)"""
-        self.n += 1
-        src, dst = self.dir / f"s{os.getpid()}_{self.exe.name}_{self.n}.bin", self.dir / f"s{os.getpid()}_{self.exe.name}_{self.n}.out"
-        src.write_bytes(struct.pack("<i", len(cases)) + b"".join(pack_case(c) for c in cases))
-        r = subprocess.run([str(self.exe), "run", str(src), str(dst)] + ([str(rounds)] if rounds is not None else []),
-                           capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, f"read_split_host exit {r.returncode}:\n{r.stderr[-4000:]}"
-        b = dst.read_bytes()
-        src.unlink()
-        dst.unlink()
-        out, off = [], 0
-        for c in cases:
-            status, needed, nseg = struct.unpack_from("<3i", b, off)
-            off += 12
-            arrs = None
-            if status >= 0:
-                arrs = []
-                for rows, stride in c["shapes"]:
-                    arrs.append(np.frombuffer(b, np.int16, rows * stride * 64, off).reshape(rows, stride, 64).copy())
-                    off += rows * stride * 128
-            out.append((status, needed, nseg, arrs))
-        assert off == len(b)
-        return out
+        that many synchronisation rounds instead of the build's constant"""
+        return super().run(cases, *([rounds] if rounds is not None else []))
 
 
 def table_period(header):

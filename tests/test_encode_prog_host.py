@@ -1,5 +1,5 @@
 """Progressive files (spectral selection) before any GPU is involved: libjpeg 9 itself writes the files
-(tests/libjpeg9_encode_prog.c); the plain Python restatement of tests/encode_prog_oracle.py and the host build of
+(tests/libjpeg9_encode.c); the plain Python restatement of tests/encode_prog_oracle.py and the host build of
 csrc/qs_encode_prog.h (tests/encode_prog_host.cpp, plain and under ASan + UBSan as a program of its own) are pinned to
 them, whole file; the script validation of the library, of jpeg_file and of libjpeg agree; libjpeg and Pillow read the
 files back.  DESIGN.md section 17."""

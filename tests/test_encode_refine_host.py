@@ -1,5 +1,5 @@
 """Progressive files with refinement scans (Ah > 0) before any GPU is involved: libjpeg 9 itself writes the files
-(tests/libjpeg9_encode_prog.c); the plain Python restatement of tests/encode_refine_oracle.py and the host build of
+(tests/libjpeg9_encode.c); the plain Python restatement of tests/encode_refine_oracle.py and the host build of
 csrc/qs_encode_prog.h (tests/encode_refine_host.cpp, plain and under ASan + UBSan as a program of its own) are pinned to
 them, whole file; crafted images put every rule of the AC refinement's EOB runs to work; libjpeg and Pillow read the files
 back; jpeg_file.simple_progression is libjpeg's jpeg_simple_progression.  DESIGN.md section 17.1."""

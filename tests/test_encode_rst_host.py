@@ -1,5 +1,5 @@
 """Restart intervals of the device entropy coder, without a GPU: the plain restatement of libjpeg 9's restart rules
-(tests/encode_rst_oracle.py) against libjpeg 9 itself (tests/libjpeg9_encode_rst.c) on every case the GPU module runs,
+(tests/encode_rst_oracle.py) against libjpeg 9 itself (tests/libjpeg9_encode.c) on every case the GPU module runs,
 the DRI marker of jpeg_file.compose, the optimal tables of a restart scan, what the cases are there for, and the
 qs_hip_encode_device_batch_info_opts bounds and argument checks."""
 import numpy as np

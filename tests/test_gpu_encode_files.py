@@ -1,6 +1,6 @@
 """Whole JPEG files built on the device (torch_qs.encode_file_batch / encode_file, qs_hip_encode_device_batch_files):
 histogram, optimal tables, DHT markers, framing and the segment in one run, against libjpeg 9 itself writing the same
-arrays with optimize_coding (tests/libjpeg9_encode.c, tests/libjpeg9_encode_rst.c)."""
+arrays with optimize_coding (tests/libjpeg9_encode.c)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """Progressive files (spectral selection) built on the device (torch_qs.encode_file_batch(scans=...),
 qs_hip_encode_progressive_device_batch_files) against libjpeg 9 itself writing the same arrays with the same scan script
-(tests/libjpeg9_encode_prog.c): whole files, byte for byte.  DESIGN.md section 17."""
+(tests/libjpeg9_encode.c): whole files, byte for byte.  DESIGN.md section 17."""
 import hashlib
 import warnings
 

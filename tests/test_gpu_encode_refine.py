@@ -1,6 +1,6 @@
 """Progressive files with refinement scans (Ah > 0) built on the device (torch_qs.encode_file_batch(scans=...,
 refinement=True), qs_hip_encode_progressive_device_batch_files with QS_HIP_PROG_REFINE) against libjpeg 9 itself writing
-the same arrays with the same scan script (tests/libjpeg9_encode_prog.c): whole files, byte for byte.  DESIGN.md section
+the same arrays with the same scan script (tests/libjpeg9_encode.c): whole files, byte for byte.  DESIGN.md section
 17.1."""
 import warnings
 

@@ -1,6 +1,6 @@
 """Restart intervals of the device entropy coder on the GPU (torch_qs.encode / encode_scan / encode_histogram_batch with
 restart_interval / restart_in_rows, qs_hip_encode_device_batch_prepare_opts): against libjpeg 9 itself writing the same
-arrays with cinfo.restart_interval / cinfo.restart_in_rows (tests/libjpeg9_encode_rst.c) and against the plain Python
+arrays with cinfo.restart_interval / cinfo.restart_in_rows (tests/libjpeg9_encode.c) and against the plain Python
 restatement of its rules (tests/encode_rst_oracle.py).  Every output and workspace lies between sentinel margins."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """The device scan reader on the GPU (qs_hip_read_device_batch, torch_qs.read / read_batch): files written by libjpeg 9
-(tests/libjpeg9_encode_rst.c) against libjpeg 9's own read of them (tests/libjpeg9_decode.c), the round trip through the
+(tests/libjpeg9_encode.c) against libjpeg 9's own read of them (tests/libjpeg9_decode.c), the round trip through the
 device entropy coder, a captured graph, and the corrupt corpus of tests/test_read_host.py against the host build of the
 same csrc/qs_read.h.  Every array, file, status buffer and workspace lies between sentinel margins."""
 import numpy as np

@@ -1,5 +1,5 @@
 """The progressive route of the device scan reader on the GPU (qs_hip_read_prog_device_batch, torch_qs.read_progressive /
-read_progressive_batch / read_batch): files written by libjpeg 9 (tests/libjpeg9_encode_prog.c) against libjpeg 9's own
+read_progressive_batch / read_batch): files written by libjpeg 9 (tests/libjpeg9_encode.c) against libjpeg 9's own
 read of them (tests/libjpeg9_decode.c), the round trip through the device progressive coder, a captured graph, the
 dispatch of read_batch, and the corrupt corpus of tests/test_read_prog_host.py against the host build of the same
 csrc/qs_read_prog.h.  Every array, file, status buffer and workspace lies between sentinel margins."""

@@ -1,4 +1,4 @@
-"""jpeg_file.parse, the inverse of jpeg_file.compose, on files libjpeg 9 wrote (tests/libjpeg9_encode_rst.c): geometry,
+"""jpeg_file.parse, the inverse of jpeg_file.compose, on files libjpeg 9 wrote (tests/libjpeg9_encode.c): geometry,
 tables, restart interval and quantisers equal what went in, compose(parse(...)) reproduces the header bytes, and every
 form the device scan reader does not cover raises ValueError.  No device."""
 import struct

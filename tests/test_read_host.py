@@ -1,5 +1,5 @@
 """The device scan reader without a GPU: csrc/qs_read.h compiled for the host (tests/read_host.cpp) against libjpeg 9 at
-both ends -- files written by libjpeg (tests/libjpeg9_encode_rst.c), expected arrays read by libjpeg
+both ends -- files written by libjpeg (tests/libjpeg9_encode.c), expected arrays read by libjpeg
 (tests/libjpeg9_decode.c) -- and the same program under -fsanitize=address,undefined on a seeded corrupt corpus."""
 import re
 

@@ -1,5 +1,5 @@
 """The progressive route of the device scan reader without a GPU: csrc/qs_read_prog.h compiled for the host
-(tests/read_prog_host.cpp) against libjpeg 9 at both ends -- files written by libjpeg (tests/libjpeg9_encode_prog.c),
+(tests/read_prog_host.cpp) against libjpeg 9 at both ends -- files written by libjpeg (tests/libjpeg9_encode.c),
 expected arrays read by libjpeg (tests/libjpeg9_decode.c) -- jpeg_file.parse_progressive on the same files, and the same
 program under -fsanitize=address,undefined on a seeded corrupt corpus."""
 import struct

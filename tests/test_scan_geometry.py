@@ -2,27 +2,16 @@
 (qs_hip_encode_device_batch_info) and the reader's (qr_geometry of csrc/qs_read.h, compiled for the host:
 tests/geom_host.cpp) accept and refuse the same frames and agree on the blocks of an MCU, the blocks of each component
 and the blocks of the scan."""
-import os
-import shutil
 import subprocess
-from pathlib import Path
 
-import pytest
+from host_tools import build
 
-HERE = Path(__file__).resolve().parent
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
 SIZES = (1, 7, 8, 9, 16, 17, 65500)
 MAXBITS = 27 + 63 * 26                                        # QS_ENC_MAXBITS: the longest code of one block
 
 
 def _reader_grid(workdir):
-    exe = workdir / "geom_host"
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or "g++"
-    r = subprocess.run([cxx, "-std=c++17", "-Wall", "-O2", f"-I{CSRC}", "-o", str(exe), str(HERE / "geom_host.cpp")],
-                       capture_output=True, text=True)
-    if r.returncode or not exe.exists():
-        pytest.fail(f"tests/geom_host.cpp did not build:\n{r.stderr}")
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run([str(build("geom_host.cpp"))], capture_output=True, text=True, check=True).stdout
     return [[int(x) for x in line.split()] for line in out.splitlines()]
 
 

@@ -3,7 +3,6 @@ DESIGN.md section 12.1): the recorded fixtures of tests/golden/triangle (made by
 libjpeg-turbo as Pillow runs it), the host build of the filter (tests/decode_triangle_host.cpp), Pillow in a child
 process with and without turbo's SIMD code, and the arrays-with-junk variant of an image."""
 import os
-import shutil
 import struct
 import subprocess
 import sys
@@ -11,10 +10,10 @@ from pathlib import Path
 
 import numpy as np
 
-HERE = Path(__file__).resolve().parent
-CSRC = HERE.parent / "jpeg-quantsmooth_amd" / "csrc"
+from host_tools import HERE, Tool, build
+from wire import MAGIC, pack_image  # noqa: F401
+
 FIXDIR = HERE / "golden" / "triangle"
-MAGIC = 0x51534A43
 
 # the sizes of the mode's contract: both sides of the Wc <= 2 rule, the 64 x 16 tile and its neighbours, a halo that
 # crosses tile corners in both directions, and the suite's odd size
@@ -70,38 +69,22 @@ def with_junk(im, extra_w=2, extra_h=1, seed=5):
 
 
 def pack_case(im, planes=False) -> bytes:
-    parts = [struct.pack("<6i", 1 if planes else 0, MAGIC, len(im["coefs"]), im["image_size"][0], im["image_size"][1],
-                         im["colorspace"])]
-    for ci, c in enumerate(im["coefs"]):
-        parts.append(struct.pack("<5i", c.shape[1], c.shape[0], im["hsamp"][ci], im["vsamp"][ci], 1))
-        parts.append(np.asarray(im["quants"][ci], np.uint16).tobytes())
-    for c in im["coefs"]:
-        parts.append(np.ascontiguousarray(c, np.int16).tobytes())
-    return b"".join(parts)
+    return struct.pack("<i", 1 if planes else 0) + pack_image(im)
 
 
-class TriHost:
+class TriHost(Tool):
     """tests/decode_triangle_host.cpp: the triangle mode of csrc/qs_decode.h on the host, tile by tile as the kernel"""
+    SILENT = True
 
-    def __init__(self, workdir: Path, sanitize=False):
-        self.dir = Path(workdir)
-        self.exe = self.dir / ("decode_triangle_host_san" if sanitize else "decode_triangle_host")
-        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run([cxx or "g++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(self.exe),
-                            str(HERE / "decode_triangle_host.cpp")], capture_output=True, text=True)
-        if r.returncode or not self.exe.exists():
-            raise AssertionError(f"tests/decode_triangle_host.cpp did not build:\n{r.stderr}")
-        self.n = 0
+    def __init__(self, workdir, sanitize=False):
+        super().__init__(build("decode_triangle_host.cpp", sanitize=sanitize), workdir)
 
     def run(self, ims, planes=False):
         """-> one uint8 (H, W, C) per image: the pixels, or with planes the upsampled components without colour
         conversion; fails on a non-zero exit or anything on stderr (a sanitizer report)"""
-        self.n += 1
-        src, dst = self.dir / f"t{os.getpid()}_{self.n}.bin", self.dir / f"t{os.getpid()}_{self.n}.out"
+        src, dst = self.tmp(".bin"), self.tmp(".out")
         src.write_bytes(struct.pack("<i", len(ims)) + b"".join(pack_case(im, planes) for im in ims))
-        r = subprocess.run([str(self.exe), "run", str(src), str(dst)], capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, f"decode_triangle_host exit {r.returncode}:\n{r.stderr[-4000:]}"
+        self._run("run", src, dst)
         b = np.fromfile(dst, np.uint8)
         src.unlink()
         dst.unlink()

@@ -37,7 +37,7 @@ unless the first file of each case is libjpeg's optimized file.
 (job, scan) pair through histogram, table kernel, coder and framing) on the same three cases, in device time, next to the
 baseline whole-file run with optimized tables on the same arrays in the same process, with the ratio of the two and the
 sizes of the progressive and the baseline-optimized files.  Exits non-zero unless the first file of each case is the
-file libjpeg writes with that script (tests/libjpeg9_encode_prog.c).
+file libjpeg writes with that script (tests/libjpeg9_encode.c).
 --encode --progressive --script simple adds, per case, the run of jpeg_file.simple_progression (libjpeg's own script, four of
 its ten YCbCr scans refinement scans) next to the spectral run and the baseline run on the same arrays, the file sizes, and
 the time of the worst case of the refinement scans' run cutting (worst_case_last_bit_scan).
