@@ -405,6 +405,60 @@ def load_library(path: Path | None = None) -> C.CDLL:
     return lib
 
 
+def _ptr_array(rec, records, n, message):
+    """the array of pointers to `rec` records a batch call of n jobs takes, one slot at least; an entry None stays NULL.
+    records None: None, the call without them, where the ABI allows it.  Anything but n records: ValueError(message)"""
+    if records is None:
+        return None
+    if len(records) != n:
+        raise ValueError(message)
+    return (C.POINTER(rec) * max(1, n))(*[None if r is None else C.pointer(r) for r in records])
+
+
+def _named_ptrs(rec, field, names, what, opts, n):
+    """opts: one entry per job -- None (the call's default mode), a name of `names`, one of its values or a `rec` -> (the
+    pointer array, what it points to: keep it alive over the call); `what` and `field` word the refusals"""
+    if len(opts) != n:
+        raise ValueError(f"{what} opts: {len(opts)} entries for {n} jobs")
+    keep = []
+    for o in opts:
+        if o is not None and not isinstance(o, rec):
+            if isinstance(o, str):
+                if o not in names:
+                    raise ValueError(f"{what} opts: {field} {o!r} (one of {sorted(names)})")
+                o = names[o]
+            o = rec(**{field: int(o)})
+        keep.append(o)
+    return _ptr_array(rec, keep, n, None), keep
+
+
+_DECODE_MODES = (DecodeOpts, "upsampling", UPSAMPLING, "decode")             # what _named_ptrs takes for decode opts
+_COMPRESS_MODES = (CompressOpts, "downsampling", DOWNSAMPLING, "compress")   # ... and for compress opts
+
+
+def _fill_huff(tabs, arr, has, ids, who):
+    """tabs = {id: (bits[17], huffval)} or None into the HuffTable array `arr`, has[id] = 1 for each; ids: the ids the
+    record has room for"""
+    for k, (bits, vals) in (tabs or {}).items():
+        if k not in ids or len(bits) != 17 or len(vals) > 256:
+            raise ValueError(f"{who}: table {ids[0]}{' or ' if len(ids) == 2 else '..'}{ids[-1]}, bits[17], at most 256 "
+                             f"symbols")
+        arr[k].bits[:] = [int(b) for b in bits]
+        for i, v in enumerate(vals):
+            arr[k].huffval[i] = int(v)
+        has[k] = 1
+
+
+def _c_array(ctype, values):
+    """values (addresses, sizes, pitches) as the C array a batch call takes, one slot at least"""
+    return (ctype * max(1, len(values)))(*values)
+
+
+def _info_dict(rec):
+    """an info record of plain integers as a dict"""
+    return {f: int(getattr(rec, f)) for f, _ in rec._fields_}
+
+
 class HipQS:
     """Thin object wrapper: job layer on numpy arrays, plane layer on device pointers."""
 
@@ -436,7 +490,7 @@ class HipQS:
         """host-side constant block (uint8 array) for one component"""
         q = np.ascontiguousarray(quant, dtype=np.uint16)
         out = np.zeros(self.consts_bytes(), dtype=np.uint8)
-        self._check(self.lib.qs_hip_consts_build(out.ctypes.data, q.ctypes.data_as(C.POINTER(C.c_uint16)), flags))
+        self._check(self.lib.qs_hip_consts_build(out.ctypes.data, (C.c_uint16 * q.size).from_buffer_copy(q), flags))
         return out
 
     # -- band arithmetic (one definition, shared with csrc/qs_shard.cpp) ----------
@@ -541,7 +595,7 @@ class HipQS:
         (ret < 0: that job failed with this error code)"""
         made = [self._make_job(j["coefs"], j["quants"], j.get("hsamp"), j.get("vsamp"),
                                j.get("colorspace"), j.get("image_size")) for j in jobs]
-        ptrs = (C.POINTER(Job) * len(made))(*[C.pointer(m[0]) for m in made])
+        ptrs = self._job_ptrs([m[0] for m in made])
         results = (C.c_int * max(1, len(made)))()
         self._check(self.lib.qs_hip_do_quantsmooth_batch(ptrs, len(made), flags, niter, results))
         return [self._job_result(m[0], m[1], j["quants"], int(results[i])) for i, (m, j) in enumerate(zip(made, jobs))]
@@ -582,7 +636,7 @@ class HipQS:
         static_stop)"""
         info = DeviceInfo()
         self._check(self.lib.qs_hip_device_job_info(C.byref(job), flags, niter, C.byref(info)))
-        return {f: int(getattr(info, f)) for f, _ in DeviceInfo._fields_}
+        return _info_dict(info)
 
     def device_job_prepare(self, job: Job, flags: int, niter: int, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_device_job_prepare: the constant blocks into the workspace (synchronises `stream`; not inside a capture)"""
@@ -597,7 +651,7 @@ class HipQS:
     # -- device-resident batch (a list of device_job() Jobs) -------------------------
     @staticmethod
     def _job_ptrs(jobs):
-        return (C.POINTER(Job) * max(1, len(jobs)))(*[C.pointer(j) if j is not None else None for j in jobs])
+        return _ptr_array(Job, jobs, len(jobs), None)
 
     def device_batch_info(self, jobs, flags: int, niter: int):
         """qs_hip_device_batch_info (no device needed) -> (list of per-job dicts as device_job_info returns them,
@@ -605,7 +659,7 @@ class HipQS:
         per = (DeviceInfo * max(1, len(jobs)))()
         total = C.c_size_t(0)
         self._check(self.lib.qs_hip_device_batch_info(self._job_ptrs(jobs), len(jobs), flags, niter, per, C.byref(total)))
-        return [{f: int(getattr(per[i], f)) for f, _ in DeviceInfo._fields_} for i in range(len(jobs))], int(total.value)
+        return [_info_dict(p) for p in per[:len(jobs)]], int(total.value)
 
     def device_batch_prepare(self, jobs, flags: int, niter: int, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_device_batch_prepare: constants and descriptor tables into the workspace (synchronises `stream`; not
@@ -621,34 +675,13 @@ class HipQS:
                                                                 d_workspace, nbytes, d_stop, stream))
 
     # -- device decode to pixels (a list of device_job() Jobs) ---------------------------
-    @staticmethod
-    def _decode_opt_ptrs(opts, n):
-        """opts: one entry per job -- None (the dct mode), "dct" / "triangle", an UPSAMPLE_* value or a DecodeOpts -> (the
-        pointer array, what it points to: keep it alive over the call)"""
-        if len(opts) != n:
-            raise ValueError(f"decode opts: {len(opts)} entries for {n} jobs")
-        keep = []
-        for o in opts:
-            if o is None or isinstance(o, DecodeOpts):
-                keep.append(o)
-                continue
-            if isinstance(o, str):
-                if o not in UPSAMPLING:
-                    raise ValueError(f"decode opts: upsampling {o!r} (one of {sorted(UPSAMPLING)})")
-                o = UPSAMPLING[o]
-            rec = DecodeOpts()
-            rec.upsampling = int(o)
-            keep.append(rec)
-        arr = (C.POINTER(DecodeOpts) * max(1, n))(*[C.pointer(o) if o is not None else None for o in keep])
-        return arr, keep
-
     @classmethod
     def _decode_scale_ptrs(cls, opts, scales, n):
-        """scales: one scale_denom per job (None: full size); opts as _decode_opt_ptrs takes them or None -> (the pointer
+        """scales: one scale_denom per job (None: full size); opts as decode_batch_info takes them or None -> (the pointer
         array of DecodeScaleOpts, what it points to)"""
         if len(scales) != n:
             raise ValueError(f"decode scales: {len(scales)} entries for {n} jobs")
-        _arr, modes = cls._decode_opt_ptrs([None] * n if opts is None else opts, n)
+        _arr, modes = _named_ptrs(*_DECODE_MODES, [None] * n if opts is None else opts, n)
         keep = []
         for mode, d in zip(modes, scales):
             if isinstance(d, DecodeScaleOpts):
@@ -658,7 +691,7 @@ class HipQS:
             rec.upsampling = UPSAMPLE_DCT if mode is None else mode.upsampling
             rec.scale_denom = 1 if d is None else int(d)
             keep.append(rec)
-        return (C.POINTER(DecodeScaleOpts) * max(1, n))(*[C.pointer(o) for o in keep]), keep
+        return _ptr_array(DecodeScaleOpts, keep, n, None), keep
 
     def decode_batch_info(self, jobs, opts=None, scales=None):
         """qs_hip_decode_device_batch_info[_opts / _scaled] (no device needed) -> (list of dict(width, height, channels,
@@ -675,14 +708,10 @@ class HipQS:
         elif opts is None:
             self._check(self.lib.qs_hip_decode_device_batch_info(self._job_ptrs(jobs), len(jobs), per, C.byref(total)))
         else:
-            arr, _keep = self._decode_opt_ptrs(opts, len(jobs))
+            arr, _keep = _named_ptrs(*_DECODE_MODES, opts, len(jobs))
             self._check(self.lib.qs_hip_decode_device_batch_info_opts(self._job_ptrs(jobs), len(jobs), arr, per,
                                                                       C.byref(total)))
-        return [{f: int(getattr(per[i], f)) for f, _ in DecodeInfo._fields_} for i in range(len(jobs))], int(total.value)
-
-    @staticmethod
-    def _outs(d_out, pitch):
-        return (C.c_void_p * max(1, len(d_out)))(*d_out), (C.c_size_t * max(1, len(pitch)))(*pitch)
+        return [_info_dict(p) for p in per[:len(jobs)]], int(total.value)
 
     def decode_batch_prepare(self, jobs, d_workspace: int, nbytes: int, stream=None, opts=None, scales=None) -> None:
         """qs_hip_decode_device_batch_prepare[_opts / _scaled]: geometry, modes, scales and tables into the workspace
@@ -695,7 +724,7 @@ class HipQS:
             self._check(self.lib.qs_hip_decode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), d_workspace, nbytes,
                                                                     stream))
         else:
-            arr, _keep = self._decode_opt_ptrs(opts, len(jobs))
+            arr, _keep = _named_ptrs(*_DECODE_MODES, opts, len(jobs))
             self._check(self.lib.qs_hip_decode_device_batch_prepare_opts(self._job_ptrs(jobs), len(jobs), arr,
                                                                          d_workspace, nbytes, stream))
 
@@ -703,32 +732,10 @@ class HipQS:
         """qs_hip_decode_device_batch: enqueue the decode of every job (one launch per 44 jobs); d_out[i] = device
         address of job i's output, pitch[i] = bytes between its rows; d_stop: the device int32[njobs] a
         smoothing run wrote (picks each UPSAMPLE_UV job's geometry on the device) or None"""
-        outs, pitches = self._outs(d_out, pitch)
-        self._check(self.lib.qs_hip_decode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, pitches,
-                                                        d_workspace, nbytes, stream))
+        self._check(self.lib.qs_hip_decode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, _c_array(C.c_void_p, d_out),
+                                                        _c_array(C.c_size_t, pitch), d_workspace, nbytes, stream))
 
     # -- device compress of pixels (a list of device_job() Jobs over the arrays to fill) ---
-    @staticmethod
-    def _compress_opt_ptrs(opts, n):
-        """opts: one entry per job -- None (the box mode), "box" / "dct", a DOWNSAMPLE_* value or a CompressOpts -> (the
-        pointer array, what it points to: keep it alive over the call)"""
-        if len(opts) != n:
-            raise ValueError(f"compress opts: {len(opts)} entries for {n} jobs")
-        keep = []
-        for o in opts:
-            if o is None or isinstance(o, CompressOpts):
-                keep.append(o)
-                continue
-            if isinstance(o, str):
-                if o not in DOWNSAMPLING:
-                    raise ValueError(f"compress opts: downsampling {o!r} (one of {sorted(DOWNSAMPLING)})")
-                o = DOWNSAMPLING[o]
-            rec = CompressOpts()
-            rec.downsampling = int(o)
-            keep.append(rec)
-        arr = (C.POINTER(CompressOpts) * max(1, n))(*[C.pointer(o) if o is not None else None for o in keep])
-        return arr, keep
-
     def compress_batch_info(self, jobs, fancy: bool = False, opts=None):
         """qs_hip_compress_device_batch_info[_opts] (no device needed) -> (list of dict(width, height, channels, layout,
         wblk, hblk: libjpeg's block geometry per component), the batch's workspace bytes).  opts: None (the call without
@@ -740,7 +747,7 @@ class HipQS:
             self._check(self.lib.qs_hip_compress_device_batch_info(self._job_ptrs(jobs), len(jobs), int(bool(fancy)), per,
                                                                    C.byref(total)))
         else:
-            arr, _keep = self._compress_opt_ptrs(opts, len(jobs))
+            arr, _keep = _named_ptrs(*_COMPRESS_MODES, opts, len(jobs))
             self._check(self.lib.qs_hip_compress_device_batch_info_opts(self._job_ptrs(jobs), len(jobs), arr, per,
                                                                         C.byref(total)))
         out = []
@@ -758,28 +765,23 @@ class HipQS:
             self._check(self.lib.qs_hip_compress_device_batch_prepare(self._job_ptrs(jobs), len(jobs), int(bool(fancy)),
                                                                       d_workspace, nbytes, stream))
         else:
-            arr, _keep = self._compress_opt_ptrs(opts, len(jobs))
+            arr, _keep = _named_ptrs(*_COMPRESS_MODES, opts, len(jobs))
             self._check(self.lib.qs_hip_compress_device_batch_prepare_opts(self._job_ptrs(jobs), len(jobs), arr,
                                                                            d_workspace, nbytes, stream))
 
     def compress_batch(self, jobs, d_pixels, pitch, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_compress_device_batch: enqueue the compress of every job (one launch per 44 jobs); d_pixels[i] = device
         address of job i's interleaved uint8 pixels, pitch[i] = bytes between its rows; the arrays are job.coef"""
-        pix, pitches = self._outs(d_pixels, pitch)
-        self._check(self.lib.qs_hip_compress_device_batch(self._job_ptrs(jobs), len(jobs), pix, pitches, d_workspace,
-                                                          nbytes, stream))
+        self._check(self.lib.qs_hip_compress_device_batch(self._job_ptrs(jobs), len(jobs), _c_array(C.c_void_p, d_pixels),
+                                                          _c_array(C.c_size_t, pitch), d_workspace, nbytes, stream))
 
     # -- device entropy coder (a list of device_job() Jobs) -------------------------------
     @staticmethod
     def _opt_ptrs(opts, n):
         """opts: None, or one (restart_interval, restart_in_rows) / None per job -> (the pointer array or None, what it
         points to: keep it alive over the call)"""
-        if opts is None:
-            return None, None
-        if len(opts) != n:
-            raise ValueError("one options entry (or None) per job")
-        recs = [None if o is None else EncodeOpts(int(o[0]), int(o[1])) for o in opts]
-        return (C.POINTER(EncodeOpts) * max(1, n))(*[None if r is None else C.pointer(r) for r in recs]), recs
+        recs = None if opts is None else [None if o is None else EncodeOpts(int(o[0]), int(o[1])) for o in opts]
+        return _ptr_array(EncodeOpts, recs, n, "one options entry (or None) per job"), recs
 
     def encode_batch_info(self, jobs, opts=None):
         """qs_hip_encode_device_batch_info, or _info_opts when opts is given (one (restart_interval, restart_in_rows) or
@@ -801,23 +803,15 @@ class HipQS:
     def huff_tables(dc=None, ac=None) -> HuffTables:
         """a qs_hip_huff_tables: dc / ac = {table index: (bits[17], huffval)}; a table left out is the standard one"""
         t = HuffTables()
-        for tabs, arr, has in ((dc or {}, t.dc, t.has_dc), (ac or {}, t.ac, t.has_ac)):
-            for k, (bits, vals) in tabs.items():
-                if k not in (0, 1) or len(bits) != 17 or len(vals) > 256:
-                    raise ValueError("huff_tables: table 0 or 1, bits[17], at most 256 symbols")
-                arr[k].bits[:] = [int(b) for b in bits]
-                for i, v in enumerate(vals):
-                    arr[k].huffval[i] = int(v)
-                has[k] = 1
+        _fill_huff(dc, t.dc, t.has_dc, (0, 1), "huff_tables")
+        _fill_huff(ac, t.ac, t.has_ac, (0, 1), "huff_tables")
         return t
 
     def encode_batch_prepare(self, jobs, tables, d_workspace: int, nbytes: int, stream=None, opts=None) -> None:
         """qs_hip_encode_device_batch_prepare, or _prepare_opts when opts is given (as encode_batch_info): geometry, code
         tables and restart intervals into the workspace (synchronises `stream`; not inside a capture); tables: None or
         one HuffTables / None per job"""
-        ptrs = None
-        if tables is not None:
-            ptrs = (C.POINTER(HuffTables) * max(1, len(jobs)))(*[C.pointer(t) if t is not None else None for t in tables])
+        ptrs = _ptr_array(HuffTables, tables, len(jobs), "one HuffTables (or None) per job")
         if opts is None:
             self._check(self.lib.qs_hip_encode_device_batch_prepare(self._job_ptrs(jobs), len(jobs), ptrs, d_workspace,
                                                                     nbytes, stream))
@@ -830,9 +824,9 @@ class HipQS:
                      stream=None) -> None:
         """qs_hip_encode_device_batch: enqueue the scan coder of every job; d_out[i] = device address of job i's buffer
         of capacity[i] bytes, d_len / d_status = device uint64[njobs] / int32[njobs]"""
-        outs, caps = self._outs(d_out, capacity)
-        self._check(self.lib.qs_hip_encode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, outs, caps, d_len,
-                                                        d_status, d_workspace, nbytes, stream))
+        self._check(self.lib.qs_hip_encode_device_batch(self._job_ptrs(jobs), len(jobs), d_stop, _c_array(C.c_void_p, d_out),
+                                                        _c_array(C.c_size_t, capacity), d_len, d_status, d_workspace, nbytes,
+                                                        stream))
 
     def encode_batch_histogram(self, jobs, d_stop, d_counts: int, d_status: int, d_workspace: int, nbytes: int,
                                stream=None) -> None:
@@ -860,20 +854,22 @@ class HipQS:
                     ptr[v], nb[v] = part[v][0] or None, int(part[v][1])
         return f
 
+    @staticmethod
+    def _frames(frames, n):
+        if len(frames) != n:
+            raise ValueError("one EncodeFrame per job")
+        return _c_array(EncodeFrame, frames)
+
     def encode_batch_files(self, jobs, frames, optimize, d_stop, d_out, capacity, d_len: int, d_status: int, d_tables,
                            d_scratch: int, scratch_bytes: int, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_encode_device_batch_files: enqueue whole files -- head, DHT markers (optimize), mid, segment, EOI -- into
         d_out[i]; frames: None (markers and segment only) or one EncodeFrame per job; d_tables: device
         qs_hip_huff_tables[njobs] or None; the workspace as encode_batch takes it"""
-        outs, caps = self._outs(d_out, capacity)
-        fr = None
-        if frames is not None:
-            if len(frames) != len(jobs):
-                raise ValueError("one EncodeFrame per job")
-            fr = (EncodeFrame * max(1, len(jobs)))(*frames)
+        fr = None if frames is None else self._frames(frames, len(jobs))
         self._check(self.lib.qs_hip_encode_device_batch_files(self._job_ptrs(jobs), len(jobs), fr, 1 if optimize else 0,
-                                                              d_stop, outs, caps, d_len, d_status, d_tables, d_scratch,
-                                                              scratch_bytes, d_workspace, nbytes, stream))
+                                                              d_stop, _c_array(C.c_void_p, d_out),
+                                                              _c_array(C.c_size_t, capacity), d_len, d_status, d_tables,
+                                                              d_scratch, scratch_bytes, d_workspace, nbytes, stream))
 
     # -- progressive files (spectral selection) ---------------------------------------------
     @staticmethod
@@ -898,9 +894,7 @@ class HipQS:
 
     @staticmethod
     def _prog_opt_ptrs(opts, n):
-        if len(opts) != n:
-            raise ValueError("one EncodeProgOpts per job")
-        return (C.POINTER(EncodeProgOpts) * max(1, n))(*[C.pointer(o) for o in opts])
+        return _ptr_array(EncodeProgOpts, opts, n, "one EncodeProgOpts per job")
 
     def encode_progressive_info(self, jobs, opts):
         """qs_hip_encode_progressive_device_batch_info; no device needed -> (list of dict(nscans, mcus, interval,
@@ -924,13 +918,11 @@ class HipQS:
                                  scratch_bytes: int, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_encode_progressive_device_batch_files: enqueue whole progressive files into d_out[i]; frames: one
         EncodeFrame per job (its heads: SOI .. SOF2)"""
-        outs, caps = self._outs(d_out, capacity)
-        if len(frames) != len(jobs):
-            raise ValueError("one EncodeFrame per job")
-        fr = (EncodeFrame * max(1, len(jobs)))(*frames)
-        self._check(self.lib.qs_hip_encode_progressive_device_batch_files(self._job_ptrs(jobs), len(jobs), fr, d_stop, outs,
-                                                                          caps, d_len, d_status, d_scratch, scratch_bytes,
-                                                                          d_workspace, nbytes, stream))
+        self._check(self.lib.qs_hip_encode_progressive_device_batch_files(self._job_ptrs(jobs), len(jobs),
+                                                                          self._frames(frames, len(jobs)), d_stop,
+                                                                          _c_array(C.c_void_p, d_out),
+                                                                          _c_array(C.c_size_t, capacity), d_len, d_status,
+                                                                          d_scratch, scratch_bytes, d_workspace, nbytes, stream))
 
     # -- device scan reader (a list of device_job() Jobs over the arrays to fill) ---------
     @staticmethod
@@ -938,14 +930,8 @@ class HipQS:
         """a qs_hip_read_opts: dc / ac = {DHT id 0..3: (bits[17], huffval)} (a table left out is the standard one),
         dc_tbl / ac_tbl = Td / Ta of each component, restart_interval = the DRI value"""
         o = ReadOpts()
-        for tabs, arr, has in ((dc or {}, o.dc, o.has_dc), (ac or {}, o.ac, o.has_ac)):
-            for k, (bits, vals) in tabs.items():
-                if k not in (0, 1, 2, 3) or len(bits) != 17 or len(vals) > 256:
-                    raise ValueError("read_opts: table 0..3, bits[17], at most 256 symbols")
-                arr[k].bits[:] = [int(b) for b in bits]
-                for i, v in enumerate(vals):
-                    arr[k].huffval[i] = int(v)
-                has[k] = 1
+        _fill_huff(dc, o.dc, o.has_dc, (0, 1, 2, 3), "read_opts")
+        _fill_huff(ac, o.ac, o.has_ac, (0, 1, 2, 3), "read_opts")
         for ci, (td, ta) in enumerate(zip(dc_tbl, ac_tbl)):
             o.dc_tbl[ci], o.ac_tbl[ci] = int(td), int(ta)
         o.restart_interval = int(restart_interval)
@@ -953,9 +939,7 @@ class HipQS:
 
     @staticmethod
     def _read_opt_ptrs(opts, n):
-        if len(opts) != n:
-            raise ValueError("one ReadOpts per job")
-        return (C.POINTER(ReadOpts) * max(1, n))(*[None if o is None else C.pointer(o) for o in opts])
+        return _ptr_array(ReadOpts, opts, n, "one ReadOpts per job")
 
     def read_batch_info(self, jobs, opts, split=False):
         """qs_hip_read_device_batch_info (no device needed) -> (list of dict(blocks_in_mcu, mcus, intervals,
@@ -966,7 +950,7 @@ class HipQS:
         per = (info * max(1, len(jobs)))()
         total = C.c_size_t(0)
         self._check(call(self._job_ptrs(jobs), len(jobs), self._read_opt_ptrs(opts, len(jobs)), per, C.byref(total)))
-        return [{f: int(getattr(per[i], f)) for f, _ in info._fields_} for i in range(len(jobs))], int(total.value)
+        return [_info_dict(p) for p in per[:len(jobs)]], int(total.value)
 
     def read_batch_prepare(self, jobs, opts, d_workspace: int, nbytes: int, stream=None, split=False) -> None:
         """qs_hip_read_device_batch_prepare (split: qs_hip_read_split_device_batch_prepare): geometry and derived code
@@ -979,8 +963,7 @@ class HipQS:
         """qs_hip_read_device_batch (split: qs_hip_read_split_device_batch): enqueue the scan reader of every job;
         d_scan[i] = device address of job i's bytes behind the SOS header, scan_bytes[i] = how many may be read,
         d_status = device int32[njobs]"""
-        scans = (C.c_void_p * max(1, len(d_scan)))(*d_scan)
-        lens = (C.c_uint64 * max(1, len(scan_bytes)))(*[int(v) for v in scan_bytes])
+        scans, lens = _c_array(C.c_void_p, d_scan), _c_array(C.c_uint64, [int(v) for v in scan_bytes])
         call = self.lib.qs_hip_read_split_device_batch if split else self.lib.qs_hip_read_device_batch
         self._check(call(self._job_ptrs(jobs), len(jobs), scans, lens, d_status, d_workspace, nbytes, stream))
 
@@ -999,14 +982,8 @@ class HipQS:
             r.scan.Ss, r.scan.Se, r.scan.Ah, r.scan.Al = int(s["ss"]), int(s["se"]), int(s["ah"]), int(s["al"])
             for k, (td, ta) in enumerate(list(zip(s["dc_tbl"], s["ac_tbl"]))[:4]):
                 r.dc_tbl[k], r.ac_tbl[k] = int(td), int(ta)
-            for tabs, dst, has in ((s.get("dc") or {}, r.dc, r.has_dc), (s.get("ac") or {}, r.ac, r.has_ac)):
-                for k, (bits, vals) in tabs.items():
-                    if k not in (0, 1, 2, 3) or len(bits) != 17 or len(vals) > 256:
-                        raise ValueError("read_prog_opts: table 0..3, bits[17], at most 256 symbols")
-                    dst[k].bits[:] = [int(b) for b in bits]
-                    for i, v in enumerate(vals):
-                        dst[k].huffval[i] = int(v)
-                    has[k] = 1
+            _fill_huff(s.get("dc"), r.dc, r.has_dc, (0, 1, 2, 3), "read_prog_opts")
+            _fill_huff(s.get("ac"), r.ac, r.has_ac, (0, 1, 2, 3), "read_prog_opts")
             r.restart_interval = int(s["restart_interval"])
             r.offset = int(s["offset"])
         o = ReadProgOpts(C.cast(arr, C.POINTER(ReadProgScan)), len(scans))
@@ -1015,9 +992,7 @@ class HipQS:
 
     @staticmethod
     def _read_prog_opt_ptrs(opts, n):
-        if len(opts) != n:
-            raise ValueError("one ReadProgOpts per job")
-        return (C.POINTER(ReadProgOpts) * max(1, n))(*[None if o is None else C.pointer(o) for o in opts])
+        return _ptr_array(ReadProgOpts, opts, n, "one ReadProgOpts per job")
 
     def read_prog_batch_info(self, jobs, opts):
         """qs_hip_read_prog_device_batch_info (no device needed) -> (list of dict(nscans, levels, mcus, intervals), the
@@ -1040,8 +1015,7 @@ class HipQS:
     def read_prog_batch(self, jobs, d_file, file_bytes, d_status: int, d_workspace: int, nbytes: int, stream=None) -> None:
         """qs_hip_read_prog_device_batch: enqueue the progressive reader of every job; d_file[i] = device address of job
         i's whole file, file_bytes[i] = how many bytes may be read there, d_status = device int32[njobs]"""
-        files = (C.c_void_p * max(1, len(d_file)))(*d_file)
-        lens = (C.c_uint64 * max(1, len(file_bytes)))(*[int(v) for v in file_bytes])
+        files, lens = _c_array(C.c_void_p, d_file), _c_array(C.c_uint64, [int(v) for v in file_bytes])
         self._check(self.lib.qs_hip_read_prog_device_batch(self._job_ptrs(jobs), len(jobs), files, lens, d_status,
                                                            d_workspace, nbytes, stream))
 

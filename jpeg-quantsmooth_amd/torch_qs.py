@@ -45,6 +45,8 @@ downsampling="dct" (libjpeg 9's own default: 2x chroma through 16-point scaled f
 torch is imported on first use only: importing the package does not need it."""
 from __future__ import annotations
 
+from functools import partial
+
 import numpy as np
 
 from .hipqs import HipQS
@@ -115,6 +117,78 @@ def _check_quants(quants, n, who="quantsmooth_"):
     return qs
 
 
+def _device_job(hip, coefs, quants, **kw):
+    """the qs_hip_job over coefficient tensors (kw: HipQS.device_job's keywords)"""
+    return hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], quants, **kw)
+
+
+def _prepared(workspace, key, total, dev, prepare, who, same, in_place=True):
+    """The workspace step of every stage: `workspace` as it is when it was prepared for `key`, else prepared for it -- by
+    prepare(address, bytes, stream) on dev's current stream, in a buffer of at least `total` bytes -- and keyed.  The key
+    is what the layout and its constants depend on, everything but the array addresses; it starts with the stage's tag,
+    so a workspace that comes from another stage is prepared again.  Preparing synchronises, so inside a graph capture it
+    is refused; `same` words what the earlier call must have shared ("on the same geometry and tables (workspace=...)").
+
+    A buffer that is too small or on another device is replaced in one of two ways.  in_place, every stage but the
+    smoothing: the passed object gets the new buffer, and None stands for an empty Workspace() -- decode() and the other
+    single-image forms return no dict that could carry a new object.  Not in_place, quantsmooth_ and quantsmooth_batch_:
+    the passed object stays as it was, and a new Workspace is returned for the result dict to carry."""
+    import torch
+    if workspace is None and in_place:
+        workspace = Workspace()
+    if workspace is None or workspace.key != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call {same}: "
+                               f"preparing one synchronises")
+        if workspace is None or workspace.buf is None or workspace.nbytes < total or workspace.buf.device != dev:
+            buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+            if in_place:
+                workspace.buf = buf
+            else:
+                workspace = Workspace(buf)
+        prepare(workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
+        workspace.key = key
+    return workspace
+
+
+def _check_list(images, who):
+    if not isinstance(images, (list, tuple)) or not images:
+        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+
+
+def _images_on_one_device(images, result, who, needs, one, torch):
+    """what the batch calls check of their images: a non-empty list of dicts that hold `needs`, all on one device, and
+    `result` -- a smoothing result or None -- with one entry per image and its stop tensor on that device.
+    one(i, image, the result's entry or None) checks image i as its stage requires, keeps what the stage needs of it and
+    returns its device -> (the device, the stop tensor or None)"""
+    _check_list(images, who)
+    if result is not None and len(result["images"]) != len(images):
+        raise ValueError(f"{who}: result holds {len(result['images'])} images, the batch {len(images)}")
+    dev, keys, entries = None, set(needs), [None] * len(images) if result is None else result["images"]
+    for i, (im, res) in enumerate(zip(images, entries)):
+        if not isinstance(im, dict) or not im.keys() >= keys:
+            raise ValueError(f"{who}: image {i} must be a dict with {' and '.join(needs)}")
+        d = one(i, im, res)
+        if dev is None:
+            dev = d
+        elif d != dev:
+            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
+    stop = None
+    if result is not None:
+        stop = result["stop"]
+        _check_stop(stop, len(images), dev, who, torch)
+    return dev, stop
+
+
+def _batch_result(result):
+    """a single image's smoothing result as the result of a batch of one"""
+    return None if result is None else dict(stop=result["stop"], images=[result])
+
+
+def _outs_of(out):
+    return None if out is None else [out]
+
+
 def _enqueue(jobs, tables, dev, flags, niter, workspace, who, single):
     """what quantsmooth_ (single: the single-job calls) and quantsmooth_batch_ share: the workspace, prepared outside
     any capture when the jobs changed; the replacement chroma tensors; the run on the current stream; what it reports"""
@@ -128,15 +202,10 @@ def _enqueue(jobs, tables, dev, flags, niter, workspace, who, single):
         arg, prepare, run = jobs, hip.device_batch_prepare, hip.do_quantsmooth_device_batch
         per, total = hip.device_batch_info(jobs, flags, niter)
     key = (single,) + tuple(_key(job, flags, niter) for job in jobs)     # (a job alone is laid out unlike a batch of one)
+    workspace = _prepared(workspace, key, total, dev,
+                          lambda ptr, nbytes, stream: prepare(arg, flags, niter, ptr, nbytes, stream), who,
+                          f"of the same {'job' if single else 'batch'} (workspace=res['workspace'])", in_place=False)
     stream = torch.cuda.current_stream(dev)
-    if workspace is None or workspace.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call of the same "
-                               f"{'job' if single else 'batch'} (workspace=res['workspace']): preparing one synchronises")
-        if workspace is None or workspace.nbytes < total or workspace.buf.device != dev:
-            workspace = Workspace(torch.empty(max(1, total), dtype=torch.uint8, device=dev))
-        prepare(arg, flags, niter, workspace.buf.data_ptr(), workspace.nbytes, stream.cuda_stream)
-        workspace.key = key
     ups = []
     for job, inf in zip(jobs, per):
         up = None
@@ -168,8 +237,7 @@ def quantsmooth_(coefs, quants, flags: int, niter: int, *, hsamp=None, vsamp=Non
     import torch
     dev = _check_tensors(coefs, torch)
     qs = _check_quants(quants, len(coefs))
-    job = _hip().device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hsamp,
-                            vsamp=vsamp, colorspace=colorspace, image_size=image_size)
+    job = _device_job(_hip(), coefs, qs, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace, image_size=image_size)
     stop, (out,), workspace = _enqueue([job], [qs], dev, flags, niter, workspace, "quantsmooth_", True)
     return dict(stop=stop, **out, workspace=workspace)
 
@@ -187,29 +255,24 @@ def quantsmooth_batch_(images, flags: int, niter: int, *, workspace: Workspace |
       workspace  the Workspace used; pass it again (also inside a graph capture) for a batch of the same geometry"""
     import torch
     who = "quantsmooth_batch_"
-    if not isinstance(images, (list, tuple)) or not images:
-        raise ValueError(f"{who}: images must be a non-empty list of dicts")
-    dev, seen, jobs, tables = None, set(), [], []
     hip = _hip()
-    for i, im in enumerate(images):
-        if not isinstance(im, dict) or "coefs" not in im or "quants" not in im:
-            raise ValueError(f"{who}: image {i} must be a dict with coefs and quants")
+    seen, jobs, tables = set(), [], []
+
+    def one(i, im, _res):
         coefs = im["coefs"]
         if isinstance(coefs, (list, tuple)) and coefs:      # (the tables first: they need no device)
             qs = _check_quants(im["quants"], len(coefs), who=f"{who}: image {i}")
         d = _check_tensors(coefs, torch, who=f"{who}: image {i}")
-        if dev is None:
-            dev = d
-        elif d != dev:
-            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
         for t in coefs:
             if t.data_ptr() in seen:
                 raise ValueError(f"{who}: image {i} passes a tensor (or its storage) that appears earlier in the batch")
             seen.add(t.data_ptr())
         tables.append(qs)
-        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs,
-                                   hsamp=im.get("hsamp"), vsamp=im.get("vsamp"), colorspace=im.get("colorspace"),
-                                   image_size=im.get("image_size")))
+        jobs.append(_device_job(hip, coefs, qs, hsamp=im.get("hsamp"), vsamp=im.get("vsamp"),
+                                colorspace=im.get("colorspace"), image_size=im.get("image_size")))
+        return d
+
+    dev, _stop = _images_on_one_device(images, None, who, ("coefs", "quants"), one, torch)
     stop, out, workspace = _enqueue(jobs, tables, dev, flags, niter, workspace, who, False)
     return dict(stop=stop, images=out, workspace=workspace)
 
@@ -226,9 +289,8 @@ def _decode_job(hip, coefs, quants, im, res, who, torch):
     up = res.get("coef_up") if res is not None else None
     if up is not None:
         _check_tensors(list(up), torch, who=f"{who}: coef_up")
-    job = hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=im.get("hsamp"),
-                         vsamp=im.get("vsamp"), colorspace=im.get("colorspace"), image_size=im.get("image_size"),
-                         coef_up=None if up is None else (up[0].data_ptr(), up[1].data_ptr()))
+    job = _device_job(hip, coefs, qs, hsamp=im.get("hsamp"), vsamp=im.get("vsamp"), colorspace=im.get("colorspace"),
+                      image_size=im.get("image_size"), coef_up=None if up is None else (up[0].data_ptr(), up[1].data_ptr()))
     if up is not None:
         job.up_hblk, job.up_wblk = int(up[0].shape[0]), int(up[0].shape[1])
     return job
@@ -257,17 +319,9 @@ def _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes=None, scales=No
     per, total = hip.decode_batch_info(jobs, modes, scales)
     key = ("decode",) + tuple(_key(job, 0, 0) for job in jobs) + (() if modes is None else ("upsampling", tuple(modes))) \
         + (() if scales is None else ("scale_denom", tuple(scales)))
-    if workspace is None:
-        workspace = Workspace()
-    if workspace.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
-                               f"geometry (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:      # (filled in place: decode() returns no dict)
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.decode_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream,
-                                 modes, scales)
-        workspace.key = key
+    workspace = _prepared(workspace, key, total, dev,
+                          lambda ptr, nbytes, stream: hip.decode_batch_prepare(jobs, ptr, nbytes, stream, modes, scales),
+                          who, "on the same geometry (workspace=...)")
     if outs is None:
         outs = [None] * len(jobs)
     res = []
@@ -317,8 +371,7 @@ def decode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
     reused as it is inside one: pass the same object to the call that is captured."""
     r = decode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                            image_size=image_size)],
-                     result=None if result is None else dict(stop=result["stop"], images=[result]),
-                     outs=None if out is None else [out], workspace=workspace, upsampling=upsampling,
+                     result=_batch_result(result), outs=_outs_of(out), workspace=workspace, upsampling=upsampling,
                      scale_denom=scale_denom, _who="decode")
     return r["images"][0]
 
@@ -336,8 +389,7 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
     import torch
     who = _who
     _upsampling(upsampling, who)
-    if not isinstance(images, (list, tuple)) or not images:
-        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    _check_list(images, who)
     modes = [upsampling if not isinstance(im, dict) or im.get("upsampling") is None
              else _upsampling(im["upsampling"], f"{who}: image {i}") for i, im in enumerate(images)]
     if isinstance(scale_denom, (list, tuple)):
@@ -359,28 +411,9 @@ def decode_batch(images, *, result=None, outs=None, workspace: Workspace | None 
     for i, im in enumerate(images):
         if isinstance(im, dict) and im.get("image_size") is None:
             raise ValueError(f"{who}: image {i} has no image_size: the decode needs (width, height)")
-    if result is not None and len(result["images"]) != len(images):
-        raise ValueError(f"{who}: result holds {len(result['images'])} images, the batch {len(images)}")
     if outs is not None and len(outs) != len(images):
         raise ValueError(f"{who}: one output (or None) per image")
-    hip = _hip()
-    dev, jobs = None, []
-    for i, im in enumerate(images):
-        if not isinstance(im, dict) or "coefs" not in im:
-            raise ValueError(f"{who}: image {i} must be a dict with coefs")
-        res = None if result is None else result["images"][i]
-        if res is None and im.get("quants") is None:
-            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
-        d = _check_tensors(im["coefs"], torch, who=f"{who}: image {i}")
-        if dev is None:
-            dev = d
-        elif d != dev:
-            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
-        jobs.append(_decode_job(hip, im["coefs"], im.get("quants"), im, res, f"{who}: image {i}", torch))
-    stop = None
-    if result is not None:
-        stop = result["stop"]
-        _check_stop(stop, len(images), dev, who, torch)
+    jobs, dev, stop = _encode_jobs(images, result, who, torch, needs_quants=True)
     px, workspace = _decode_enqueue(jobs, dev, stop, outs, workspace, who, modes, scales)
     return dict(images=px, workspace=workspace)
 
@@ -398,30 +431,23 @@ def _huff_tables(hip, huffman, n, who):
     return tabs, b"|".join(b"" if t is None else bytes(t) for t in tabs)
 
 
-def _encode_jobs(images, result, who, torch):
-    if not isinstance(images, (list, tuple)) or not images:
-        raise ValueError(f"{who}: images must be a non-empty list of dicts")
-    if result is not None and len(result["images"]) != len(images):
-        raise ValueError(f"{who}: result holds {len(result['images'])} images, the batch {len(images)}")
+def _encode_jobs(images, result, who, torch, needs_quants=False):
+    """the qs_hip_jobs of images that hold coefs, their device, and the smoothing result's stop tensor (or None).
+    needs_quants (decode_batch): an image without a smoothing result must bring its tables; the scan coder needs none"""
     hip = _hip()
-    dev, jobs = None, []
-    for i, im in enumerate(images):
-        if not isinstance(im, dict) or "coefs" not in im:
-            raise ValueError(f"{who}: image {i} must be a dict with coefs")
+    jobs = []
+
+    def one(i, im, res):
         if im.get("image_size") is None:
             raise ValueError(f"{who}: image {i} has no image_size: the encoder needs (width, height)")
-        res = None if result is None else result["images"][i]
+        if needs_quants and res is None and im.get("quants") is None:
+            raise ValueError(f"{who}: image {i} needs quants (or a smoothing result)")
         d = _check_tensors(im["coefs"], torch, who=f"{who}: image {i}")
-        if dev is None:
-            dev = d
-        elif d != dev:
-            raise ValueError(f"{who}: image {i} is on {d}, image 0 on {dev}")
         quants = im.get("quants") if im.get("quants") is not None else [None] * len(im["coefs"])
         jobs.append(_decode_job(hip, im["coefs"], quants, im, res, f"{who}: image {i}", torch))
-    stop = None
-    if result is not None:
-        stop = result["stop"]
-        _check_stop(stop, len(images), dev, who, torch)
+        return d
+
+    dev, stop = _images_on_one_device(images, result, who, ("coefs",), one, torch)
     return jobs, dev, stop
 
 
@@ -441,6 +467,23 @@ def _restart_opts(restart_interval, restart_in_rows, n, who):
             raise ValueError(f"{who}: {name} must be an int or hold one per image")
         cols.append(vals)
     return list(zip(*cols))
+
+
+def _block_shapes(w, h, hsamp, vsamp):
+    """(hblk, wblk) of each component of a w x h image with these sampling factors: libjpeg's height_in_blocks and
+    width_in_blocks, ceil(size * samp / (8 * max_samp))"""
+    w, h, mh, mv = int(w), int(h), 8 * max(hsamp), 8 * max(vsamp)
+    return [(-(-h * v // mv), -(-w * s // mh)) for s, v in zip(hsamp, vsamp)]
+
+
+def _coef_outs(outs, i, shapes, dev, who, torch):
+    """the coefficient tensors image i is written to: new ones of `shapes`, or the caller's outs[i], checked"""
+    if outs is None or outs[i] is None:
+        return [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
+    coefs = list(outs[i])
+    if len(coefs) != len(shapes) or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
+        raise ValueError(f"{who}: output {i} must be {len(shapes)} tensors on {dev}")
+    return coefs
 
 
 def _mcu_geometry(hsamp, vsamp, image_size):
@@ -463,18 +506,9 @@ def _encode_workspace(jobs, dev, tabs, tabkey, workspace, who, torch, opts=None)
     hip = _hip()
     per, total = hip.encode_batch_info(jobs, opts)
     key = ("encode", tabkey) + tuple(_key(job, 0, 0) for job in jobs) + (() if opts is None else ("restart", tuple(opts)))
-    if workspace is None:
-        workspace = Workspace()
-    if workspace.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
-                               f"geometry and tables (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.encode_batch_prepare(jobs, tabs, workspace.buf.data_ptr(), workspace.nbytes,
-                                 torch.cuda.current_stream(dev).cuda_stream, opts)
-        workspace.key = key
-    return per, workspace
+    return per, _prepared(workspace, key, total, dev,
+                          lambda ptr, nbytes, stream: hip.encode_batch_prepare(jobs, tabs, ptr, nbytes, stream, opts),
+                          who, "on the same geometry and tables (workspace=...)")
 
 
 def _encode_outs(outs, images, per, dev, default_bytes, who, torch):
@@ -584,8 +618,7 @@ def encode_scan(coefs, *, hsamp=None, vsamp=None, colorspace=None, image_size=No
     """encode_scan_batch on one image -> dict(segment, len, status, workspace); len and status are device tensors of
     one element"""
     r = _encode_scan_batch([dict(coefs=coefs, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace, image_size=image_size)],
-                           None if result is None else dict(stop=result["stop"], images=[result]), huffman,
-                           None if out is None else [out], workspace, "encode_scan",
+                           _batch_result(result), huffman, _outs_of(out), workspace, "encode_scan",
                            _restart_opts(restart_interval, restart_in_rows, 1, "encode_scan"))
     return dict(segment=r["segments"][0], len=r["len"], status=r["status"], workspace=r["workspace"])
 
@@ -688,7 +721,7 @@ def encode(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, image
     """encode_batch on one image -> the JPEG file as bytes"""
     return encode_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                               image_size=image_size)],
-                        result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
+                        result=_batch_result(result), optimize=optimize,
                         huffman=huffman, restart_interval=restart_interval, restart_in_rows=restart_in_rows)[0]
 
 
@@ -750,6 +783,14 @@ def _file_frames(images, result, opts, optimize, huffman, who):
                                               0 if opts is None else _scan_interval(opts[i], vh, vv, size))
                       for vh, vv in variants])
     return parts
+
+
+def _stage_files(workspace, key, parts, scratch_bytes, dev, torch):
+    """workspace.files for `key`: the marker bytes `parts` (_marker_blob) and the scratch of a whole-file run in device
+    memory.  A captured graph goes on pointing into both, so they live as long as the workspace"""
+    buf, frames, fixed = _marker_blob(_hip(), parts, dev, torch)
+    workspace.files = dict(key=key, buf=buf, frames=frames, fixed=fixed,
+                           scratch=torch.empty(max(1, scratch_bytes), dtype=torch.uint8, device=dev))
 
 
 def encode_file_batch(images, *, result=None, optimize=True, huffman=None, outs=None, workspace: Workspace | None = None,
@@ -815,18 +856,13 @@ def _encode_progressive_batch(images, result, scans, outs, workspace, who, opts,
            tuple(_key(job, 0, 0) for job in jobs), tuple(tuple(h) for h in heads), str(dev))
     if workspace is None:
         workspace = Workspace()
-    if workspace.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call with the same "
-                               f"geometry, scripts and markers (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.encode_progressive_prepare(jobs, popts, workspace.buf.data_ptr(), workspace.nbytes,
-                                       torch.cuda.current_stream(dev).cuda_stream)
-        buf, frames, fixed = _marker_blob(hip, [[(head,) for head in variants] for variants in heads], dev, torch)
-        workspace.files = dict(key=key, buf=buf, frames=frames, scratch=torch.empty(max(1, scratch_bytes), dtype=torch.uint8, device=dev),
-                               fixed=fixed)
-        workspace.key = key
+
+    def prepare(ptr, nbytes, stream):
+        hip.encode_progressive_prepare(jobs, popts, ptr, nbytes, stream)
+        _stage_files(workspace, key, [[(head,) for head in variants] for variants in heads], scratch_bytes, dev, torch)
+
+    workspace = _prepared(workspace, key, total, dev, prepare, who,
+                          "with the same geometry, scripts and markers (workspace=...)")
     fs = workspace.files
     bufs = _encode_outs(outs, images, per, dev, lambda i, inf, blocks: fs["fixed"][i] + min(
         inf["max_body_bytes"], 4096 + 600 * inf["nscans"] + 40 * blocks), who, torch)
@@ -853,10 +889,7 @@ def _encode_file_batch(images, result, optimize, huffman, outs, workspace, who, 
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call with the same "
                                f"markers (workspace=...): uploading them copies from the host")
-        buf, frames, fixed = _marker_blob(hip, parts, dev, torch)
-        nbytes = hip.encode_files_scratch_bytes(n)
-        workspace.files = dict(key=fkey, buf=buf, frames=frames, scratch=torch.empty(nbytes, dtype=torch.uint8, device=dev),
-                               fixed=fixed)
+        _stage_files(workspace, fkey, parts, hip.encode_files_scratch_bytes(n), dev, torch)
     fs = workspace.files
     bufs = _encode_outs(outs, images, per, dev, lambda i, inf, blocks: fs["fixed"][i] + 4 * 277 + 2 + min(
         inf["max_segment_bytes"], 4096 + (32 if opts is None else 36) * blocks), who, torch)
@@ -877,16 +910,14 @@ def encode_file(coefs, quants=None, *, hsamp=None, vsamp=None, colorspace=None, 
     if scans is not None:
         r = encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
                                     image_size=image_size)],
-                              result=None if result is None else dict(stop=result["stop"], images=[result]), optimize=optimize,
-                              huffman=huffman, outs=None if out is None else [out], workspace=workspace,
+                              result=_batch_result(result), optimize=optimize, huffman=huffman, outs=_outs_of(out),
+                              workspace=workspace,
                               restart_interval=restart_interval, restart_in_rows=restart_in_rows, scans=list(scans),
                               refinement=refinement)
         return dict(file=r["files"][0], len=r["len"], status=r["status"], tables=None, workspace=r["workspace"])
     r = _encode_file_batch([dict(coefs=coefs, quants=quants, hsamp=hsamp, vsamp=vsamp, colorspace=colorspace,
-                                 image_size=image_size)],
-                           None if result is None else dict(stop=result["stop"], images=[result]), optimize, huffman,
-                           None if out is None else [out], workspace, "encode_file",
-                           _restart_opts(restart_interval, restart_in_rows, 1, "encode_file"))
+                                 image_size=image_size)], _batch_result(result), optimize, huffman, _outs_of(out), workspace,
+                           "encode_file", _restart_opts(restart_interval, restart_in_rows, 1, "encode_file"))
     return dict(file=r["files"][0], len=r["len"], status=r["status"], tables=r["tables"], workspace=r["workspace"])
 
 
@@ -957,22 +988,14 @@ def read_batch(datas, *, outs=None, workspace: Workspace | None = None, device=N
 
 def _read_batch(datas, outs, workspace, device, who, split=False):
     import torch
-    if not isinstance(datas, (list, tuple)) or not datas:
-        raise ValueError(f"{who}: datas must be a non-empty list of files")
-    if outs is not None and len(outs) != len(datas):
-        raise ValueError(f"{who}: one output list (or None) per file")
-    capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        if workspace is None or getattr(workspace, "headers", None) is None or len(workspace.headers) != len(datas):
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on files with "
-                               f"the same headers (workspace=...): parsing a header copies it to the host")
-        if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
-            raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
-        headers = workspace.headers
+    _check_files(datas, outs, who)
+    if torch.cuda.is_current_stream_capturing():
+        headers = _stored_headers(datas, workspace, who, "header", torch)
         if headers[0].get("sof") == 0xC2:                               # a workspace of the progressive route
             if split:
                 raise ValueError(f"{who}: split=True reads sequential files; these are progressive (SOF2)")
             return _read_progressive_batch(datas, outs, workspace, device, who)
+        _check_file_types(datas, who, torch)
     else:
         # a sequential file takes the path below; a batch in which every frame is SOF2 goes to the progressive route
         headers, prog = [], []
@@ -993,58 +1016,86 @@ def _read_batch(datas, outs, workspace, device, who, split=False):
             if split:
                 raise ValueError(f"{who}: split=True reads sequential files; these are progressive (SOF2)")
             return _read_progressive_batch(datas, outs, workspace, device, who)
+    hip = _hip()
+    split = bool(split)
+
+    def per_file(p):
+        opt = hip.read_opts(p["dc"], p["ac"], p["dc_tbl"], p["ac_tbl"], p["restart_interval"])
+        return opt, bytes(opt), p["scan_offset"], dict(huffman=_huffman_of(p), restart_interval=p["restart_interval"])
+
+    return _read_files(datas, outs, workspace, device, who, headers, per_file,
+                       "read-split" if split else "read", "on the same geometry and tables (workspace=...)",
+                       partial(hip.read_batch_info, split=split), partial(hip.read_batch_prepare, split=split),
+                       partial(hip.read_batch, split=split))
+
+
+def _check_files(datas, outs, who):
+    if not isinstance(datas, (list, tuple)) or not datas:
+        raise ValueError(f"{who}: datas must be a non-empty list of files")
+    if outs is not None and len(outs) != len(datas):
+        raise ValueError(f"{who}: one output list (or None) per file")
+
+
+def _check_file_types(datas, who, torch):
+    for i, d in enumerate(datas):
+        if isinstance(d, torch.Tensor):
+            if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_contiguous():
+                raise TypeError(f"{who}: file {i} must be a contiguous one-dimensional uint8 tensor")
+        elif not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError(f"{who}: a file is bytes or a contiguous one-dimensional uint8 tensor")
+
+
+def _stored_headers(datas, workspace, who, parsed, torch, sof2=False):
+    """inside a graph capture nothing is copied to the host: the headers the workspace was prepared with (sof2: with
+    progressive files) stand for those of the files, which must lie on the device"""
+    headers = getattr(workspace, "headers", None)
+    if headers is None or len(headers) != len(datas) or (sof2 and headers[0].get("sof") != 0xC2):
+        raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on files with "
+                           f"the same headers (workspace=...): parsing a {parsed} copies it to the host")
+    if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
+        raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
+    return headers
+
+
+def _read_files(datas, outs, workspace, device, who, headers, per_file, tag, same, info, prepare, run):
+    """what the readers share once the headers are there: the files onto the device, the coefficient outputs and the
+    jobs over them, the workspace step, the run, the status tensor and its per-image views.  per_file(header) -> (the
+    route's opts record of the file, the bytes of it that go into the key, the offset of the bytes the run is pointed
+    at, the fields of the image dict that the route adds); tag and same: the key's tag and the words of _prepared; info, prepare, run: the route's HipQS calls"""
+    import torch
     dev = next((d.device for d in datas if isinstance(d, torch.Tensor) and d.is_cuda), None)
     if dev is None:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     hip = _hip()
-    bufs, jobs, opts, images = [], [], [], []
+    bufs, at, jobs, opts, keyed, images = [], [], [], [], [], []
     for i, (d, p) in enumerate(zip(datas, headers)):
         if isinstance(d, torch.Tensor):
-            if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_contiguous():
-                raise TypeError(f"{who}: file {i} must be a contiguous one-dimensional uint8 tensor")
             if d.is_cuda and d.device != dev:
                 raise ValueError(f"{who}: file {i} is on {d.device}, the batch on {dev}")
             buf = d if d.is_cuda else d.to(dev, non_blocking=True)
         else:
             buf = torch.frombuffer(bytearray(d), dtype=torch.uint8).to(dev)
-        if buf.numel() <= p["scan_offset"]:
+        opt, opt_key, offset, extra = per_file(p)
+        if offset and buf.numel() <= offset:
             raise ValueError(f"{who}: file {i} ends with its SOS header")
         bufs.append(buf)
-        n = len(p["hsamp"])
+        at.append(offset)
+        opts.append(opt)
+        keyed.append(opt_key)
         w, h = p["image_size"]
-        mh, mv = max(p["hsamp"]), max(p["vsamp"])
-        shapes = [(-(-h * p["vsamp"][ci] // (8 * mv)), -(-w * p["hsamp"][ci] // (8 * mh))) for ci in range(n)]
-        if outs is None or outs[i] is None:
-            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
-        else:
-            coefs = list(outs[i])
-            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
-                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
-        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], [None] * n,
-                                   hsamp=p["hsamp"], vsamp=p["vsamp"], colorspace=p["colorspace"] or 1, image_size=(w, h)))
-        opts.append(hip.read_opts(p["dc"], p["ac"], p["dc_tbl"], p["ac_tbl"], p["restart_interval"]))
+        coefs = _coef_outs(outs, i, _block_shapes(w, h, p["hsamp"], p["vsamp"]), dev, who, torch)
+        jobs.append(_device_job(hip, coefs, [None] * len(coefs), hsamp=p["hsamp"], vsamp=p["vsamp"],
+                                colorspace=p["colorspace"] or 1, image_size=(w, h)))
         images.append(dict(coefs=coefs, quants=[q.copy() for q in p["quants"]], hsamp=list(p["hsamp"]),
-                           vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), huffman=_huffman_of(p),
-                           restart_interval=p["restart_interval"]))
-    split = bool(split)
-    _per, total = hip.read_batch_info(jobs, opts, split=split)
-    key = ("read-split" if split else "read",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o) for o in opts)
-    if workspace is None:
-        workspace = Workspace()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if workspace.key != key:
-        if capturing:
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
-                               f"geometry and tables (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.read_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream, split=split)
-        workspace.key = key
+                           vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), **extra))
+    _per, total = info(jobs, opts)
+    key = (tag,) + tuple(_key(job, 0, 0) for job in jobs) + tuple(keyed)
+    workspace = _prepared(workspace, key, total, dev,
+                          lambda ptr, nbytes, stream: prepare(jobs, opts, ptr, nbytes, stream), who, same)
     workspace.headers = headers
     status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
-    hip.read_batch(jobs, [b.data_ptr() + p["scan_offset"] for b, p in zip(bufs, headers)],
-                   [b.numel() - p["scan_offset"] for b, p in zip(bufs, headers)], status.data_ptr(), workspace.buf.data_ptr(),
-                   workspace.nbytes, stream, split=split)
+    run(jobs, [b.data_ptr() + a for b, a in zip(bufs, at)], [b.numel() - a for b, a in zip(bufs, at)], status.data_ptr(),
+        workspace.buf.data_ptr(), workspace.nbytes, torch.cuda.current_stream(dev).cuda_stream)
     for i, im in enumerate(images):
         im["status"] = status[i:i + 1]
     return dict(images=images, status=status, workspace=workspace)
@@ -1053,7 +1104,7 @@ def _read_batch(datas, outs, workspace, device, who, split=False):
 def read(data, *, out=None, workspace: Workspace | None = None, device=None, split=False) -> dict:
     """read_batch on one file -> its image dict (coefs, quants, hsamp, vsamp, colorspace, image_size, huffman,
     restart_interval, status) with the workspace used under `workspace`; split as read_batch takes it"""
-    r = _read_batch([data], None if out is None else [out], workspace, device, "read", split)
+    r = _read_batch([data], _outs_of(out), workspace, device, "read", split)
     return dict(r["images"][0], workspace=r["workspace"])
 
 
@@ -1082,82 +1133,28 @@ def read_progressive_batch(datas, *, outs=None, workspace: Workspace | None = No
 def _read_progressive_batch(datas, outs, workspace, device, who):
     import torch
     from . import jpeg_file
-    if not isinstance(datas, (list, tuple)) or not datas:
-        raise ValueError(f"{who}: datas must be a non-empty list of files")
-    if outs is not None and len(outs) != len(datas):
-        raise ValueError(f"{who}: one output list (or None) per file")
-    for i, d in enumerate(datas):
-        if isinstance(d, torch.Tensor):
-            if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_contiguous():
-                raise TypeError(f"{who}: file {i} must be a contiguous one-dimensional uint8 tensor")
-        elif not isinstance(d, (bytes, bytearray, memoryview)):
-            raise TypeError(f"{who}: a file is bytes or a contiguous one-dimensional uint8 tensor")
-    capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        if workspace is None or getattr(workspace, "headers", None) is None or len(workspace.headers) != len(datas) \
-                or workspace.headers[0].get("sof") != 0xC2:
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on files with "
-                               f"the same headers (workspace=...): parsing a file copies it to the host")
-        if not all(isinstance(d, torch.Tensor) and d.is_cuda for d in datas):
-            raise RuntimeError(f"{who}: inside a graph capture the files must be device tensors")
-        headers = workspace.headers
+    _check_files(datas, outs, who)
+    _check_file_types(datas, who, torch)
+    if torch.cuda.is_current_stream_capturing():
+        headers = _stored_headers(datas, workspace, who, "file", torch, sof2=True)
     else:
         headers = [jpeg_file.parse_progressive(d.cpu().numpy().tobytes() if isinstance(d, torch.Tensor) else bytes(d))
                    for d in datas]
-    dev = next((d.device for d in datas if isinstance(d, torch.Tensor) and d.is_cuda), None)
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     hip = _hip()
-    bufs, jobs, opts, images = [], [], [], []
-    for i, (d, p) in enumerate(zip(datas, headers)):
-        if isinstance(d, torch.Tensor):
-            if d.is_cuda and d.device != dev:
-                raise ValueError(f"{who}: file {i} is on {d.device}, the batch on {dev}")
-            buf = d if d.is_cuda else d.to(dev, non_blocking=True)
-        else:
-            buf = torch.frombuffer(bytearray(d), dtype=torch.uint8).to(dev)
-        bufs.append(buf)
-        n = len(p["hsamp"])
-        w, h = p["image_size"]
-        mh, mv = max(p["hsamp"]), max(p["vsamp"])
-        shapes = [(-(-h * p["vsamp"][ci] // (8 * mv)), -(-w * p["hsamp"][ci] // (8 * mh))) for ci in range(n)]
-        if outs is None or outs[i] is None:
-            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
-        else:
-            coefs = list(outs[i])
-            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
-                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
-        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], [None] * n,
-                                   hsamp=p["hsamp"], vsamp=p["vsamp"], colorspace=p["colorspace"] or 1, image_size=(w, h)))
-        opts.append(hip.read_prog_opts(p["scans"]))
-        images.append(dict(coefs=coefs, quants=[q.copy() for q in p["quants"]], hsamp=list(p["hsamp"]),
-                           vsamp=list(p["vsamp"]), colorspace=p["colorspace"], image_size=(w, h), huffman=None,
-                           scans=list(p["script"]), restart_interval=p["scans"][0]["restart_interval"]))
-    _per, total = hip.read_prog_batch_info(jobs, opts)
-    key = ("read-prog",) + tuple(_key(job, 0, 0) for job in jobs) + tuple(bytes(o._scans) for o in opts)
-    if workspace is None:
-        workspace = Workspace()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if workspace.key != key:
-        if capturing:
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
-                               f"geometry, scans and tables (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.read_prog_batch_prepare(jobs, opts, workspace.buf.data_ptr(), workspace.nbytes, stream)
-        workspace.key = key
-    workspace.headers = headers
-    status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
-    hip.read_prog_batch(jobs, [b.data_ptr() for b in bufs], [b.numel() for b in bufs], status.data_ptr(),
-                        workspace.buf.data_ptr(), workspace.nbytes, stream)
-    for i, im in enumerate(images):
-        im["status"] = status[i:i + 1]
-    return dict(images=images, status=status, workspace=workspace)
+
+    def per_file(p):
+        opt = hip.read_prog_opts(p["scans"])                            # (a record that points to its scans: keyed by them)
+        return opt, bytes(opt._scans), 0, dict(huffman=None, scans=list(p["script"]),
+                                               restart_interval=p["scans"][0]["restart_interval"])
+
+    return _read_files(datas, outs, workspace, device, who, headers, per_file,
+                       "read-prog", "on the same geometry, scans and tables (workspace=...)",
+                       hip.read_prog_batch_info, hip.read_prog_batch_prepare, hip.read_prog_batch)
 
 
 def read_progressive(data, *, out=None, workspace: Workspace | None = None, device=None) -> dict:
     """read_progressive_batch on one file -> its image dict with the workspace used under `workspace`"""
-    r = _read_progressive_batch([data], None if out is None else [out], workspace, device, "read_progressive")
+    r = _read_progressive_batch([data], _outs_of(out), workspace, device, "read_progressive")
     return dict(r["images"][0], workspace=r["workspace"])
 
 
@@ -1202,7 +1199,7 @@ def compress(pixels, *, quality=None, quants=None, hsamp=None, vsamp=None, color
     take it as it is."""
     r = compress_batch([dict(pixels=pixels, quality=quality, quants=quants, hsamp=hsamp, vsamp=vsamp,
                              colorspace=colorspace)], fancy=fancy, downsampling=downsampling,
-                       outs=None if out is None else [out],
+                       outs=_outs_of(out),
                        workspace=workspace, _who="compress")
     return r["images"][0]
 
@@ -1223,8 +1220,7 @@ def compress_batch(images, *, fancy=False, downsampling="box", outs=None, worksp
     arrays.  Returns dict(images=[image dicts], workspace=Workspace)."""
     import torch
     who = _who
-    if not isinstance(images, (list, tuple)) or not images:
-        raise ValueError(f"{who}: images must be a non-empty list of dicts")
+    _check_list(images, who)
     if fancy:
         raise ValueError(f"{who}: fancy=True is refused; libjpeg 9's default downsampling (2x chroma through 16-point "
                          f"scaled DCTs) is downsampling=\"dct\"")
@@ -1232,11 +1228,10 @@ def compress_batch(images, *, fancy=False, downsampling="box", outs=None, worksp
     if outs is not None and len(outs) != len(images):
         raise ValueError(f"{who}: one output list (or None) per image")
     hip = _hip()
-    dev, metas, modes = None, [], []
-    for i, im in enumerate(images):
+    metas, modes = [], []
+
+    def one(i, im, _res):
         w_i = f"{who}: image {i}"
-        if not isinstance(im, dict) or "pixels" not in im:
-            raise ValueError(f"{w_i} must be a dict with pixels")
         modes.append(downsampling if im.get("downsampling") is None else _downsampling(im["downsampling"], w_i))
         px = im["pixels"]
         if not isinstance(px, torch.Tensor) or px.dtype != torch.uint8 or not px.is_cuda:
@@ -1246,10 +1241,6 @@ def compress_batch(images, *, fancy=False, downsampling="box", outs=None, worksp
         n = int(px.shape[2])
         if px.stride(2) != 1 or px.stride(1) != n or (px.shape[0] > 1 and px.stride(0) < px.shape[1] * n):
             raise ValueError(f"{w_i}: pixels must have contiguous rows (stride {px.stride()})")
-        if dev is None:
-            dev = px.device
-        elif px.device != dev:
-            raise ValueError(f"{w_i} is on {px.device}, image 0 on {dev}")
         cs = im.get("colorspace")
         cs = (1 if n == 1 else 3) if cs is None else int(cs)
         if (n == 1 and cs != 1) or (n == 3 and cs not in (2, 3)):
@@ -1260,38 +1251,24 @@ def compress_batch(images, *, fancy=False, downsampling="box", outs=None, worksp
             raise ValueError(f"{w_i}: one sampling factor per component")
         if n == 3 and (hs[1:] != [1, 1] or vs[1:] != [1, 1] or (hs[0], vs[0]) not in ((1, 1), (2, 1), (1, 2), (2, 2), (4, 1))):
             raise ValueError(f"{w_i}: sampling {hs} x {vs}: chroma must be 1x1 and luma 1x1, 2x1, 1x2, 2x2 or 4x1")
-        qs = _compress_tables(im, n, w_i)
-        metas.append((px, n, cs, hs, vs, qs))
+        metas.append((px, n, cs, hs, vs, _compress_tables(im, n, w_i)))
+        return px.device
+
+    dev, _stop = _images_on_one_device(images, None, who, ("pixels",), one, torch)
     jobs, results = [], []
     for i, (px, n, cs, hs, vs, qs) in enumerate(metas):
         h, w = int(px.shape[0]), int(px.shape[1])
-        mh, mv = (1, 1) if n == 1 else (max(hs), max(vs))
-        shapes = [(-(-h * (1 if n == 1 else vs[ci]) // (8 * mv)), -(-w * (1 if n == 1 else hs[ci]) // (8 * mh)))
-                  for ci in range(n)]
-        if outs is None or outs[i] is None:
-            coefs = [torch.empty((hb, wb, 64), dtype=torch.int16, device=dev) for hb, wb in shapes]
-        else:
-            coefs = list(outs[i])
-            if len(coefs) != n or _check_tensors(coefs, torch, who=f"{who}: output {i}") != dev:
-                raise ValueError(f"{who}: output {i} must be {n} tensors on {dev}")
-        jobs.append(hip.device_job([t.data_ptr() for t in coefs], [tuple(t.shape[:2]) for t in coefs], qs, hsamp=hs,
-                                   vsamp=vs, colorspace=cs, image_size=(w, h)))
+        coefs = _coef_outs(outs, i, _block_shapes(w, h, hs, vs), dev, who, torch)
+        jobs.append(_device_job(hip, coefs, qs, hsamp=hs, vsamp=vs, colorspace=cs, image_size=(w, h)))
         results.append(dict(coefs=coefs, quants=[q.copy() for q in qs], hsamp=hs, vsamp=vs, colorspace=cs,
                             image_size=(w, h)))
     opts = modes if any(m != "box" for m in modes) else None      # (all box: the calls without opts)
     _per, total = hip.compress_batch_info(jobs, opts=opts)
     key = ("compress",) + tuple(_key(job, 0, 0) + (mode,) for job, mode in zip(jobs, modes))
-    if workspace is None:
-        workspace = Workspace()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if workspace.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who}: inside a graph capture the workspace must come from an earlier call on the same "
-                               f"geometry and tables (workspace=...): preparing one synchronises")
-        if workspace.nbytes < total or workspace.buf.device != dev:
-            workspace.buf = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        hip.compress_batch_prepare(jobs, workspace.buf.data_ptr(), workspace.nbytes, stream, opts=opts)
-        workspace.key = key
+    workspace = _prepared(workspace, key, total, dev,
+                          lambda ptr, nbytes, stream: hip.compress_batch_prepare(jobs, ptr, nbytes, stream, opts=opts),
+                          who, "on the same geometry and tables (workspace=...)")
     pitches = [int(m[0].stride(0)) if m[0].shape[0] > 1 else int(m[0].shape[1]) * m[1] for m in metas]
-    hip.compress_batch(jobs, [m[0].data_ptr() for m in metas], pitches, workspace.buf.data_ptr(), workspace.nbytes, stream)
+    hip.compress_batch(jobs, [m[0].data_ptr() for m in metas], pitches, workspace.buf.data_ptr(), workspace.nbytes,
+                       torch.cuda.current_stream(dev).cuda_stream)
     return dict(images=results, workspace=workspace)
